@@ -5,7 +5,11 @@ Default (the driver's contract): BASELINE.json config 2 — full_1d fp16,
 B=8 H=16 d=64 Nq=Nk=4096, forward — metric "fwd TFLOP/s per GPU + MFMA util %".
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--shard|--weak]
-                  [--no-cpu-baseline]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes work
+of its own beside the timed steps: the CPU baseline (`cpu_baseline` in the line).  --dump-outputs
+DIR writes what the last timed step returned as DIR/<name>.npy (see dump_outputs).
 
 For N>1: one process per GPU, each rank runs its own shard of batch×head
 slices (no data-path collective; a gloo barrier / max-reduce over CPU tensors
@@ -231,6 +235,25 @@ def load_traffic(workload_key: str):
         return None, 0
 
 
+DUMP_MAX_ELEMS = 1 << 20   # per array: at most 6 arrays of 4-8 bytes an element, far under 64 MB in all
+
+
+def dump_outputs(path: str, outputs: dict, rank: int, world: int) -> None:
+    """Write each output of the last timed step as path/<name>.npy (<name>.rank<r>.npy when there is
+    more than one rank), fp16 / fp32 as float32 and fp64 as float64.  An array of more than
+    DUMP_MAX_ELEMS elements is written as a fixed sample: the elements at
+    default_rng(0).integers(0, numel, DUMP_MAX_ELEMS) of the flattened array, so two runs with the
+    same arguments (the inputs are seeded) write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.random.default_rng(0).integers(0, flat.numel(), DUMP_MAX_ELEMS)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -245,9 +268,15 @@ def main():
                     help="split the config's batch across ranks (strong scaling; the default)")
     ap.add_argument("--weak", dest="weak", action="store_true",
                     help="every rank runs the whole config batch (weak scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline work")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not part of the headline figure: the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline work (--full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -293,13 +322,13 @@ def main():
     bwd_flops_rank = 2.0 * (3 * d + 2 * d) * pairs_rank if bwd else 0.0
     step_flops_rank = fwd_flops_rank + bwd_flops_rank
 
-    o = l = m = None
+    o = l = m = grads = None
 
     def step():
-        nonlocal o, l, m
+        nonlocal o, l, m, grads
         o, l, m = _call_forward(cfg, q, k, v)
         if bwd:
-            _call_backward(cfg, q, k, v, o, l, m, do)
+            grads = _call_backward(cfg, q, k, v, o, l, m, do)
 
     tw = time.perf_counter()
     for _ in range(args.warmup):
@@ -340,6 +369,12 @@ def main():
         total_flops = step_flops_rank * args.steps
     value = total_flops / elapsed / 1e12
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs:
+        outputs = {"o": o, "l": l, "m": m}
+        if bwd:
+            outputs.update(zip(("dq", "dk", "dv"), grads))
+        dump_outputs(args.dump_outputs, outputs, rank, world)
 
     if rank == 0:
         dname = DTYPE_NAME[dt]
@@ -388,7 +423,7 @@ def main():
             "mfma_util_pct": round(100.0 * achieved / peak, 2),
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_budget)
         print(json.dumps(line), flush=True)
     if dist:

@@ -105,3 +105,24 @@ def test_bench_batch_shard_split():
             assert bench.rank_batch(cfg, world, 0, weak=True) == (b_total, "weak")
     assert bench.rank_batch(bench.CONFIGS["c2"], 2, 1) == (64, "strong")
     assert bench.rank_batch(bench.CONFIGS["c4"], 8, 7) == (128, "strong")
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: small arrays whole, large ones as the same fixed sample on every
+    call; fp16 / fp32 as float32, fp64 as float64; one file per name (per name and rank past one)."""
+    import bench
+    n = bench.DUMP_MAX_ELEMS
+    big = torch.arange(2 * n + 3, dtype=torch.float32).reshape(1, -1)
+    outs = {"o": big, "l": torch.tensor([[1.5, -2.0]], dtype=torch.float16),
+            "m": torch.tensor([0.25], dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), outs, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), outs, 0, 1)
+    assert sorted(os.listdir(tmp_path / "a")) == ["l.npy", "m.npy", "o.npy"]
+    o = np.load(tmp_path / "a" / "o.npy")
+    assert o.dtype == np.float32 and o.shape == (n,) and np.array_equal(o, np.load(tmp_path / "b" / "o.npy"))
+    assert np.array_equal(o, np.random.default_rng(0).integers(0, 2 * n + 3, n).astype(np.float32))
+    l, m = np.load(tmp_path / "a" / "l.npy"), np.load(tmp_path / "a" / "m.npy")
+    assert l.dtype == np.float32 and l.tolist() == [1.5, -2.0]
+    assert m.dtype == np.float64 and m.tolist() == [0.25]
+    bench.dump_outputs(str(tmp_path / "c"), {"o": outs["l"]}, 1, 2)
+    assert os.listdir(tmp_path / "c") == ["o.rank1.npy"]

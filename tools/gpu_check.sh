@@ -14,6 +14,8 @@ if [ -z "$SKIP_SMOKE" ]; then
   ok $c || exit $c
 fi
 if [ -z "$SKIP_BENCH" ]; then
+  # the CPU baseline is part of bench.py --full only
+  BENCH_ARGS=${BENCH_ARGS:---full --steps 10 --warmup 3 --cpu-budget 8}
   timeout -k 10 600 python bench.py ${BENCH_ARGS:---steps 10 --warmup 3 --cpu-budget 8} > gpurun_out/bench.log 2>&1
   c=$?; echo "bench exit $c"; tail -3 gpurun_out/bench.log
 fi

@@ -37,7 +37,7 @@ for cfg in ${CONFIGS:-c2}; do
   python3 tools/pmc_traffic.py $cfg "$rx" $OUT/pmc_$cfg --out $OUT/traffic_$cfg.json > $OUT/traffic_$cfg.log 2>&1
   echo "[$cfg] traffic: $(cat $OUT/traffic_$cfg.log)"
   cp $OUT/traffic_$cfg.json profiles/ 2>/dev/null
-  timeout -k 10 600 python3 bench.py --config $cfg ${BENCH_EXTRA} > $OUT/${cfg}_bench.json 2> $OUT/bench_$cfg.err
+  timeout -k 10 600 python3 bench.py --full --config $cfg ${BENCH_EXTRA} > $OUT/${cfg}_bench.json 2> $OUT/bench_$cfg.err
   c=$?; echo "[$cfg] bench exit $c: $(cat $OUT/${cfg}_bench.json)"; [ $c -eq 0 ] || exit $c
 done
 exit 0
