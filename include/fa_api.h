@@ -90,6 +90,25 @@ int fa_forward(void* stream, const fa_problem* p,
                const void* Q, const void* K, const void* V,
                void* O, void* l, void* m);
 
+/* Split-key forward: fp16 problems with one query block (at most 128 queries), max(d, v_d) <= 128
+ * and a rule-bounded key range of at least 2048 keys cut that range into chunks, one workgroup
+ * per (slice, chunk), and merge the partial results (fa_forward itself never splits; it keeps one
+ * workgroup per slice for such shapes).  The routing is a pure function of the problem WITHOUT b,
+ * so a slice's result does not depend on how the batch is sharded.
+ *
+ * fa_forward_workspace_bytes (host-only): bytes of device scratch fa_forward_ws needs; 0 when
+ *   the problem is outside the split envelope.
+ * fa_forward_ws: with fa_forward_workspace_bytes(p) == 0 exactly fa_forward (the workspace is
+ *   ignored); otherwise the split path, or FA_ERR_WORKSPACE_TOO_SMALL (nothing is written).
+ * fa_forward_split_plan (host-only): out[0] = number of chunks (0 outside the envelope),
+ *   out[1] = keys per chunk, out[2..3] = key range [kb, ke) of the query block. */
+size_t fa_forward_workspace_bytes(const fa_problem* p);
+int fa_forward_ws(void* stream, const fa_problem* p,
+                  const void* Q, const void* K, const void* V,
+                  void* O, void* l, void* m,
+                  void* workspace, size_t workspace_bytes);
+int fa_forward_split_plan(const fa_problem* p, int32_t out[4]);
+
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);

@@ -29,6 +29,9 @@ EXPORTED_SYMBOLS = (
     "fa_sync_mode_from_string",
     "fa_validate",
     "fa_forward",
+    "fa_forward_workspace_bytes",
+    "fa_forward_ws",
+    "fa_forward_split_plan",
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_estimate_forward_flops",
@@ -84,6 +87,12 @@ def _declare(lib):
     lib.fa_validate.restype = ctypes.c_int
     lib.fa_forward.argtypes = [vp, P, vp, vp, vp, vp, vp, vp]
     lib.fa_forward.restype = ctypes.c_int
+    lib.fa_forward_workspace_bytes.argtypes = [P]
+    lib.fa_forward_workspace_bytes.restype = ctypes.c_size_t
+    lib.fa_forward_ws.argtypes = [vp, P, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
+    lib.fa_forward_ws.restype = ctypes.c_int
+    lib.fa_forward_split_plan.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
+    lib.fa_forward_split_plan.restype = ctypes.c_int
     lib.fa_backward_workspace_bytes.argtypes = [P]
     lib.fa_backward_workspace_bytes.restype = ctypes.c_size_t
     lib.fa_backward.argtypes = [vp, P, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]

@@ -175,6 +175,47 @@ WsLayout ws_layout(const fa_problem* p) {
   return w;
 }
 
+// Split-key routing of the fp16 forward.  A pure function of the problem WITHOUT b,
+// so a slice's result does not depend on how the batch is sharded.
+constexpr int32_t kSplitMaxQ = 128;        // one query block of the partial kernel
+constexpr int32_t kSplitMinRange = 2048;   // shorter key ranges never split
+constexpr int32_t kSplitTile = 64;         // the kernels' key tile
+constexpr int32_t kSplitMaxChunks = 64;    // bounds the workspace beside K and V
+
+struct SplitPlan {
+  int32_t nchunks, chunk, kb, ke, k_first;
+};
+
+SplitPlan split_plan(const fa_problem* p) {
+  SplitPlan s = {0, 0, 0, 0, 0};
+  if (fa_validate(p) != FA_OK || p->dtype != FA_F16 || p->d > 128 || p->v_d > 128) return s;
+#ifdef FA_DIAG
+  // a pinned forward variant keeps measuring the kernel it names
+  if (fa::diag_variant("FA_FWD_VARIANT") >= 0) return s;
+#endif
+  const int64_t nq = seq_elems(p->q_seq, p->seq_dims);
+  if (nq < 1 || nq > kSplitMaxQ) return s;
+  fa::Rule r;
+  build_rule(p, &r);
+  if (r.k.n < 1) return s;
+  fa::k_range_for_q_block(r, 0, (int32_t)nq - 1, &s.kb, &s.ke);
+  if (s.ke - s.kb < kSplitMinRange) return s;
+  s.k_first = s.kb / kSplitTile * kSplitTile;
+  const int32_t span = s.ke - s.k_first;
+  // a partial is nq*(v_d+3) floats per chunk beside chunk*(d+v_d) halfs of K/V: above 64 queries the
+  // chunks are twice as long, so the partials stay near an eighth of the K/V bytes
+  const int32_t min_chunk = nq <= 64 ? 512 : 1024;
+  const int32_t capped = ((span + kSplitMaxChunks - 1) / kSplitMaxChunks + kSplitTile - 1) / kSplitTile * kSplitTile;
+  s.chunk = capped > min_chunk ? capped : min_chunk;
+  s.nchunks = (span + s.chunk - 1) / s.chunk;
+  return s;
+}
+
+size_t split_ws_bytes(const fa_problem* p, const SplitPlan& s) {
+  const size_t nq = (size_t)seq_elems(p->q_seq, p->seq_dims);
+  return align_up((size_t)p->b * (size_t)s.nchunks * nq * (size_t)(p->v_d + 3) * sizeof(float));
+}
+
 }  // namespace
 
 extern "C" {
@@ -254,6 +295,57 @@ int fa_forward(void* stream, const fa_problem* p, const void* Q, const void* K, 
   }
   if (e != hipSuccess)
     return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+  return FA_OK;
+}
+
+size_t fa_forward_workspace_bytes(const fa_problem* p) {
+  const SplitPlan s = split_plan(p);
+  return s.nchunks ? split_ws_bytes(p, s) : 0;
+}
+
+int fa_forward_split_plan(const fa_problem* p, int32_t out[4]) {
+  int st = fa_validate(p);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const SplitPlan s = split_plan(p);
+  out[0] = s.nchunks;
+  out[1] = s.chunk;
+  out[2] = s.kb;
+  out[3] = s.ke;
+  return FA_OK;
+}
+
+int fa_forward_ws(void* stream, const fa_problem* p, const void* Q, const void* K, const void* V, void* O, void* l,
+                  void* m, void* workspace, size_t workspace_bytes) {
+  const SplitPlan sp = split_plan(p);
+  if (sp.nchunks == 0) return fa_forward(stream, p, Q, K, V, O, l, m);
+  if (!workspace || workspace_bytes < split_ws_bytes(p, sp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "forward workspace is smaller than fa_forward_workspace_bytes()");
+  FA_DIAG_COUNT(0);
+  if (p->b == 0) return FA_OK;
+  fa::SplitArgs sa;
+  fa::FwdArgs& a = sa.f;
+  a.d = p->d; a.v_d = p->v_d;
+  a.scale = 1.0 / sqrt((double)p->d);
+  build_rule(p, &a.rule);
+  sa.nchunks = sp.nchunks; sa.chunk = sp.chunk; sa.k_first = sp.k_first; sa.k_end = sp.ke;
+  const int64_t nq = a.rule.q.n, nk = a.rule.k.n;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // one launch pair covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
+  const int64_t bmax = fa::fwd_f16_splitk_max_batch(sa);
+  for (int64_t b0 = 0; b0 < p->b; b0 += bmax) {
+    a.b = p->b - b0 < bmax ? p->b - b0 : bmax;
+    a.Q = static_cast<const uint16_t*>(Q) + b0 * p->d * nq;
+    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
+    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
+    a.O = static_cast<uint16_t*>(O) + b0 * p->v_d * nq;
+    a.l = static_cast<float*>(l) + b0 * nq;
+    a.m = static_cast<uint16_t*>(m) + b0 * nq;
+    sa.ws = static_cast<float*>(workspace) + b0 * sp.nchunks * (p->v_d + 3) * nq;
+    const hipError_t e = fa::launch_fwd_f16_splitk(sa, s);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+  }
   return FA_OK;
 }
 
@@ -381,7 +473,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16, mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}";
 }
 
 }  // extern "C"

@@ -43,6 +43,16 @@ struct BwdArgs {
   Rule rule;
 };
 
+// split-key fp16 forward (fa_fwd_f16_splitk.hip): the plan of fa_api.hip plus the workspace
+struct SplitArgs {
+  FwdArgs f;
+  float* ws;        // [b][nchunks][v_d + 3][nq] floats
+  int32_t nchunks;  // chunks of the key range, >= 2
+  int32_t chunk;    // keys per chunk (a multiple of the 64-key tile)
+  int32_t k_first;  // first key of chunk 0 (tile-aligned, <= the range's first key)
+  int32_t k_end;    // one past the range's last key
+};
+
 // generic (any dtype) path — fa_generic.hip
 hipError_t launch_fwd_generic(int dtype, const FwdArgs& a, hipStream_t s);
 hipError_t launch_bwd_generic(int dtype, const BwdArgs& a, hipStream_t s);
@@ -79,6 +89,11 @@ hipError_t launch_fwd_f16_wide(const FwdArgs& a, hipStream_t s);
 // persistent band forward for 1d unit-stride local windows, 32 < max(d, v_d) <= 64 — fa_fwd_f16_band.hip
 bool fwd_f16_band_supported(const FwdArgs& a);
 hipError_t launch_fwd_f16_band(const FwdArgs& a, hipStream_t s);
+// split-key fp16 forward for one query block against a long key range: a partial kernel per
+// (slice, key chunk) and a merge kernel — fa_fwd_f16_splitk.hip.  At most
+// fwd_f16_splitk_max_batch() slices per call (grid limits).
+int64_t fwd_f16_splitk_max_batch(const SplitArgs& sa);
+hipError_t launch_fwd_f16_splitk(const SplitArgs& sa, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

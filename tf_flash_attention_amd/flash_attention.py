@@ -189,9 +189,16 @@ def attention_forward(policy: str, seq_dims: int, Q, K, V, sync_mode, window_siz
     prob = _lib.make_problem(dt, _POLICIES[policy], seq_dims, sid, _prod(Qb), Qs, Ks, Q_ch, V_ch,
                              window_size, log2_stride_size, is_causal)
     L = _lib.lib()
+    # few queries against a long key range: the split-key path needs scratch for its partials
+    ws_bytes = int(L.fa_forward_workspace_bytes(prob))
     with torch.cuda.device(Q.device):
-        st = L.fa_forward(_stream_handle(Q.device), prob, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
-                          O.data_ptr(), l.data_ptr(), m.data_ptr())
+        if ws_bytes:
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=Q.device)
+            st = L.fa_forward_ws(_stream_handle(Q.device), prob, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                 O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+        else:
+            st = L.fa_forward(_stream_handle(Q.device), prob, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                              O.data_ptr(), l.data_ptr(), m.data_ptr())
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return O, l, m

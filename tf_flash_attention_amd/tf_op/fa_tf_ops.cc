@@ -16,7 +16,8 @@
 // Internal("Failed to launch the Forward kernel: <str>(<code>)") (forward.cc:383-385).
 // Differences: no output memsets and no Br_occupancy temp (the kernels
 // write every O/l/m element); the backward scratch is an allocate_temp of
-// fa_backward_workspace_bytes(); Estimate*Flops returns rule-exact algorithmic
+// fa_backward_workspace_bytes(), the split-key forward's one of
+// fa_forward_workspace_bytes(); Estimate*Flops returns rule-exact algorithmic
 // FLOPs instead of the reference's tile-issued count.
 //
 // This image has no TensorFlow, so this file is built only where one is present.
@@ -210,7 +211,13 @@ class FaForwardOp : public OpKernel {
     OP_REQUIRES_OK(ctx, ctx->allocate_output(0, o_shape, &O));
     OP_REQUIRES_OK(ctx, ctx->allocate_output(1, lm_shape, &l));  // float for the Float16 ops, else T
     OP_REQUIRES_OK(ctx, ctx->allocate_output(2, lm_shape, &m));
-    const int rc = fa_forward(StreamOf(ctx), &p, Q.data(), K.data(), V.data(), O->data(), l->data(), m->data());
+    // few queries against a long key range take the split-key path, whose partials need scratch;
+    // with 0 bytes fa_forward_ws is fa_forward
+    const size_t ws_bytes = fa_forward_workspace_bytes(&p);
+    Tensor ws;
+    OP_REQUIRES_OK(ctx, ctx->allocate_temp(DT_UINT8, TensorShape({static_cast<int64_t>(ws_bytes > 0 ? ws_bytes : 1)}), &ws));
+    const int rc = fa_forward_ws(StreamOf(ctx), &p, Q.data(), K.data(), V.data(), O->data(), l->data(), m->data(),
+                                 ws.data(), ws_bytes);
     OP_REQUIRES(ctx, rc == FA_OK,
                 errors::Internal("Failed to launch the Forward kernel: ", fa_error_string(rc), "(", rc, ")"));
   }
