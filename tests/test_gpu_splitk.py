@@ -113,6 +113,24 @@ def test_ragged_key_length(d):
     _split_case("causal", "scale_end", (33,), (2603,), d, d, seed=29)
 
 
+# The <D, POL, FAST> instances of splitk_partial_kernel that no case above reaches (the others are
+# D 64 / 128 under POL 0 / 1 with both stagings, D 64 POL 2 FAST and D 32 POL 0 element-wise): the
+# 32-channel tile under every rule form, and the per-element rule check (POL 2) with element-wise
+# staging at D = 64 and with both stagings at D = 128.  FAST needs d == v_d == D and nk % 8 == 0.
+@pytest.mark.parametrize("policy,mode,qs,ks,d,vd,ws,ls", [
+    ("full", "none_front", (33,), (2600,), 32, 32, 1, 0),       # D 32, POL 0, FAST
+    ("causal", "scale_end", (64,), (4200,), 32, 32, 1, 0),      # D 32, POL 1, FAST
+    ("causal", "scale_end", (33,), (2603,), 24, 17, 1, 0),      # D 32, POL 1, element-wise
+    ("local", "scale_end", (4, 8), (40, 66), 32, 32, 20, 1),    # D 32, POL 2, FAST
+    ("local", "scale_end", (4, 8), (40, 66), 24, 17, 20, 1),    # D 32, POL 2, element-wise
+    ("local", "scale_end", (4, 8), (40, 66), 64, 48, 20, 1),    # D 64, POL 2, element-wise
+    ("local", "scale_end", (4, 8), (40, 66), 128, 128, 20, 1),  # D 128, POL 2, FAST
+    ("local", "scale_end", (4, 8), (40, 66), 100, 72, 20, 1),   # D 128, POL 2, element-wise
+])
+def test_partial_kernel_instances(policy, mode, qs, ks, d, vd, ws, ls):
+    _split_case(policy, mode, qs, ks, d, vd, ws=ws, ls=ls, seed=31 + d)
+
+
 # ------------------------------------------------------------------ the C ABI directly
 def _inputs(b, d, vd, nq, nk, seed):
     g = torch.Generator(device="cpu").manual_seed(seed)

@@ -108,7 +108,6 @@ __host__ __device__ constexpr int stv_j(int, int p, int g, int i) {
 __host__ __device__ constexpr int stv_part(int, int p, int g, int i) {
   return ((g == 0 && p == 1) || (g == 1 && p == 0)) ? (i & 1) : 0;
 }
-constexpr float kRescaleThr = 8.f;
 // after a 16-B buffer store: a wait state before any VALU may overwrite its data VGPRs (hipcc,
 // ROCm 7.2, emitted such a write as the very next instruction and the stored dword arrived corrupted:
 // DESIGN.md §6 toolchain finding (b); tools/check_store_hazard.py checks the shipped library)

@@ -35,7 +35,6 @@ using namespace mf;
 
 constexpr int kBN = 64;             // keys per tile
 constexpr int kVPad = 1;            // V group row padding, in 16-byte rows
-constexpr float kRescaleThr = 8.f;  // log2 units (cdna_hip_programming.md T13)
 
 // structure flags of the shipped instances (the launcher picks them per shape class)
 constexpr int kFPrio = 2;    // s_setprio 1 for the second half of the waves (guide T5, static form)
@@ -444,19 +443,9 @@ __global__ __launch_bounds__(NW * 64, fast_waves_per_eu(D)) void fwd_f16_fast_ke
           if (v < vd) O[(int64_t)v * nq + qi] = __float2half(acc_o[u][i] * inv);
         }
     }
-    if (h == 0) {
-      float* lo = static_cast<float*>(a.l) + bi * (int64_t)nq;
-      __half* mo = static_cast<__half*>(a.m) + bi * (int64_t)nq;
-      if (l_tot > 0.f) {
-        const __half mT = __float2half(m_max * kLn2);
-        // l relative to the STORED (rounded) m, so exp(s - m)/l is exact downstream
-        lo[qi] = l_tot * __builtin_amdgcn_exp2f(m_run - __half2float(mT) * kLog2e);
-        mo[qi] = mT;
-      } else {
-        lo[qi] = 0.f;
-        mo[qi] = neg_inf_approx<__half>();
-      }
-    }
+    if (h == 0)
+      store_lm(static_cast<float*>(a.l) + bi * (int64_t)nq, static_cast<__half*>(a.m) + bi * (int64_t)nq, qi,
+               l_tot, m_run, m_max);
   }
 }
 

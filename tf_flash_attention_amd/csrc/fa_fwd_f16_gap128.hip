@@ -54,7 +54,6 @@ constexpr int kOffK = 0;                // K ring (the Q image [128][256] lies o
 constexpr int kOffV = kNS * kTile;      // V ring
 constexpr int kSmem = 2 * kNS * kTile;  // 128 KB
 constexpr int kPPW = kTile / 1024 / kNW;  // DMA pieces (1 KB) per wave per tile: 4
-constexpr float kRescaleThr = 8.f;
 
 template <int B, int E, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -656,17 +655,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void fwd_f16_gap128_kernel(FwdArgs a) 
           const int v = 32 * u + (i & 3) + 8 * (i >> 2) + 4 * h;
           if (v < vd) O[(int64_t)v * nq + qi] = __float2half(X.o[u][i] * inv);
         }
-      if (h == 0) {
-        if (l_tot > 0.f) {
-          const __half mT = __float2half(m_max * kLn2);
-          // l relative to the STORED (rounded) m, so exp(s - m)/l is exact downstream
-          lo[qi] = l_tot * __builtin_amdgcn_exp2f(X.m_run - __half2float(mT) * kLog2e);
-          mo[qi] = mT;
-        } else {
-          lo[qi] = 0.f;
-          mo[qi] = neg_inf_approx<__half>();
-        }
-      }
+      if (h == 0) store_lm(lo, mo, qi, l_tot, X.m_run, m_max);
     };
     finish(A, 0);
     finish(B, 1);

@@ -56,7 +56,6 @@ constexpr int kOffK = kD * kQRow;    // Q image [64][256] first (prologue only)
 constexpr int kNS = 3;               // ring slots for K and for V (and staging register sets)
 constexpr int kOffV = kOffK + kNS * kTile;
 constexpr int kSmem = kOffV + kNS * kTile;
-constexpr float kRescaleThr = 8.f;
 
 __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong_kernel(FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -431,19 +430,9 @@ __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong_kernel(FwdArgs a
         if (v < vd) O[(int64_t)v * nq + qi] = __float2half(o[u][i] * inv);
       }
   }
-  if (h == 0) {
-    float* lo = static_cast<float*>(a.l) + bi * (int64_t)nq;
-    __half* mo = static_cast<__half*>(a.m) + bi * (int64_t)nq;
-    if (l_tot > 0.f) {
-      const __half mT = __float2half(m_max * kLn2);
-      // l relative to the STORED (rounded) m, so exp(s - m)/l is exact downstream
-      lo[qi] = l_tot * __builtin_amdgcn_exp2f(m_run - __half2float(mT) * kLog2e);
-      mo[qi] = mT;
-    } else {
-      lo[qi] = 0.f;
-      mo[qi] = neg_inf_approx<__half>();
-    }
-  }
+  if (h == 0)
+    store_lm(static_cast<float*>(a.l) + bi * (int64_t)nq, static_cast<__half*>(a.m) + bi * (int64_t)nq, qi,
+             l_tot, m_run, m_max);
 }
 
 }  // namespace

@@ -58,7 +58,6 @@ constexpr int kOffV = kOffK + kNS * kTile;
 constexpr int kOffQ = kOffV + kNS * kTile;
 constexpr int kSmem = kOffQ + kD * kQRow;  // 160 KB
 constexpr int kCPT = kD * 8 / (kNW * 64);   // 16-B chunks per thread per tile (2)
-constexpr float kRescaleThr = 8.f;
 
 // query blocks a workgroup runs: one (full policy), or the heavy / light pair of an interval rule
 __host__ __device__ inline int64_t pp128_groups(int64_t nqb, int pol) { return pol == 0 ? nqb : (nqb + 1) / 2; }
@@ -435,18 +434,9 @@ __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong128_kernel(FwdArg
           const int v = 32 * u + (i & 3) + 8 * (i >> 2) + 4 * h;
           if (v < vd) O[(int64_t)v * nq + qi] = __float2half(o[u][i] * inv);
         }
-      if (h == 0) {
-        float* lo = static_cast<float*>(a.l) + bi * (int64_t)nq;
-        __half* mo = static_cast<__half*>(a.m) + bi * (int64_t)nq;
-        if (l_tot > 0.f) {
-          const __half mT = __float2half(m_max * kLn2);
-          lo[qi] = l_tot * __builtin_amdgcn_exp2f(m_run - __half2float(mT) * kLog2e);
-          mo[qi] = mT;
-        } else {
-          lo[qi] = 0.f;
-          mo[qi] = neg_inf_approx<__half>();
-        }
-      }
+      if (h == 0)
+        store_lm(static_cast<float*>(a.l) + bi * (int64_t)nq, static_cast<__half*>(a.m) + bi * (int64_t)nq, qi,
+                 l_tot, m_run, m_max);
     }
   };
   run_block(IC<0>{}, (int)(nqb - 1 - j) * kBM);

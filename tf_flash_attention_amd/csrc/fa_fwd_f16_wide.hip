@@ -41,7 +41,6 @@ constexpr int kTile = kD * kBN * 2;    // 32 KB
 constexpr int kOffV = 2 * kTile;       // K ring [0, 64 KB), V ring [64 KB, 128 KB)
 constexpr int kSmem = 4 * kTile;       // 128 KB (the Q image, 64 KB, aliases the K ring)
 constexpr int kCPT = kD * 8 / (kNW * 64);  // 16-B chunks of a tile per thread: 8
-constexpr float kRescaleThr = 8.f;
 
 template <int POL, bool ALN>
 __global__ __launch_bounds__(kNW * 64, 1) void fwd_f16_wide_kernel(FwdArgs a) {
@@ -343,19 +342,9 @@ __global__ __launch_bounds__(kNW * 64, 1) void fwd_f16_wide_kernel(FwdArgs a) {
         if (v < vd) O[(int64_t)v * nq + qi] = __float2half(o[u][i] * inv);
       }
   }
-  if (h == 0) {
-    float* lo = static_cast<float*>(a.l) + bi * (int64_t)nq;
-    __half* mo = static_cast<__half*>(a.m) + bi * (int64_t)nq;
-    if (l_tot > 0.f) {
-      const __half mT = __float2half(m_max * kLn2);
-      // l relative to the STORED (rounded) m, so exp(s - m)/l is exact downstream
-      lo[qi] = l_tot * __builtin_amdgcn_exp2f(m_run - __half2float(mT) * kLog2e);
-      mo[qi] = mT;
-    } else {
-      lo[qi] = 0.f;
-      mo[qi] = neg_inf_approx<__half>();
-    }
-  }
+  if (h == 0)
+    store_lm(static_cast<float*>(a.l) + bi * (int64_t)nq, static_cast<__half*>(a.m) + bi * (int64_t)nq, qi,
+             l_tot, m_run, m_max);
 }
 
 }  // namespace

@@ -90,7 +90,8 @@ hipError_t launch_fwd_f16_wide(const FwdArgs& a, hipStream_t s);
 bool fwd_f16_band_supported(const FwdArgs& a);
 hipError_t launch_fwd_f16_band(const FwdArgs& a, hipStream_t s);
 // split-key fp16 forward for one query block against a long key range: a partial kernel per
-// (slice, key chunk) and a merge kernel — fa_fwd_f16_splitk.hip.  At most
+// (slice, key chunk), which runs the general kernel's key loop (fa_fwd_f16_core.h) over its chunk,
+// and a merge kernel — fa_fwd_f16_splitk.hip.  At most
 // fwd_f16_splitk_max_batch() slices per call (grid limits).
 int64_t fwd_f16_splitk_max_batch(const SplitArgs& sa);
 hipError_t launch_fwd_f16_splitk(const SplitArgs& sa, hipStream_t s);

@@ -1,12 +1,14 @@
 // fa_mfma.h — gfx950 MFMA-kernel helpers shared by the fp16 forward and backward
-// translation units: vector types, LDS transposed reads, buffer descriptors and
-// half-wave reductions.  Device code only (gfx950).
+// translation units: vector types, LDS transposed reads, buffer descriptors,
+// half-wave reductions and the fp16 forward's l / m store.  Device code only (gfx950).
 #ifndef TF_FLASH_ATTENTION_AMD_FA_MFMA_H_
 #define TF_FLASH_ATTENTION_AMD_FA_MFMA_H_
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+
+#include "fa_device.h"
 
 namespace fa {
 namespace mf {
@@ -29,6 +31,9 @@ typedef __attribute__((address_space(3))) float lds_f_t;
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
+// lazy rescale of the fp16 forwards' online softmax: the running reference moves only when a
+// tile's row max exceeds it by more than this (log2 units, so P <= 2^8; cdna_hip_programming.md T13)
+constexpr float kRescaleThr = 8.f;
 
 template <int V>
 struct IC {
@@ -39,6 +44,10 @@ struct IC {
 __device__ __forceinline__ half4 tr_read(const lds_char_t* p) {
   const v4i16 t = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16_t*)p);
   return __builtin_bit_cast(half4, t);
+}
+__device__ __forceinline__ half4 tr_read(const lds_char_t* base, uint32_t off) { return tr_read(base + off); }
+__device__ __forceinline__ half4 read_b64(const lds_char_t* base, uint32_t off) {
+  return *reinterpret_cast<const __attribute__((address_space(3))) half4*>(base + off);
 }
 __device__ __forceinline__ half8 read_b128(const lds_char_t* p) { return *reinterpret_cast<const lds_half8_t*>(p); }
 
@@ -51,6 +60,12 @@ __device__ __forceinline__ float max_pair32(float x) {
 __device__ __forceinline__ float sum_pair32(float x) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// value of lane l^32 (v_permlane32_swap instead of an LDS bpermute)
+__device__ __forceinline__ float xor32(float x) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
 }
 
 // Buffer descriptor over `bytes` bytes at `p`, built from provably wave-uniform
@@ -94,6 +109,21 @@ __device__ __forceinline__ half8 scale8(half8 x, float s) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) x[j] = (_Float16)((float)x[j] * s);
   return x;
+}
+
+// l[q] and m[q] of one query row as the fp16 forwards store them.  l_tot is the row sum relative to
+// m_run and m_max the exact row max (both log2 units); the stored l is relative to the STORED
+// (rounded) m, so exp(s - m)/l is exact downstream.  A row that attends nothing keeps l = 0 and
+// the NegInfApprox m.
+__device__ __forceinline__ void store_lm(float* l, __half* m, int q, float l_tot, float m_run, float m_max) {
+  if (l_tot > 0.f) {
+    const __half mT = __float2half(m_max * kLn2);
+    l[q] = l_tot * __builtin_amdgcn_exp2f(m_run - __half2float(mT) * kLog2e);
+    m[q] = mT;
+  } else {
+    l[q] = 0.f;
+    m[q] = neg_inf_approx<__half>();
+  }
 }
 
 }  // namespace mf
