@@ -121,6 +121,30 @@ int fa_backward(void* stream, const fa_problem* p,
                 void* dQ, void* dK, void* dV,
                 void* workspace, size_t workspace_bytes);
 
+/* Split-key backward: the few-query shapes of the split-key forward also cut the backward's dQ pass
+ * (query-outer: one workgroup per slice for such shapes) into the same key chunks, one workgroup per
+ * (slice, chunk) writing fp32 partials, and sum the partials of a query in chunk order (no atomics:
+ * deterministic).  The prep and the key-outer dK/dV pass are fa_backward's, so dK and dV are bitwise
+ * fa_backward's; dQ differs by fp32 summation order only.  fa_backward itself never splits.  The
+ * routing is a pure function of the problem WITHOUT b, so a slice's result does not depend on how
+ * the batch is sharded.
+ *
+ * fa_backward_split_plan (host-only): the layout of fa_forward_split_plan.  The plan is the
+ *   forward's where in addition max(d, v_d) * (nk + 8) * 2 < 2^31 (a slice's K / V channel rows stay
+ *   inside the dQ kernel's 32-bit buffer offsets); 0 chunks otherwise.
+ * fa_backward_split_workspace_bytes (host-only): bytes of device scratch fa_backward_split needs:
+ *   fa_backward_workspace_bytes(p) with 0 chunks, otherwise that plus b * chunks * d * nq floats
+ *   (rounded up to 256 bytes; the partials follow fa_backward's regions).
+ * fa_backward_split: with 0 chunks exactly fa_backward; otherwise the split path, or
+ *   FA_ERR_WORKSPACE_TOO_SMALL (nothing is written). */
+int fa_backward_split_plan(const fa_problem* p, int32_t out[4]);
+size_t fa_backward_split_workspace_bytes(const fa_problem* p);
+int fa_backward_split(void* stream, const fa_problem* p,
+                      const void* Q, const void* K, const void* V,
+                      const void* O, const void* l, const void* m, const void* dO,
+                      void* dQ, void* dK, void* dV,
+                      void* workspace, size_t workspace_bytes);
+
 /* Algorithmic forward FLOPs 2*(d+v_d)*P, P = rule-allowed (q,k) pairs summed
  * over b (host-only; replaces EstimateForwardFlops, flash_attention.cu:2069-2144,
  * which counted issued tiles instead). */

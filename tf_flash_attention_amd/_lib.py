@@ -34,6 +34,9 @@ EXPORTED_SYMBOLS = (
     "fa_forward_split_plan",
     "fa_backward_workspace_bytes",
     "fa_backward",
+    "fa_backward_split_plan",
+    "fa_backward_split_workspace_bytes",
+    "fa_backward_split",
     "fa_estimate_forward_flops",
     "fa_allowed_pairs",
     "fa_error_string",
@@ -97,6 +100,15 @@ def _declare(lib):
     lib.fa_backward_workspace_bytes.restype = ctypes.c_size_t
     lib.fa_backward.argtypes = [vp, P, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
     lib.fa_backward.restype = ctypes.c_int
+    # (absent from a library built before the split-key backward: tools/lib_ab.py routes such a build in
+    # through using() and calls fa_backward only; the wrappers fail loudly on the missing symbol)
+    if hasattr(lib, "fa_backward_split"):
+        lib.fa_backward_split_plan.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
+        lib.fa_backward_split_plan.restype = ctypes.c_int
+        lib.fa_backward_split_workspace_bytes.argtypes = [P]
+        lib.fa_backward_split_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_backward_split.argtypes = [vp, P, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
+        lib.fa_backward_split.restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

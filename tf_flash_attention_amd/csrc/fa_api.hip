@@ -216,6 +216,30 @@ size_t split_ws_bytes(const fa_problem* p, const SplitPlan& s) {
   return align_up((size_t)p->b * (size_t)s.nchunks * nq * (size_t)(p->v_d + 3) * sizeof(float));
 }
 
+// Split-key routing of the fp16 backward's dQ pass: the forward's plan, where the
+// dQ kernel's 32-bit buffer offsets reach a slice's K / V channel rows (the b-free part of
+// bwd_f16_fast_supported).  Also a pure function of the problem WITHOUT b, and a subset of the
+// forward's plan (in the diagnostic library too: a pinned forward variant turns both off).
+SplitPlan bwd_split_plan(const fa_problem* p) {
+  const SplitPlan none = {0, 0, 0, 0, 0};
+#ifdef FA_DIAG
+  // a pinned backward variant keeps measuring the kernel it names
+  if (fa::diag_variant("FA_BWD_VARIANT") >= 0) return none;
+#endif
+  const SplitPlan s = split_plan(p);
+  if (s.nchunks == 0) return none;
+  const int64_t nk = seq_elems(p->k_seq, p->seq_dims);
+  const int64_t dm = p->d > p->v_d ? p->d : p->v_d;
+  if (dm * (nk + 8) * 2 >= (int64_t(1) << 31)) return none;
+  return s;
+}
+
+// the dQ partials of the split backward: b * nchunks records of d * nq floats, after ws_layout's regions
+size_t bwd_split_part_bytes(const fa_problem* p, const SplitPlan& s) {
+  const size_t nq = (size_t)seq_elems(p->q_seq, p->seq_dims);
+  return align_up((size_t)p->b * (size_t)s.nchunks * (size_t)p->d * nq * sizeof(float));
+}
+
 }  // namespace
 
 extern "C" {
@@ -398,6 +422,69 @@ int fa_backward(void* stream, const fa_problem* p, const void* Q, const void* K,
   return FA_OK;
 }
 
+int fa_backward_split_plan(const fa_problem* p, int32_t out[4]) {
+  int st = fa_validate(p);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const SplitPlan s = bwd_split_plan(p);
+  out[0] = s.nchunks;
+  out[1] = s.chunk;
+  out[2] = s.kb;
+  out[3] = s.ke;
+  return FA_OK;
+}
+
+size_t fa_backward_split_workspace_bytes(const fa_problem* p) {
+  if (fa_validate(p) != FA_OK) return 0;
+  const SplitPlan s = bwd_split_plan(p);
+  return ws_layout(p).total + (s.nchunks ? bwd_split_part_bytes(p, s) : 0);
+}
+
+int fa_backward_split(void* stream, const fa_problem* p, const void* Q, const void* K, const void* V, const void* O,
+                      const void* l, const void* m, const void* dO, void* dQ, void* dK, void* dV, void* workspace,
+                      size_t workspace_bytes) {
+  const SplitPlan sp = bwd_split_plan(p);
+  if (sp.nchunks == 0) return fa_backward(stream, p, Q, K, V, O, l, m, dO, dQ, dK, dV, workspace, workspace_bytes);
+  const WsLayout w = ws_layout(p);
+  if (!workspace || workspace_bytes < w.total + bwd_split_part_bytes(p, sp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
+                     "backward workspace is smaller than fa_backward_split_workspace_bytes()");
+  FA_DIAG_COUNT(1);
+  if (p->b == 0) return FA_OK;
+  fa::BwdSplitArgs sa;
+  fa::BwdArgs& a = sa.b;
+  a.d = p->d; a.v_d = p->v_d;
+  a.scale = 1.0 / sqrt((double)p->d);
+  build_rule(p, &a.rule);
+  sa.nchunks = sp.nchunks; sa.chunk = sp.chunk; sa.k_first = sp.k_first; sa.k_end = sp.ke;
+  const int64_t nq = a.rule.q.n, nk = a.rule.k.n;
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // one call covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
+  const int64_t bmax = fa::bwd_f16_split_max_batch(sa);
+  for (int64_t b0 = 0; b0 < p->b; b0 += bmax) {
+    a.b = p->b - b0 < bmax ? p->b - b0 : bmax;
+    a.Q = static_cast<const uint16_t*>(Q) + b0 * p->d * nq;
+    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
+    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
+    a.O = static_cast<const uint16_t*>(O) + b0 * p->v_d * nq;
+    a.l = static_cast<const float*>(l) + b0 * nq;
+    a.m = static_cast<const uint16_t*>(m) + b0 * nq;
+    a.dO = static_cast<const uint16_t*>(dO) + b0 * p->v_d * nq;
+    a.dQ = static_cast<uint16_t*>(dQ) + b0 * p->d * nq;
+    a.dK = static_cast<uint16_t*>(dK) + b0 * p->d * nk;
+    a.dV = static_cast<uint16_t*>(dV) + b0 * p->v_d * nk;
+    a.ws_dQ = ws + w.dq;  // (the two-pass kernels keep no dQ accumulator)
+    a.ws_D = reinterpret_cast<float*>(ws + w.D) + b0 * nq;
+    a.ws_lse = reinterpret_cast<float*>(ws + w.lse) + b0 * nq;
+    sa.ws_part = reinterpret_cast<float*>(ws + w.total) + b0 * sp.nchunks * p->d * nq;
+    const hipError_t e = fa::launch_bwd_f16_split(sa, s);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
 int64_t fa_allowed_pairs(const fa_problem* p) {
   if (fa_validate(p) != FA_OK) return -1;
   fa::Rule r;
@@ -473,7 +560,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}";
 }
 
 }  // extern "C"

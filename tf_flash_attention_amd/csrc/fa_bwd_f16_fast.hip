@@ -24,6 +24,9 @@
 // against the algorithmic 10d) in exchange for writing dQ exactly once; the
 // single-kernel alternative (fa_bwd_f16.hip) spends that in fp32 atomics, which
 // cap it at ≈ 1.3 TB/s of added bytes (MI355X_MICROARCH.md 'Global float atomics').
+// With one query block against a long key range the dq pass would run one workgroup per slice;
+// launch_bwd_f16_split runs it on one workgroup per (slice, key chunk) instead (bwd_dq_kernel's SPLIT
+// form: fp32 partials) and sums the partials in chunk order (dq_split_reduce_kernel): still no atomics.
 // Masks are rules (fa_rules.h): per-lane index intervals (POL 1: full windows of an
 // interval rule) or the per-element order check (POL 2: strided / 2d local windows), and
 // per-wave tile classes; tiles with no allowed pair are skipped.
@@ -1591,8 +1594,19 @@ struct DqSmem {
 // block index mod OC), recomputing Sᵀ and dPᵀ over all D channels.  ONESET: one staging register set
 // (tile it+1 loaded at the head of step it and stored after its MFMAs, into the slot tile it-1 left)
 // instead of two sets loaded two steps ahead: at D = 256 a set is 64 registers.
-template <int D, int NW, int WPE, int POL, bool ALN, bool PRE = false, bool MSPEC = false, int OC = 1, bool ONESET = false>
-__global__ __launch_bounds__(NW * 64, WPE) void bwd_dq_kernel(BwdArgs a) {
+// SPLIT (one query block against a long key range, BwdSplitArgs): the grid is (slice, key chunk);
+// the workgroup walks only the tiles of its chunk of the block's key range and stores its unscaled
+// fp32 accumulator as the partial record [d][nq] of (slice, chunk); dq_split_reduce_kernel sums them.
+template <bool SPLIT> struct DqArgsOf { using type = BwdArgs; };
+template <> struct DqArgsOf<true> { using type = BwdSplitArgs; };
+__device__ __forceinline__ const BwdArgs& dq_bwd_args(const BwdArgs& x) { return x; }
+__device__ __forceinline__ const BwdArgs& dq_bwd_args(const BwdSplitArgs& x) { return x.b; }
+
+template <int D, int NW, int WPE, int POL, bool ALN, bool PRE = false, bool MSPEC = false, int OC = 1, bool ONESET = false,
+          bool SPLIT = false>
+__global__ __launch_bounds__(NW * 64, WPE) void bwd_dq_kernel(typename DqArgsOf<SPLIT>::type args) {
+  static_assert(!SPLIT || (OC == 1 && !ONESET), "the split form is the one-wave pass at D <= 128");
+  const BwdArgs& a = dq_bwd_args(args);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_char_t* smem = (lds_char_t*)smem_raw;
   using S = DqSmem<D, NW>;
@@ -1610,8 +1624,10 @@ __global__ __launch_bounds__(NW * 64, WPE) void bwd_dq_kernel(BwdArgs a) {
   const uint32_t bidc = xcd_remap(blockIdx.x, gridDim.x);
   const int oc = (int)(bidc % OC), ou0 = oc * (kDO / 32);
   const uint32_t bid = bidc / OC;
-  const int64_t bi = bid / nqb;
-  const int q0 = (int)(nqb - 1 - (bid % nqb)) * kBM;  // latest (heaviest under causal) blocks first
+  uint32_t per_slice = nqb;  // SPLIT: one query block (q0 = 0) and the chunks of its key range
+  if constexpr (SPLIT) per_slice = (uint32_t)args.nchunks;
+  const int64_t bi = bid / per_slice;
+  const int q0 = SPLIT ? 0 : (int)(nqb - 1 - (bid % nqb)) * kBM;  // latest (heaviest under causal) blocks first
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, r = lane & 31;
@@ -1682,8 +1698,13 @@ __global__ __launch_bounds__(NW * 64, WPE) void bwd_dq_kernel(BwdArgs a) {
   const int qlast = min(q0 + kBM, nq) - 1;
   int kb = 0, ke = nk;
   if (POL != 0) k_range_for_q_block(a.rule, q0, qlast, &kb, &ke);
-  const int kt0 = (kb / kBN) * kBN;
-  const int ntiles = (ke > kb) ? (ke - kt0 + kBN - 1) / kBN : 0;
+  int kt0 = (kb / kBN) * kBN;
+  int ntiles = (ke > kb) ? (ke - kt0 + kBN - 1) / kBN : 0;
+  if constexpr (SPLIT) {  // this chunk's share of that range (k_first and chunk are tile-aligned; wave-uniform)
+    kt0 = args.k_first + (int)(bid % per_slice) * args.chunk;
+    __builtin_assume(kt0 % kBN == 0);  // (the per-element key offsets then fold into the tile base)
+    ntiles = (min(kt0 + args.chunk, args.k_end) - kt0 + kBN - 1) / kBN;
+  }
   int klo = 0, kspan = nk, wlo_min = 0, wlo_max = 0, whi_min = nk - 1, whi_max = nk - 1;
   if (POL == 1 && wave_active) {
     int khi;
@@ -1880,6 +1901,19 @@ __global__ __launch_bounds__(NW * 64, WPE) void bwd_dq_kernel(BwdArgs a) {
   }
 
   if (!wave_active || qi >= nq) return;
+  if constexpr (SPLIT) {
+    // the unscaled fp32 partial of (slice, chunk), bid = slice * nchunks + chunk: record [d][nq],
+    // lanes along nq so the stores coalesce; the reduce kernel scales and rounds
+    float* rec = args.ws_part + (int64_t)bid * d * nq;
+#pragma unroll
+    for (int u = 0; u < kDO / 32; ++u)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int c = 32 * u + (i & 3) + 8 * (i >> 2) + 4 * h;
+        if (c < d) rec[(int64_t)c * nq + qi] = dq[u][i];
+      }
+    return;
+  }
   __half* dQ = static_cast<__half*>(a.dQ) + bi * (int64_t)d * nq;
   const float sc = (float)a.scale;
   if (d == D) {  // one buffer store per value (see the dK/dV pass)
@@ -1900,6 +1934,31 @@ __global__ __launch_bounds__(NW * 64, WPE) void bwd_dq_kernel(BwdArgs a) {
       const int c = 32 * (ou0 + u) + (i & 3) + 8 * (i >> 2) + 4 * h;
       if (c < d) dQ[(int64_t)c * nq + qi] = __float2half(dq[u][i] * sc);
     }
+}
+
+// dQ of the split form: one thread per (slice, channel, query), queries fastest.  The chunk partials
+// are added in chunk order in fp32 (no atomics: the result is deterministic and a slice's bits do not
+// depend on the batch), then scaled and rounded as the unsplit epilogue does.  The loads of a group
+// of eight chunks are issued together; only the additions are a chain.
+__global__ __launch_bounds__(256) void dq_split_reduce_kernel(BwdSplitArgs sa) {
+  const BwdArgs& a = sa.b;
+  const int nc = sa.nchunks;
+  const int64_t per = (int64_t)a.d * a.rule.q.n;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= a.b * per) return;
+  const int64_t bi = gid / per;
+  const float* part = sa.ws_part + bi * nc * per + (gid - bi * per);
+  float sum = 0.f;
+  int c = 0;
+  for (; c + 8 <= nc; c += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = part[(c + j) * per];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum += v[j];
+  }
+  for (; c < nc; ++c) sum += part[c * per];
+  static_cast<__half*>(a.dQ)[gid] = __float2half(sum * (float)a.scale);
 }
 
 // ---------------------------------------------------------------------------
@@ -2313,6 +2372,33 @@ hipError_t launch_dq(const BwdArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// the same pass on one workgroup per (slice, key chunk), then the reduce over the chunks.  WPEU: the
+// launch bound of the element-wise staging instances (at D = 64 under two waves per SIMD they spill
+// 8-336 bytes a lane once the tile base is a chunk's, as the unsplit ones do by 16-40; one wave per
+// SIMD holds them in registers)
+template <int D, int NW, int WPE, int WPEU, bool PRE = false, bool MSPEC = false>
+hipError_t launch_dq_split(const BwdSplitArgs& sa, hipStream_t s) {
+  using S = DqSmem<D, NW>;
+  using SplitKernel = void (*)(BwdSplitArgs);
+  const BwdArgs& a = sa.b;
+  const int pol = bwd_pol(a.rule);
+  const SplitKernel kern =
+      bwd_aligned(a) ? (pol == 0   ? bwd_dq_kernel<D, NW, WPE, 0, true, PRE, MSPEC, 1, false, true>
+                        : pol == 1 ? bwd_dq_kernel<D, NW, WPE, 1, true, PRE, MSPEC, 1, false, true>
+                                   : bwd_dq_kernel<D, NW, WPE, 2, true, PRE, MSPEC, 1, false, true>)
+                     : (pol == 0   ? bwd_dq_kernel<D, NW, WPEU, 0, false, PRE, MSPEC, 1, false, true>
+                        : pol == 1 ? bwd_dq_kernel<D, NW, WPEU, 1, false, PRE, MSPEC, 1, false, true>
+                                   : bwd_dq_kernel<D, NW, WPEU, 2, false, PRE, MSPEC, 1, false, true>);
+  hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), S::kTotal);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * sa.nchunks)), dim3(NW * 64), S::kTotal, s, sa);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int64_t threads = a.b * (int64_t)a.d * a.rule.q.n;
+  hipLaunchKernelGGL(dq_split_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, sa);
+  return hipGetLastError();
+}
+
 // 128 < max(d, v_d) <= 256, any alignment and length (the ALN = false instances stage element-wise):
 // the passes at D = 256
 // OC / OCQ = 0: the four-role dK / dV / dQ passes; > 0: the one-wave passes on that many output-channel
@@ -2405,18 +2491,56 @@ bool bwd_f16_fast_supported(const BwdArgs& a) {
          a.b * ((nq + 127) / 128) * 2 < (1ll << 31);
 }
 
-hipError_t launch_bwd_f16_fast(const BwdArgs& a, hipStream_t s) {
+namespace {
+
+// -D and -lse2 of every query; eight queries a thread where the rows allow 16-B loads
+hipError_t launch_prep(const BwdArgs& a, hipStream_t s, bool allow_prep8 = true) {
   const int64_t nrows = a.b * (int64_t)a.rule.q.n;
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  bool prep8 = (a.rule.q.n % 8) == 0 && al16(a.O) && al16(a.dO) && al16(a.ws_D) && al16(a.ws_lse);
-#ifdef FA_DIAG
-  if (diag_variant("FA_BWD_VARIANT") == 1430) prep8 = false;  // the one-query-a-thread prep, for A/B
-#endif
+  const bool prep8 = allow_prep8 && (a.rule.q.n % 8) == 0 && al16(a.O) && al16(a.dO) && al16(a.ws_D) && al16(a.ws_lse);
   if (prep8)
     hipLaunchKernelGGL(bwd_prep8_kernel, dim3((unsigned)((nrows / 8 + kThrPrep - 1) / kThrPrep)), dim3(kThrPrep), 0, s, a);
   else
     hipLaunchKernelGGL(bwd_prep_kernel, dim3((unsigned)((nrows + kThrPrep - 1) / kThrPrep)), dim3(kThrPrep), 0, s, a);
-  hipError_t e = hipGetLastError();
+  return hipGetLastError();
+}
+
+}  // namespace
+
+// Slices per call of launch_bwd_f16_split: every grid (prep, dK/dV, split dQ, reduce) stays below 2^31 blocks.
+int64_t bwd_f16_split_max_batch(const BwdSplitArgs& sa) {
+  const BwdArgs& a = sa.b;
+  const int64_t reduce_blocks = ((int64_t)a.d * a.rule.q.n + 255) / 256;
+  const int64_t dkdv_blocks = 2 * (((int64_t)a.rule.k.n + 127) / 128);  // (the bound of bwd_f16_fast_supported)
+  int64_t per = sa.nchunks > reduce_blocks ? sa.nchunks : reduce_blocks;
+  if (dkdv_blocks > per) per = dkdv_blocks;
+  return ((1ll << 31) - 1) / per;
+}
+
+// One query block (nq <= 128), max(d, v_d) <= 128: the prep and the dK/dV pass launch_bwd_f16_fast runs
+// for the shape, then the one-wave dQ pass split over key chunks and its reduce (the producer /
+// consumer dQ pass holds 160 KB of LDS, one workgroup a CU, and is not split: few queries need
+// occupancy, not the per-workgroup MFMA rate).
+hipError_t launch_bwd_f16_split(const BwdSplitArgs& sa, hipStream_t s) {
+  const BwdArgs& a = sa.b;
+  hipError_t e = launch_prep(a, s);
+  if (e != hipSuccess) return e;
+  if (max(a.d, a.v_d) <= 64) {
+    e = launch_dkdv<64, 4, 2>(a, s);
+    if (e != hipSuccess) return e;
+    return launch_dq_split<64, 4, 2, 1, false, true>(sa, s);
+  }
+  e = launch_dkdv_pc<128>(a, s);
+  if (e != hipSuccess) return e;
+  return launch_dq_split<128, 4, 1, 1, true>(sa, s);
+}
+
+hipError_t launch_bwd_f16_fast(const BwdArgs& a, hipStream_t s) {
+  bool prep8 = true;
+#ifdef FA_DIAG
+  if (diag_variant("FA_BWD_VARIANT") == 1430) prep8 = false;  // the one-query-a-thread prep, for A/B
+#endif
+  hipError_t e = launch_prep(a, s, prep8);
   if (e != hipSuccess) return e;
 #ifdef FA_DIAG
   // FA_BWD_VARIANT=1421: round 4's D = 256 dK/dV pass (two 128-channel chunks, S / dP formed in each)

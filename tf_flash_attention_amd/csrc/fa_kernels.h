@@ -53,6 +53,16 @@ struct SplitArgs {
   int32_t k_end;    // one past the range's last key
 };
 
+// split-key dQ pass of the fp16 backward (fa_bwd_f16_fast.hip): the plan of fa_api.hip plus the partials
+struct BwdSplitArgs {
+  BwdArgs b;
+  float* ws_part;   // [b][nchunks][d][nq] floats: unscaled fp32 dQ partials
+  int32_t nchunks;  // chunks of the key range, >= 2
+  int32_t chunk;    // keys per chunk (a multiple of the 64-key tile)
+  int32_t k_first;  // first key of chunk 0 (tile-aligned, <= the range's first key)
+  int32_t k_end;    // one past the range's last key
+};
+
 // generic (any dtype) path — fa_generic.hip
 hipError_t launch_fwd_generic(int dtype, const FwdArgs& a, hipStream_t s);
 hipError_t launch_bwd_generic(int dtype, const BwdArgs& a, hipStream_t s);
@@ -117,6 +127,12 @@ hipError_t launch_dkdv_k64(const BwdArgs& a, hipStream_t s);
 // two-pass fp16 backward (dK/dV key-outer + dQ query-outer, no atomics) — fa_bwd_f16_fast.hip
 bool bwd_f16_fast_supported(const BwdArgs& a);
 hipError_t launch_bwd_f16_fast(const BwdArgs& a, hipStream_t s);
+// the same backward for one query block (nq <= 128, max(d, v_d) <= 128) against a long key range: the
+// prep and the dK/dV pass as above, then the one-wave dQ pass on one workgroup per (slice, key chunk)
+// writing fp32 partials, and a reduce kernel that sums them in chunk order — fa_bwd_f16_fast.hip.
+// At most bwd_f16_split_max_batch() slices per call (grid limits).
+int64_t bwd_f16_split_max_batch(const BwdSplitArgs& sa);
+hipError_t launch_bwd_f16_split(const BwdSplitArgs& sa, hipStream_t s);
 
 }  // namespace fa
 

@@ -229,12 +229,14 @@ def attention_backward(policy: str, seq_dims: int, Q, K, V, O, l, m, dO, sync_mo
     prob = _lib.make_problem(dt, _POLICIES[policy], seq_dims, sid, _prod(Qb), Qs, Ks, Q_ch, V_ch,
                              window_size, log2_stride_size, is_causal)
     L = _lib.lib()
-    ws_bytes = L.fa_backward_workspace_bytes(prob)
+    # few queries against a long key range: the dQ pass splits over key chunks (more scratch);
+    # everywhere else this is fa_backward and its workspace
+    ws_bytes = L.fa_backward_split_workspace_bytes(prob)
     ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=Q.device)
     with torch.cuda.device(Q.device):
-        st = L.fa_backward(_stream_handle(Q.device), prob, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
-                           O.data_ptr(), l.data_ptr(), m.data_ptr(), dO.data_ptr(), dQ.data_ptr(),
-                           dK.data_ptr(), dV.data_ptr(), ws.data_ptr(), ws_bytes)
+        st = L.fa_backward_split(_stream_handle(Q.device), prob, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                 O.data_ptr(), l.data_ptr(), m.data_ptr(), dO.data_ptr(), dQ.data_ptr(),
+                                 dK.data_ptr(), dV.data_ptr(), ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Backward")
     return dQ, dK, dV

@@ -16,7 +16,7 @@
 // Internal("Failed to launch the Forward kernel: <str>(<code>)") (forward.cc:383-385).
 // Differences: no output memsets and no Br_occupancy temp (the kernels
 // write every O/l/m element); the backward scratch is an allocate_temp of
-// fa_backward_workspace_bytes(), the split-key forward's one of
+// fa_backward_split_workspace_bytes(), the split-key forward's one of
 // fa_forward_workspace_bytes(); Estimate*Flops returns rule-exact algorithmic
 // FLOPs instead of the reference's tile-issued count.
 //
@@ -281,11 +281,12 @@ class FaBackwardOp : public OpKernel {
     OP_REQUIRES_OK(ctx, ctx->allocate_output(0, Q.shape(), &dQ));
     OP_REQUIRES_OK(ctx, ctx->allocate_output(1, K.shape(), &dK));
     OP_REQUIRES_OK(ctx, ctx->allocate_output(2, V.shape(), &dV));
-    const size_t ws_bytes = fa_backward_workspace_bytes(&p);
+    // outside the split-key envelope these are fa_backward_workspace_bytes and fa_backward
+    const size_t ws_bytes = fa_backward_split_workspace_bytes(&p);
     Tensor ws;
     OP_REQUIRES_OK(ctx, ctx->allocate_temp(DT_UINT8, TensorShape({static_cast<int64_t>(ws_bytes > 0 ? ws_bytes : 1)}), &ws));
-    const int rc = fa_backward(StreamOf(ctx), &p, Q.data(), K.data(), V.data(), O.data(), l.data(), m.data(),
-                               dO.data(), dQ->data(), dK->data(), dV->data(), ws.data(), ws_bytes);
+    const int rc = fa_backward_split(StreamOf(ctx), &p, Q.data(), K.data(), V.data(), O.data(), l.data(), m.data(),
+                                     dO.data(), dQ->data(), dK->data(), dV->data(), ws.data(), ws_bytes);
     OP_REQUIRES(ctx, rc == FA_OK,
                 errors::Internal("Failed to launch the Backward kernel: ", fa_error_string(rc), "(", rc, ")"));
   }

@@ -124,7 +124,8 @@ int check() {
       {FA_F16, FA_FULL, 2, FA_SCALE_FRONT, {12, 10}, {24, 20}, 64, 1, 0, 0},
       {FA_F16, FA_CAUSAL, 2, FA_NONE_FRONT, {16, 9}, {16, 9}, 96, 1, 0, 0},
       {FA_F16, FA_LOCAL, 2, FA_SCALE_FRONT, {10, 12}, {20, 24}, 64, 3, 1, 0},
-      // few queries, long key range: fa_forward_ws takes the split-key path (6 chunks, the last partial)
+      // few queries, long key range: fa_forward_ws and fa_backward_split take their split-key paths
+      // (6 chunks, the last partial)
       {FA_F16, FA_CAUSAL, 1, FA_SCALE_END, {40, 1}, {2600, 1}, 64, 1, 0, 0},
       {FA_F32, FA_FULL, 1, FA_SCALE_FRONT, {130, 1}, {260, 1}, 64, 1, 0, 0},
       {FA_F32, FA_CAUSAL, 1, FA_SCALE_END, {150, 1}, {75, 1}, 128, 1, 0, 0},
@@ -165,11 +166,13 @@ int check() {
     HIP_OK(hipMemcpy(k.p, hk.data(), hk.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(v.p, hv.data(), hv.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(g.p, hg.data(), hg.size(), hipMemcpyHostToDevice));
-    const size_t wsb = fa_backward_workspace_bytes(&p), fwsb = fa_forward_workspace_bytes(&p);
+    const size_t wsb = fa_backward_split_workspace_bytes(&p), fwsb = fa_forward_workspace_bytes(&p);
     Dev ws(wsb), fws(fwsb);
-    // outside the split envelope (fwsb == 0) this is fa_forward
+    int32_t bplan[4] = {0, 0, 0, 0};
+    fa_backward_split_plan(&p, bplan);
+    // outside the split envelopes (fwsb == 0, bplan[0] == 0) these are fa_forward and fa_backward
     int rc = fa_forward_ws(nullptr, &p, q.p, k.p, v.p, o.p, l.p, m.p, fws.p, fwsb);
-    if (rc == FA_OK) rc = fa_backward(nullptr, &p, q.p, k.p, v.p, o.p, l.p, m.p, g.p, dq.p, dk.p, dv.p, ws.p, wsb);
+    if (rc == FA_OK) rc = fa_backward_split(nullptr, &p, q.p, k.p, v.p, o.p, l.p, m.p, g.p, dq.p, dk.p, dv.p, ws.p, wsb);
     if (rc != FA_OK) { fprintf(stderr, "launch failed: %s\n", fa_last_error()); return 2; }
     HIP_OK(hipDeviceSynchronize());
     std::vector<double> rO, rdQ, rdK, rdV;
@@ -184,9 +187,10 @@ int check() {
                          max_rel_err(gdv, c.dt, rdV)};
     const bool ok = e[0] <= tol && e[1] <= tol && e[2] <= tol && e[3] <= tol;
     failures += !ok;
-    printf("{\"check\": \"dtype=%d policy=%d seq_dims=%d sync=%d d=%d split=%d\", \"err_O\": %.3e, \"err_dQ\": %.3e, "
-           "\"err_dK\": %.3e, \"err_dV\": %.3e, \"tol\": %.0e, \"ok\": %s}\n",
-           c.dt, c.pol, c.sd, c.mode, c.d, (int)(fwsb > 0), e[0], e[1], e[2], e[3], tol, ok ? "true" : "false");
+    printf("{\"check\": \"dtype=%d policy=%d seq_dims=%d sync=%d d=%d split=%d bwd_split=%d\", \"err_O\": %.3e, "
+           "\"err_dQ\": %.3e, \"err_dK\": %.3e, \"err_dV\": %.3e, \"tol\": %.0e, \"ok\": %s}\n",
+           c.dt, c.pol, c.sd, c.mode, c.d, (int)(fwsb > 0), (int)(bplan[0] > 0), e[0], e[1], e[2], e[3], tol,
+           ok ? "true" : "false");
   }
   return failures ? 1 : 0;
 }

@@ -1,6 +1,6 @@
 """A/B timing of two builds of the product library in ONE process (interleaved rounds), through
-_lib.using(): the forward and the backward of a bench config, with a bitwise check of every output
-against the first library.  Usage: python tools/lib_ab.py [config] libA.so libB.so ..."""
+_lib.using(): the forward and the backward (fa_backward itself) of a bench config, with a bitwise check
+of every output against the first library.  Usage: python tools/lib_ab.py [config] libA.so libB.so ..."""
 import json
 import os
 import sys
@@ -25,13 +25,30 @@ def main():
     mk = lambda shp: (torch.rand(shp, generator=g, device=dev) * 4 - 2).to(dt)  # noqa: E731
     q, k, v, do = mk((b, d) + qs), mk((b, d) + ks), mk((b, d) + ks), mk((b, d) + qs)
     fwd = lambda: fa.attention_forward(policy, seq_dims, q, k, v, sync, ws, ls, causal)  # noqa: E731
+    # the backward through fa_backward itself (the wrappers call fa_backward_split, which a library built
+    # before the split-key backward does not have): the entry point whose bits and time are compared
+    prob = _lib.make_problem(fa._DTYPES[dt], fa._POLICIES[policy], seq_dims, fa._sync_mode_id(sync), b, qs, ks, d, d,
+                             ws, ls, causal)
+    grads = [torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)]
+
+    def backward(o, l, m):
+        L = _lib.lib()
+        nbytes = int(L.fa_backward_workspace_bytes(prob))
+        wsp = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        st = L.fa_backward(torch.cuda.current_stream().cuda_stream, prob, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                           o.data_ptr(), l.data_ptr(), m.data_ptr(), do.data_ptr(), grads[0].data_ptr(),
+                           grads[1].data_ptr(), grads[2].data_ptr(), wsp.data_ptr(), nbytes)
+        if st != 0:
+            raise RuntimeError(_lib.last_error())
+        return grads
+
     ref = None
     res = {x: {"fwd": [], "bwd": []} for x in libs}
     for rnd in range(5):
         for x in libs:
             with _lib.using(x):
                 o, l, m = fwd()
-                bwd = lambda: fa.attention_backward(policy, seq_dims, q, k, v, o, l, m, do, sync, ws, ls, causal)  # noqa: E731
+                bwd = lambda: backward(o, l, m)  # noqa: E731
                 outs = [o, l, m] + list(bwd())
                 torch.cuda.synchronize()
                 if rnd == 0:
