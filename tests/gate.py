@@ -160,6 +160,19 @@ def grad_stats(got, ref, e, dtype) -> dict:
                 slope=scale_slope(got, ref), ref_rms=float(np.sqrt(np.mean(ref * ref))) if err.size else 0.0)
 
 
+def m_tol_bounded(m_ref, dtype, bound):
+    """run_case's tolerance on m with its dot-product rounding term replaced by a caller's bound (same
+    shape as m_ref, or a scalar): 2 ulp of T, plus for fp16 the larger of the rtol floor
+    1e-3·max(|m|, 1) and the bound, for fp32 / fp64 1e-6·|m| plus the larger of 1e-6 (1e-12) and the
+    bound.  For inputs whose |q|·|k| products are huge but cancel exactly in the row max
+    (tests/score_ramp.py), where the default term would leave m unchecked."""
+    m_ref = np.asarray(m_ref, dtype=np.float64)
+    ulp = np.abs(np.spacing(np.abs(m_ref).astype(dtype))).astype(np.float64)
+    if dtype == np.float16:
+        return 2 * ulp + np.maximum(1e-3 * np.maximum(np.abs(m_ref), 1.0), bound)
+    return 2 * ulp + 1e-6 * np.abs(m_ref) + np.maximum(1e-6 if dtype != np.float64 else 1e-12, bound)
+
+
 def max_abs_dot(Q, K, mask, chunk=512):
     """Per slice and query row, max over the row's allowed keys of sum_c |q_c| |k_c| (Q [b, d, nq], K [b, d, nk],
     mask [nq, nk]; 0 for a row with no allowed key): the scale of the rounding a score, and so the row max,

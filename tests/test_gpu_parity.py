@@ -82,7 +82,9 @@ def _to_dev(x, dev, bwd, misalign):
 
 
 def run_case(dtype, policy, seq_dims, mode, batch, d, vd, qs, ks, ws=1, ls=0, causal=False, seed=0, bwd=True,
-             slices=None, inputs=None, misalign=False):
+             slices=None, inputs=None, misalign=False, m_bound=None):
+    """m_bound (optional, [batch, nq] or a scalar): the caller's bound on the rounding of the row max, used in
+    place of the dot-product term of m's tolerance (gate.m_tol_bounded); every other check is unchanged."""
     rng = np.random.default_rng(seed)
     qs, ks = tuple(qs), tuple(ks)
     if inputs is None:
@@ -141,6 +143,9 @@ def run_case(dtype, policy, seq_dims, mode, batch, d, vd, qs, ks, ws=1, ls=0, ca
                            if dtype == np.float16
                            else 1e-6 * np.abs(M64[:, ha]) + np.maximum(1e-6 if dtype != np.float64 else 1e-12,
                                                                       2 * eps * dot_bound))
+        if m_bound is not None:
+            mb = np.broadcast_to(np.asarray(m_bound, dtype=np.float64), (b, nq))[sl][:, ha]
+            m_tol = gate.m_tol_bounded(M64[:, ha], dtype, mb)
         assert (np.abs(m_f - M64[:, ha]) <= m_tol).all(), f"m: max err {np.abs(m_f - M64[:, ha]).max():.3e}"
         l_ref = L64[:, ha] * np.exp(M64[:, ha] - m_f)    # relative to the stored m
         _close("l", lg[:, ha], l_ref, max(rtol, 1e-6 if dtype == np.float16 else rtol), atol)
@@ -651,7 +656,8 @@ def test_f16_forward_structures(monkeypatch, diag_lib, variant, policy, seq_dims
 
 # the one-wave-per-SIMD gap-stream forward (fa_fwd_f16_gap.hip, full policy): tails of every kind (nq
 # not a multiple of its 256-query block or of the 64-query wave, nk not a multiple of 64 or shorter
-# than one tile), d / v_d below 64, 2d shapes; seeds vary the scores' scale so rebases happen
+# than one tile), d / v_d below 64, 2d shapes.  The inputs are U(-2, 2) whatever the seed, so no row rebases
+# here after its seed tile; tests/test_gpu_score_range.py runs this kernel's rebase branch
 GAP_CASES = [
     ((264,), (136,), 64, 64), ((300,), (1000,), 48, 64), ((256,), (64,), 64, 64), ((1000,), (4096,), 64, 64),
     ((17,), (72,), 64, 33), ((513,), (520,), 40, 64), ((64,), (8,), 64, 64), ((4096,), (256,), 64, 64),
