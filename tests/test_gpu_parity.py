@@ -486,7 +486,7 @@ def test_wide_channels_mfma_f64(d, vd, policy, seq, mode, qs, ks, ws, ls, causal
     run_case(np.float64, policy, seq, mode, (2,), d, vd, qs, ks, ws=ws, ls=ls, causal=causal, seed=d + 13 * vd)
 
 
-# fp16 backward for 128 < max(d, v_d) <= 256 on MFMA (fa_bwd_f16_fast.hip launch_bwd_wide: the one-wave
+# fp16 backward for 128 < max(d, v_d) <= 256 on MFMA (fa_bwd_f16_wide.hip launch_bwd_f16_wide: the one-wave
 # dK / dV and dQ passes at D = 256, two 128-channel output chunks per slice; aligned tensors, lengths
 # multiples of 8, every rule incl. 2-D windows)
 @pytest.mark.parametrize("d,vd", [(256, 256), (160, 160), (136, 256), (256, 64), (72, 200)])

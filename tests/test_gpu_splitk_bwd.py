@@ -1,4 +1,4 @@
-"""GPU tests of the split-key dQ pass of the fp16 backward (csrc/fa_bwd_f16_fast.hip: the SPLIT form of
+"""GPU tests of the split-key dQ pass of the fp16 backward (csrc/fa_bwd_f16_dq.hip: the SPLIT form of
 bwd_dq_kernel and dq_split_reduce_kernel): few queries against a long key range,
 one workgroup per (slice, key chunk) writing fp32 partials, summed in chunk order.
 

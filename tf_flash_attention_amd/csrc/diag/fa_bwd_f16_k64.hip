@@ -13,21 +13,19 @@
 // step against 32 transposed reads of Q / dO, 32 of V and 16 row reads.
 // Shapes: max(d, v_d) in (64, 128], 16-B aligned tensors, nq % 8 == nk % 8 == 0, full and interval rules.
 // Replaces the key-outer half of the reference's BackwardImpl (flash_attention.cu:1079-1967).
-#include "../fa_device.h"
-#include "../fa_kernels.h"
-#include "../fa_mfma.h"
+#include "../fa_bwd_f16_parts.h"
 
 namespace fa {
 namespace {
 
-using namespace mf;
+using namespace bwdp;
 
 constexpr int kD = 128;
 constexpr int kNW = 4;
 constexpr int kThr = kNW * 64;
 constexpr int kBK = 64 * kNW;               // keys per workgroup
 constexpr int kRow = kD * kBK * 2;          // a K or V row image [128][256] fp16, 64 KB
-constexpr int kQT = kD * 64;                // one [128][32] tile image
+constexpr int kQT = kD * 64;                // one [128][32] Q16 image (fa_bwd_f16_parts.h)
 constexpr int kOffQT = 0, kOffOT = kQT, kOffLse = 2 * kQT;
 constexpr int kSlot = kOffLse + 2 * 32 * 4;  // + lse2[32], D[32]
 constexpr int kOffV = kRow;                  // V image (stays); the ring aliases the prologue's K image
@@ -35,11 +33,6 @@ constexpr int kSmem = 2 * kRow;
 constexpr int kQChunks = kD * 4;             // 16-B chunks of one [128][32] tile
 constexpr int kCPT = 2 * kQChunks / kThr;    // Q and dO chunks a thread (4)
 static_assert(2 * kSlot <= kRow, "the ring fits in the K image");
-
-// "Q16 image" [D][32] fp16 (fa_bwd_f16_fast.hip): 16-B units XOR-swizzled by (row >> 2) & 3
-__device__ __forceinline__ uint32_t q16o(int row, int u, int half8 = 0) {
-  return row * 64 + 16 * (u ^ ((row >> 2) & 3)) + 8 * half8;
-}
 
 #define K64_MFMA_A "v_mfma_f32_32x32x16_f16 %0, %1, %2, %0"
 
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(kThr, 1) void bwd_dkdv_k64_kernel(BwdArgs a) {
 #pragma unroll
     for (int j = 0; j < kCPT; ++j) {
       const bool isO = j >= kCPT / 2;
-      *reinterpret_cast<lds_u32x4_t*>(base + (isO ? kOffOT : kOffQT) + q16o(crow_[j], cm_[j])) = qr[j];
+      *reinterpret_cast<lds_u32x4_t*>(base + (isO ? kOffOT : kOffQT) + q16_off(crow_[j], cm_[j])) = qr[j];
     }
     if (w == 0) reinterpret_cast<lds_f_t*>(base + kOffLse)[lane] = lr;
   };
@@ -258,7 +251,7 @@ __global__ __launch_bounds__(kThr, 1) void bwd_dkdv_k64_kernel(BwdArgs a) {
       half8 qa8, oa8, vb8[2];
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
-        const uint32_t off = q16o(16 * s + 8 * (g >> 1) + 4 * e + tq, 2 * (g & 1) + (sig >> 1), sig & 1);
+        const uint32_t off = q16_off(16 * s + 8 * (g >> 1) + 4 * e + tq, 2 * (g & 1) + (sig >> 1), sig & 1);
         const half4 x = tr_read(base + kOffQT + off), y = tr_read(base + kOffOT + off);
         if (e == 0) { qa8.lo = x; oa8.lo = y; } else { qa8.hi = x; oa8.hi = y; }
       }
@@ -301,8 +294,8 @@ __global__ __launch_bounds__(kThr, 1) void bwd_dkdv_k64_kernel(BwdArgs a) {
     for (int s = 0; s < 2; ++s)
 #pragma unroll
       for (int u = 0; u < kD / 32; ++u) {
-        const half8 oa = read_b128(base + kOffOT + q16o(32 * u + r, 2 * s + h));
-        const half8 qa_ = read_b128(base + kOffQT + q16o(32 * u + r, 2 * s + h));
+        const half8 oa = read_b128(base + kOffOT + q16_off(32 * u + r, 2 * s + h));
+        const half8 qa_ = read_b128(base + kOffQT + q16_off(32 * u + r, 2 * s + h));
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
           if constexpr ((ABL & kANoDvdk) != 0) {
@@ -366,10 +359,7 @@ hipError_t launch_dkdv_k64(const BwdArgs& a, hipStream_t s) {
       default: break;
     }
   }
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), kSmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * nkb)), dim3(kThr), kSmem, s, a);
-  return hipGetLastError();
+  return launch_smem(kern, (unsigned)(a.b * nkb), kThr, kSmem, s, a);
 }
 
 }  // namespace fa

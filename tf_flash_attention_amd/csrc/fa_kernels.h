@@ -53,7 +53,7 @@ struct SplitArgs {
   int32_t k_end;    // one past the range's last key
 };
 
-// split-key dQ pass of the fp16 backward (fa_bwd_f16_fast.hip): the plan of fa_api.hip plus the partials
+// split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;
   float* ws_part;   // [b][nchunks][d][nq] floats: unscaled fp32 dQ partials
@@ -124,12 +124,13 @@ hipError_t launch_bwd_f64(const BwdArgs& a, hipStream_t s);
 // diag/fa_bwd_f16_k64.hip (diagnostic library only: FA_BWD_VARIANT 1700)
 bool bwd_dkdv_k64_supported(const BwdArgs& a);
 hipError_t launch_dkdv_k64(const BwdArgs& a, hipStream_t s);
-// two-pass fp16 backward (dK/dV key-outer + dQ query-outer, no atomics) — fa_bwd_f16_fast.hip
+// two-pass fp16 backward (dK/dV key-outer + dQ query-outer, no atomics) — fa_bwd_f16_fast.hip (prep, dK/dV,
+// dispatch), fa_bwd_f16_dq.hip (dQ), fa_bwd_f16_wide.hip (D = 256); shared pieces in fa_bwd_f16_parts.h
 bool bwd_f16_fast_supported(const BwdArgs& a);
 hipError_t launch_bwd_f16_fast(const BwdArgs& a, hipStream_t s);
 // the same backward for one query block (nq <= 128, max(d, v_d) <= 128) against a long key range: the
 // prep and the dK/dV pass as above, then the one-wave dQ pass on one workgroup per (slice, key chunk)
-// writing fp32 partials, and a reduce kernel that sums them in chunk order — fa_bwd_f16_fast.hip.
+// writing fp32 partials, and a reduce kernel that sums them in chunk order — fa_bwd_f16_dq.hip.
 // At most bwd_f16_split_max_batch() slices per call (grid limits).
 int64_t bwd_f16_split_max_batch(const BwdSplitArgs& sa);
 hipError_t launch_bwd_f16_split(const BwdSplitArgs& sa, hipStream_t s);

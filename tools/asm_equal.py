@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Compare the kernels of two AMDGPU assembly files (hipcc --cuda-device-only -S) by demangled name.
+
+    tools/asm_equal.py OLD.s NEW.s          (several translation units: concatenate their .s files)
+
+Per kernel: IDENTICAL when the instruction stream (comments, labels and symbol names dropped) and the
+resource lines (.amdhsa_* descriptor, occupancy, register / scratch / LDS counts) are equal; otherwise
+the number of differing instruction lines and the resource lines that moved.  Exit status 1 if any
+kernel differs or exists on one side only.
+"""
+import difflib
+import re
+import shutil
+import subprocess
+import sys
+
+CXXFILT = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+RES_COMMENT = re.compile(r";\s*(Occupancy|NumVgprs|NumAgprs|TotalNumVgprs|TotalNumSgprs|ScratchSize|LDSByteSize)\b.*")
+
+
+def parse(path):
+    """{mangled kernel name: (instruction lines, resource lines)}"""
+    kernels, body, res = {}, {}, {}
+    cur = None       # function being read
+    last = None      # function just ended (its resource comments follow)
+    desc = None      # kernel descriptor being read
+    with open(path, errors="replace") as f:
+        for raw in f:
+            line = raw.strip()
+            m = re.match(r"\.type\s+(\S+),@function", line)
+            if m:
+                cur, last = m.group(1), None
+                body[cur], res[cur] = [], []
+                continue
+            m = re.match(r"\.amdhsa_kernel\s+(\S+)", line)
+            if m:  # (the descriptor sits inside the function's text, before its end label)
+                desc = m.group(1)
+                continue
+            if desc is not None:
+                if line.startswith(".end_amdhsa_kernel"):
+                    kernels[desc] = None
+                    desc = None
+                elif line.startswith(".amdhsa_"):
+                    res.setdefault(desc, []).append(line.split(";", 1)[0].strip())
+                continue
+            if cur is not None:
+                if re.match(r"\.Lfunc_end\d+:", line):
+                    cur, last = None, cur
+                    continue
+                code = line.split(";", 1)[0].strip()
+                if not code or code.startswith(".") or re.match(r"^[\w.$]+:$", code):  # directives, labels
+                    continue
+                code = re.sub(r"\.LBB\d+_", ".LBB_", code)
+                code = re.sub(r"\b_Z\w+", "SYM", code)
+                body[cur].append(code)
+                continue
+            if last is not None and RES_COMMENT.match(line):
+                res[last].append(line)
+    return {k: (body.get(k, []), res.get(k, [])) for k in kernels}
+
+
+def demangle(names):
+    out = subprocess.run([CXXFILT], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    return dict(zip(names, out))
+
+
+def main():
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    old, new = parse(sys.argv[1]), parse(sys.argv[2])
+    dm = demangle(sorted(set(old) | set(new)))
+    old = {dm[k]: v for k, v in old.items()}
+    new = {dm[k]: v for k, v in new.items()}
+    bad = 0
+    for name in sorted(set(old) | set(new)):
+        if name not in old or name not in new:
+            print(f"{'ONLY IN NEW' if name in new else 'ONLY IN OLD'}  {name}")
+            bad += 1
+            continue
+        (bo, ro), (bn, rn) = old[name], new[name]
+        if bo == bn and ro == rn:
+            print(f"IDENTICAL  {name}  ({len(bo)} instructions)")
+            continue
+        bad += 1
+        moved = sum(1 for d in difflib.unified_diff(bo, bn, lineterm="", n=0) if d[:1] in "+-" and d[:3] not in ("+++", "---"))
+        print(f"DIFFERS    {name}  ({len(bo)} -> {len(bn)} instructions, {moved} diff lines)")
+        if len(ro) != len(rn):  # (a line on one side only: show both lists whole)
+            print(f"           resources old: {ro}\n           resources new: {rn}")
+        for a, b in zip(ro, rn):
+            if a != b:
+                print(f"           {a}  ->  {b}")
+    print(f"{len(old)} kernels in {sys.argv[1]}, {len(new)} in {sys.argv[2]}: {bad} not identical")
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()

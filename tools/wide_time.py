@@ -1,5 +1,5 @@
 """Forward and backward time at 256 channels, plus the fp32 forward there (config 2's shape at d = 256): the MFMA kernels
-(fa_fwd_f16_wide.hip; fa_bwd_f16_fast.hip launch_bwd_wide) against the SIMT kernels the same calls took
+(fa_fwd_f16_wide.hip; fa_bwd_f16_wide.hip launch_bwd_f16_wide) against the SIMT kernels the same calls took
 before round 4 (reached here through a K pointer one element off 16-B alignment, which the MFMA kernels
 do not take).  Usage: python tools/wide_time.py [b] [n]"""
 import json
