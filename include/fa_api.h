@@ -136,8 +136,28 @@ int fa_backward(void* stream, const fa_problem* p,
  *   fa_backward_workspace_bytes(p) with 0 chunks, otherwise that plus b * chunks * d * nq floats
  *   (rounded up to 256 bytes; the partials follow fa_backward's regions).
  * fa_backward_split: with 0 chunks exactly fa_backward; otherwise the split path, or
- *   FA_ERR_WORKSPACE_TOO_SMALL (nothing is written). */
+ *   FA_ERR_WORKSPACE_TOO_SMALL (nothing is written).
+ *
+ * Split-query backward, the mirrored shape: fp16 problems with one key block (1 <= nk <= 128),
+ * max(d, v_d) <= 128, max(d, v_d) * (nq + 8) * 2 < 2^31 (a slice's Q / dO channel rows stay inside the
+ * dK/dV kernels' 32-bit buffer offsets) and a rule-bounded query range [qb, qe) of that key block of at
+ * least 2048 queries cut the key-outer dK/dV pass (one workgroup per slice for such shapes) into query
+ * chunks, one workgroup per (slice, chunk) writing unscaled fp32 dK / dV partials, and sum the partials of
+ * a key in chunk order (no atomics: deterministic).  The prep and the dQ pass are fa_backward's, so dQ is
+ * bitwise fa_backward's; dK and dV differ by fp32 summation order only.  Chunks hold
+ * max(min_chunk, ceil(ceil(span / 64) / 128) * 128) queries, span = qe - floor(qb / 32) * 32, min_chunk =
+ * 512 for nk <= 64 and 1024 above: at most 64 chunks.  The two plans are never both active (the key-chunk
+ * plan needs nq <= 128 and a key range of at least 2048 keys).
+ *
+ * fa_backward_split_q_plan (host-only): out[0] = number of query chunks (0 outside the envelope),
+ *   out[1] = queries per chunk, out[2..3] = query range [qb, qe) of the key block.  Validation and errors
+ *   as fa_backward_split_plan.
+ * fa_backward_split_workspace_bytes: with query chunks, fa_backward_workspace_bytes(p) plus
+ *   b * chunks * (d + v_d) * nk floats (rounded up to 256 bytes; the partials follow fa_backward's regions).
+ * fa_backward_split: with query chunks the split-query path, or FA_ERR_WORKSPACE_TOO_SMALL (nothing is
+ *   written); with 0 chunks in both plans exactly fa_backward. */
 int fa_backward_split_plan(const fa_problem* p, int32_t out[4]);
+int fa_backward_split_q_plan(const fa_problem* p, int32_t out[4]);
 size_t fa_backward_split_workspace_bytes(const fa_problem* p);
 int fa_backward_split(void* stream, const fa_problem* p,
                       const void* Q, const void* K, const void* V,

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_backward_split_plan",
+    "fa_backward_split_q_plan",
     "fa_backward_split_workspace_bytes",
     "fa_backward_split",
     "fa_estimate_forward_flops",
@@ -109,6 +110,10 @@ def _declare(lib):
         lib.fa_backward_split_workspace_bytes.restype = ctypes.c_size_t
         lib.fa_backward_split.argtypes = [vp, P, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
         lib.fa_backward_split.restype = ctypes.c_int
+    # (absent from a library built before the split-query dK/dV pass, as above)
+    if hasattr(lib, "fa_backward_split_q_plan"):
+        lib.fa_backward_split_q_plan.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
+        lib.fa_backward_split_q_plan.restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

@@ -240,6 +240,52 @@ size_t bwd_split_part_bytes(const fa_problem* p, const SplitPlan& s) {
   return align_up((size_t)p->b * (size_t)s.nchunks * (size_t)p->d * nq * sizeof(float));
 }
 
+// Split-query routing of the fp16 backward's dK/dV pass, the mirror of the plan above:
+// one key block of both dK/dV kernels (nk <= 128) against a rule-bounded query range of at least 2048
+// queries, where the kernels' 32-bit buffer offsets reach a slice's Q / dO channel rows (the b-free part
+// of bwd_f16_fast_supported).  A pure function of the problem WITHOUT b.  Never active together with
+// bwd_split_plan: that one needs nq <= 128 and a key range >= 2048, this one nk <= 128.
+constexpr int32_t kQSplitMaxK = 128;       // one key block of the dK/dV kernels
+constexpr int32_t kQSplitTile = 32;        // their query tile
+constexpr int32_t kQSplitGroup = 128;      // four tiles: the producer / consumer kernel's step group
+
+struct QSplitPlan {
+  int32_t nchunks, chunk, qb, qe, q_first;
+};
+
+QSplitPlan bwd_qsplit_plan(const fa_problem* p) {
+  QSplitPlan s = {0, 0, 0, 0, 0};
+  if (fa_validate(p) != FA_OK || p->dtype != FA_F16 || p->d > 128 || p->v_d > 128) return s;
+#ifdef FA_DIAG
+  // a pinned backward variant keeps measuring the kernel it names
+  if (fa::diag_variant("FA_BWD_VARIANT") >= 0) return s;
+#endif
+  const int64_t nq = seq_elems(p->q_seq, p->seq_dims), nk = seq_elems(p->k_seq, p->seq_dims);
+  if (nk < 1 || nk > kQSplitMaxK || nq < 1) return s;
+  const int64_t dm = p->d > p->v_d ? p->d : p->v_d;
+  if (dm * (nq + 8) * 2 >= (int64_t(1) << 31)) return s;
+  fa::Rule r;
+  build_rule(p, &r);
+  fa::q_range_for_k_block(r, 0, (int32_t)nk - 1, &s.qb, &s.qe);
+  if (s.qe - s.qb < kSplitMinRange) return s;
+  s.q_first = s.qb / kQSplitTile * kQSplitTile;
+  const int32_t span = s.qe - s.q_first;
+  // a partial is nk*(d+v_d) floats per chunk beside chunk*(d+v_d) halfs of Q/dO: above 64 keys the chunks
+  // are twice as long, so the partials stay within a quarter of the Q/dO bytes
+  const int32_t min_chunk = nk <= 64 ? 512 : 1024;
+  const int32_t capped = ((span + kSplitMaxChunks - 1) / kSplitMaxChunks + kQSplitGroup - 1) / kQSplitGroup * kQSplitGroup;
+  s.chunk = capped > min_chunk ? capped : min_chunk;
+  s.nchunks = (span + s.chunk - 1) / s.chunk;
+  return s;
+}
+
+// the dK/dV partials of the split-query backward: b * nchunks records of (d + v_d) * nk floats, after
+// ws_layout's regions
+size_t bwd_qsplit_part_bytes(const fa_problem* p, const QSplitPlan& s) {
+  const size_t nk = (size_t)seq_elems(p->k_seq, p->seq_dims);
+  return align_up((size_t)p->b * (size_t)s.nchunks * (size_t)(p->d + p->v_d) * nk * sizeof(float));
+}
+
 }  // namespace
 
 extern "C" {
@@ -434,17 +480,82 @@ int fa_backward_split_plan(const fa_problem* p, int32_t out[4]) {
   return FA_OK;
 }
 
+int fa_backward_split_q_plan(const fa_problem* p, int32_t out[4]) {
+  int st = fa_validate(p);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const QSplitPlan s = bwd_qsplit_plan(p);
+  out[0] = s.nchunks;
+  out[1] = s.chunk;
+  out[2] = s.qb;
+  out[3] = s.qe;
+  return FA_OK;
+}
+
 size_t fa_backward_split_workspace_bytes(const fa_problem* p) {
   if (fa_validate(p) != FA_OK) return 0;
   const SplitPlan s = bwd_split_plan(p);
-  return ws_layout(p).total + (s.nchunks ? bwd_split_part_bytes(p, s) : 0);
+  const QSplitPlan qs = bwd_qsplit_plan(p);  // (never both: see bwd_qsplit_plan)
+  return ws_layout(p).total + (s.nchunks ? bwd_split_part_bytes(p, s) : 0) + (qs.nchunks ? bwd_qsplit_part_bytes(p, qs) : 0);
 }
+
+namespace {
+
+// fa_backward_split for a problem with query chunks: the dK/dV pass split over them
+int backward_split_q(void* stream, const fa_problem* p, const QSplitPlan& qp, const void* Q, const void* K, const void* V,
+                     const void* O, const void* l, const void* m, const void* dO, void* dQ, void* dK, void* dV,
+                     void* workspace, size_t workspace_bytes) {
+  const WsLayout w = ws_layout(p);
+  if (!workspace || workspace_bytes < w.total + bwd_qsplit_part_bytes(p, qp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
+                     "backward workspace is smaller than fa_backward_split_workspace_bytes()");
+  FA_DIAG_COUNT(1);
+  if (p->b == 0) return FA_OK;
+  fa::BwdQSplitArgs sa;
+  fa::BwdArgs& a = sa.b;
+  a.d = p->d; a.v_d = p->v_d;
+  a.scale = 1.0 / sqrt((double)p->d);
+  build_rule(p, &a.rule);
+  sa.nchunks = qp.nchunks; sa.chunk = qp.chunk; sa.q_first = qp.q_first; sa.q_end = qp.qe;
+  const int64_t nq = a.rule.q.n, nk = a.rule.k.n;
+  char* ws = static_cast<char*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // one call covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
+  const int64_t bmax = fa::bwd_f16_qsplit_max_batch(sa);
+  for (int64_t b0 = 0; b0 < p->b; b0 += bmax) {
+    a.b = p->b - b0 < bmax ? p->b - b0 : bmax;
+    a.Q = static_cast<const uint16_t*>(Q) + b0 * p->d * nq;
+    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
+    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
+    a.O = static_cast<const uint16_t*>(O) + b0 * p->v_d * nq;
+    a.l = static_cast<const float*>(l) + b0 * nq;
+    a.m = static_cast<const uint16_t*>(m) + b0 * nq;
+    a.dO = static_cast<const uint16_t*>(dO) + b0 * p->v_d * nq;
+    a.dQ = static_cast<uint16_t*>(dQ) + b0 * p->d * nq;
+    a.dK = static_cast<uint16_t*>(dK) + b0 * p->d * nk;
+    a.dV = static_cast<uint16_t*>(dV) + b0 * p->v_d * nk;
+    a.ws_dQ = ws + w.dq;  // (the two-pass kernels keep no dQ accumulator)
+    a.ws_D = reinterpret_cast<float*>(ws + w.D) + b0 * nq;
+    a.ws_lse = reinterpret_cast<float*>(ws + w.lse) + b0 * nq;
+    sa.ws_part = reinterpret_cast<float*>(ws + w.total) + b0 * qp.nchunks * (p->d + p->v_d) * nk;
+    const hipError_t e = fa::launch_bwd_f16_qsplit(sa, s);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
+}  // namespace
 
 int fa_backward_split(void* stream, const fa_problem* p, const void* Q, const void* K, const void* V, const void* O,
                       const void* l, const void* m, const void* dO, void* dQ, void* dK, void* dV, void* workspace,
                       size_t workspace_bytes) {
   const SplitPlan sp = bwd_split_plan(p);
-  if (sp.nchunks == 0) return fa_backward(stream, p, Q, K, V, O, l, m, dO, dQ, dK, dV, workspace, workspace_bytes);
+  if (sp.nchunks == 0) {
+    const QSplitPlan qp = bwd_qsplit_plan(p);
+    if (qp.nchunks) return backward_split_q(stream, p, qp, Q, K, V, O, l, m, dO, dQ, dK, dV, workspace, workspace_bytes);
+    return fa_backward(stream, p, Q, K, V, O, l, m, dO, dQ, dK, dV, workspace, workspace_bytes);
+  }
   const WsLayout w = ws_layout(p);
   if (!workspace || workspace_bytes < w.total + bwd_split_part_bytes(p, sp))
     return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
@@ -560,7 +671,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}";
 }
 
 }  // extern "C"

@@ -27,6 +27,9 @@
 // With one query block against a long key range the dq pass would run one workgroup per slice;
 // launch_bwd_f16_split runs it on one workgroup per (slice, key chunk) instead (bwd_dq_kernel's SPLIT
 // form: fp32 partials) and sums the partials in chunk order (dq_split_reduce_kernel): still no atomics.
+// The mirrored shape, one key block (nk <= 128) against a long query range, would run the dkdv pass on one
+// workgroup per slice; launch_bwd_f16_qsplit runs it on one workgroup per (slice, query chunk) (the SPLIT
+// forms of both dK/dV kernels) and sums their partials the same way (dkdv_split_reduce_kernel).
 // Masks are rules (fa_rules.h): per-lane index intervals (POL 1: full windows of an
 // interval rule) or the per-element order check (POL 2: strided / 2d local windows), and
 // per-wave tile classes; tiles with no allowed pair are skipped.
@@ -118,6 +121,27 @@ __global__ __launch_bounds__(kThrPrep) void bwd_prep8_kernel(BwdArgs a) {
   ws[1] = s[1];
 }
 
+// SPLIT forms of the two dK/dV kernels (many queries against one key block, BwdQSplitArgs)
+template <bool SPLIT> struct DkdvArgsOf { using type = BwdArgs; };
+template <> struct DkdvArgsOf<true> { using type = BwdQSplitArgs; };
+__device__ __forceinline__ const BwdArgs& dkdv_bwd_args(const BwdArgs& x) { return x; }
+__device__ __forceinline__ const BwdArgs& dkdv_bwd_args(const BwdQSplitArgs& x) { return x.b; }
+
+// the unscaled fp32 partial of (slice, chunk) of the split forms, rec = its record [d + v_d][nk] (dK rows,
+// then dV rows): lanes along nk, so the stores coalesce; dkdv_split_reduce_kernel scales and rounds
+template <int kU>
+__device__ __forceinline__ void store_partial(float* rec, const floatx16 (&dk)[kU], const floatx16 (&dv)[kU], int d, int vd,
+                                              int nk, int key, int h) {
+#pragma unroll
+  for (int u = 0; u < kU; ++u)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int c = 32 * u + (i & 3) + 8 * (i >> 2) + 4 * h;
+      if (c < d) rec[(int64_t)c * nk + key] = dk[u][i];
+      if (c < vd) rec[(int64_t)(d + c) * nk + key] = dv[u][i];
+    }
+}
+
 template <int D, int NW, int NS = 2>
 struct DkdvSmem {
   static constexpr int kBK = 32 * NW;                 // keys per workgroup
@@ -136,8 +160,14 @@ struct DkdvSmem {
 // channels (chunk = block index mod OC), forming S and dP over all D channels as before: the 256-channel
 // accumulators of both gradients would not fit one wave beside the resident K' and V (round 4's D = 256
 // pass; the four-role pass below replaces it, FA_BWD_VARIANT=1421 keeps it for A/B).
-template <int D, int NW, int WPE, int POL, bool ALN, int OC = 1>
-__global__ __launch_bounds__(NW * 64, WPE) void bwd_dkdv_kernel(BwdArgs a) {
+// SPLIT (one key block, nk <= 128, against a long query range, BwdQSplitArgs): the grid is (slice, query
+// chunk); the workgroup stages the key block (k0 = 0), walks only the query tiles of its chunk of the block's
+// query range and stores its unscaled fp32 accumulators as the partial record of (slice, chunk);
+// dkdv_split_reduce_kernel sums them.
+template <int D, int NW, int WPE, int POL, bool ALN, int OC = 1, bool SPLIT = false>
+__global__ __launch_bounds__(NW * 64, WPE) void bwd_dkdv_kernel(typename DkdvArgsOf<SPLIT>::type args) {
+  static_assert(!SPLIT || (OC == 1 && NW == 4), "the split form is one 128-key block at D <= 128");
+  const BwdArgs& a = dkdv_bwd_args(args);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_char_t* smem = (lds_char_t*)smem_raw;
   using S = DkdvSmem<D, NW>;
@@ -153,8 +183,10 @@ __global__ __launch_bounds__(NW * 64, WPE) void bwd_dkdv_kernel(BwdArgs a) {
   const uint32_t bidc = xcd_remap(blockIdx.x, gridDim.x);
   const int oc = (int)(bidc % OC), ou0 = oc * (kDO / 32);  // the chunk: channel blocks ou0 .. ou0 + kDO/32 - 1
   const uint32_t bid = bidc / OC;
-  const int64_t bi = bid / nkb;
-  const int k0 = (int)(bid % nkb) * kBK;  // earliest (heaviest under causal) key blocks first
+  uint32_t per_slice = nkb;  // SPLIT: one key block (k0 = 0) and the chunks of its query range
+  if constexpr (SPLIT) per_slice = (uint32_t)args.nchunks;
+  const int64_t bi = bid / per_slice;
+  const int k0 = SPLIT ? 0 : (int)(bid % nkb) * kBK;  // earliest (heaviest under causal) key blocks first
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, r = lane & 31;
@@ -188,8 +220,15 @@ __global__ __launch_bounds__(NW * 64, WPE) void bwd_dkdv_kernel(BwdArgs a) {
   const int klast = min(k0 + kBK, nk) - 1;
   int qb = 0, qe = nq;
   if (POL != 0) q_range_for_k_block(a.rule, k0, klast, &qb, &qe);
-  const int qt0 = (qb / 32) * 32;
-  const int ntiles = (qe > qb) ? (qe - qt0 + 31) / 32 : 0;
+  int qt0 = (qb / 32) * 32;
+  int ntiles = (qe > qb) ? (qe - qt0 + 31) / 32 : 0;
+  int qlim = nq;  // queries at or past it are staged as zeros with -lse2 = -inf
+  if constexpr (SPLIT) {  // this chunk's share of that range (q_first and chunk are tile-aligned; wave-uniform)
+    qt0 = args.q_first + (int)(bid % per_slice) * args.chunk;
+    __builtin_assume(qt0 % 32 == 0);  // (the per-element query offsets then fold into the tile base)
+    qlim = min(qt0 + args.chunk, args.q_end);
+    ntiles = (qlim - qt0 + 31) / 32;
+  }
   const int key = k0 + 32 * w + r;
   const int wk0 = k0 + 32 * w;
   const bool wave_active = wk0 < nk;
@@ -210,12 +249,13 @@ __global__ __launch_bounds__(NW * 64, WPE) void bwd_dkdv_kernel(BwdArgs a) {
   // two staging sets (tile t in set t&1): a tile is loaded two steps before it is stored
   u32x4 qr[2][kCPT];
   float lr[2] = {0.f, 0.f};
+  // (SPLIT: the phantom tiles past the chunk's end move zeros too, not the next chunk's queries)
   auto load_tile = [&](int qa, int set) {
-    stager.load(qr[set], qrs, ors, d, vd, qa, nq);
+    stager.load(qr[set], qrs, ors, d, vd, qa, SPLIT ? qlim : nq);
     if (w == 0) {  // lanes 0..31: lse2, 32..63: D (wave-uniform branch; clamped load, select past nq)
       const int q = qa + (lane & 31);
       const float v = (lane < 32 ? glse : gD)[min(q, nq - 1)];
-      lr[set] = (q < nq) ? v : ((lane < 32) ? -__builtin_huge_valf() : 0.f);
+      lr[set] = (q < (SPLIT ? qlim : nq)) ? v : ((lane < 32) ? -__builtin_huge_valf() : 0.f);
     }
   };
   auto store_tile = [&](int slot, int set) {
@@ -343,6 +383,10 @@ __global__ __launch_bounds__(NW * 64, WPE) void bwd_dkdv_kernel(BwdArgs a) {
 
   // ---- dK = scale·Σ dS·Q, dV: rows c = 32u + (i&3) + 8(i>>2) + 4h, column = this lane's key
   if (!wave_active || key >= nk) return;
+  if constexpr (SPLIT) {  // bid = slice * nchunks + chunk
+    store_partial<kDO / 32>(args.ws_part + (int64_t)bid * (d + vd) * nk, dk, dv, d, vd, nk, key, h);
+    return;
+  }
   __half* dK = static_cast<__half*>(a.dK) + bi * (int64_t)d * nk;
   __half* dV = static_cast<__half*>(a.dV) + bi * (int64_t)vd * nk;
   const float sc = (float)a.scale;
@@ -374,8 +418,10 @@ struct PcSmem {
   static constexpr int kTotal = kUsed > 2 * kRow ? kUsed : 2 * kRow;  // the K/V images alias the ring
 };
 
-template <int D, int POL, bool ALN>
-__global__ __launch_bounds__(512, 1) void bwd_dkdv_pc_kernel(BwdArgs a) {
+// SPLIT: as in bwd_dkdv_kernel (the consumers store the partial record).
+template <int D, int POL, bool ALN, bool SPLIT = false>
+__global__ __launch_bounds__(512, 1) void bwd_dkdv_pc_kernel(typename DkdvArgsOf<SPLIT>::type args) {
+  const BwdArgs& a = dkdv_bwd_args(args);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_char_t* smem = (lds_char_t*)smem_raw;
   using S = PcSmem<D>;
@@ -387,8 +433,10 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_pc_kernel(BwdArgs a) {
   const int nq = a.rule.q.n, nk = a.rule.k.n;
   const uint32_t nkb = (nk + kBK - 1) / kBK;
   const uint32_t bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int64_t bi = bid / nkb;
-  const int k0 = (int)(bid % nkb) * kBK;  // earliest (heaviest under causal) key blocks first
+  uint32_t per_slice = nkb;  // SPLIT: one key block (k0 = 0) and the chunks of its query range
+  if constexpr (SPLIT) per_slice = (uint32_t)args.nchunks;
+  const int64_t bi = bid / per_slice;
+  const int k0 = SPLIT ? 0 : (int)(bid % nkb) * kBK;  // earliest (heaviest under causal) key blocks first
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = w >> 2, wl = w & 3;  // group 0 produces, group 1 consumes; wl: the key slice
@@ -413,8 +461,15 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_pc_kernel(BwdArgs a) {
   const int klast = min(k0 + kBK, nk) - 1;
   int qb = 0, qe = nq;
   if (POL != 0) q_range_for_k_block(a.rule, k0, klast, &qb, &qe);
-  const int qt0 = (qb / 32) * 32;
-  const int ntiles = (qe > qb) ? (qe - qt0 + 31) / 32 : 0;
+  int qt0 = (qb / 32) * 32;
+  int ntiles = (qe > qb) ? (qe - qt0 + 31) / 32 : 0;
+  int qlim = nq;  // queries at or past it are staged as zeros with -lse2 = -inf
+  if constexpr (SPLIT) {  // this chunk's share of that range (q_first and chunk are tile-aligned; wave-uniform)
+    qt0 = args.q_first + (int)(bid % per_slice) * args.chunk;
+    __builtin_assume(qt0 % 32 == 0);
+    qlim = min(qt0 + args.chunk, args.q_end);
+    ntiles = (qlim - qt0 + 31) / 32;
+  }
   const int key = k0 + 32 * wl + r;
   const int wk0 = k0 + 32 * wl;
   const bool wave_active = wk0 < nk;
@@ -434,12 +489,12 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_pc_kernel(BwdArgs a) {
   u32x4 qr[2][kCPT];  // two staging sets: tile t in set t&1, loaded two steps before it is stored
   float lr[2] = {0.f, 0.f};
   auto load_tile = [&](int qa, int set) __attribute__((always_inline)) {
-    stager.load(qr[set], qrs, ors, d, vd, qa, nq);
+    stager.load(qr[set], qrs, ors, d, vd, qa, SPLIT ? qlim : nq);
     if (w == 0) {  // lanes 0..31: -lse2, 32..63: -D (a wave-uniform scalar branch; the load itself is
                    // unconditional, clamped into the row, and the select replaces rows past nq)
       const int q = qa + (lane & 31);
       const float v = (lane < 32 ? glse : gD)[min(q, nq - 1)];
-      lr[set] = (q < nq) ? v : ((lane < 32) ? -__builtin_huge_valf() : 0.f);
+      lr[set] = (q < (SPLIT ? qlim : nq)) ? v : ((lane < 32) ? -__builtin_huge_valf() : 0.f);
     }
   };
   auto store_tile = [&](int slot, int set) __attribute__((always_inline)) {
@@ -613,10 +668,43 @@ __global__ __launch_bounds__(512, 1) void bwd_dkdv_pc_kernel(BwdArgs a) {
 
   // ---- dK = scale·Σ dS·Q, dV: rows c = 32u + (i&3) + 8(i>>2) + 4h, column = this lane's key
   if (!wave_active || key >= nk) return;
+  if constexpr (SPLIT) {  // bid = slice * nchunks + chunk
+    store_partial<D / 32>(args.ws_part + (int64_t)bid * (d + vd) * nk, dk, dv, d, vd, nk, key, h);
+    return;
+  }
   __half* dK = static_cast<__half*>(a.dK) + bi * (int64_t)d * nk;
   __half* dV = static_cast<__half*>(a.dV) + bi * (int64_t)vd * nk;
   const float sc = (float)a.scale;
   store_grad<D, D / 32>({{dk, dK, d, sc}, {dv, dV, vd, 1.f}}, nk, key, h, 0);
+}
+
+// dK and dV of the split forms: one thread per (slice, row of the record, key), keys fastest.  The chunk
+// partials are added in chunk order in fp32 (no atomics: the result is deterministic and a slice's bits do
+// not depend on the batch), then scaled (dK; dV by 1) and rounded as store_grad does.  The loads of a group
+// of eight chunks are issued together; only the additions are a chain.
+__global__ __launch_bounds__(256) void dkdv_split_reduce_kernel(BwdQSplitArgs sa) {
+  const BwdArgs& a = sa.b;
+  const int nc = sa.nchunks;
+  const int64_t nk = a.rule.k.n;
+  const int64_t per = (int64_t)(a.d + a.v_d) * nk, perk = (int64_t)a.d * nk;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= a.b * per) return;
+  const int64_t bi = gid / per, e = gid - bi * per;
+  const float* part = sa.ws_part + bi * nc * per + e;
+  float sum = 0.f;
+  int c = 0;
+  for (; c + 8 <= nc; c += 8) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = part[(c + j) * per];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum += v[j];
+  }
+  for (; c < nc; ++c) sum += part[c * per];
+  if (e < perk)
+    static_cast<__half*>(a.dK)[bi * perk + e] = __float2half(sum * (float)a.scale);
+  else
+    static_cast<__half*>(a.dV)[bi * (per - perk) + (e - perk)] = __float2half(sum * 1.f);
 }
 
 template <int D, int NW, int WPE>
@@ -633,6 +721,26 @@ hipError_t launch_dkdv_pc(const BwdArgs& a, hipStream_t s) {
   const int64_t nkb = (a.rule.k.n + S::kBK - 1) / S::kBK;
   return launch_smem(with_pol_aln(a, [](auto pol, auto aln) { return &bwd_dkdv_pc_kernel<D, pol.value, aln.value>; }),
                      (unsigned)(a.b * nkb), 512, S::kTotal, s, a);
+}
+
+// the same two passes on one workgroup per (slice, query chunk), at the unsplit instances' launch bounds (no
+// split instance spills there, profiles/bwd_dkdv_split_resources.txt), then the reduce over the chunks
+hipError_t launch_dkdv_qsplit(const BwdQSplitArgs& sa, hipStream_t s) {
+  const BwdArgs& a = sa.b;
+  hipError_t e;
+  if (max(a.d, a.v_d) <= 64)
+    e = launch_smem(with_pol_aln(a, [](auto pol, auto aln) {
+                      return &bwd_dkdv_kernel<64, 4, 2, pol.value, aln.value, 1, true>;
+                    }),
+                    (unsigned)(a.b * sa.nchunks), 256, DkdvSmem<64, 4>::kTotal, s, sa);
+  else
+    e = launch_smem(
+        with_pol_aln(a, [](auto pol, auto aln) { return &bwd_dkdv_pc_kernel<128, pol.value, aln.value, true>; }),
+        (unsigned)(a.b * sa.nchunks), 512, PcSmem<128>::kTotal, s, sa);
+  if (e != hipSuccess) return e;
+  const int64_t threads = a.b * (int64_t)(a.d + a.v_d) * a.rule.k.n;
+  hipLaunchKernelGGL(dkdv_split_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, sa);
+  return hipGetLastError();
 }
 
 // -D and -lse2 of every query; eight queries a thread where the rows allow 16-B loads
@@ -698,6 +806,27 @@ hipError_t launch_bwd_f16_split(const BwdSplitArgs& sa, hipStream_t s) {
   e = launch_dkdv_pass(sa.b, s, -1);
   if (e != hipSuccess) return e;
   return launch_bwd_f16_dq_split(sa, s);
+}
+
+// Slices per call of launch_bwd_f16_qsplit: every grid (prep, split dK/dV, reduce, dQ) stays below 2^31 blocks.
+int64_t bwd_f16_qsplit_max_batch(const BwdQSplitArgs& sa) {
+  const BwdArgs& a = sa.b;
+  const int64_t reduce_blocks = ((int64_t)(a.d + a.v_d) * a.rule.k.n + 255) / 256;
+  const int64_t dq_blocks = 2 * (((int64_t)a.rule.q.n + 127) / 128);  // (the bound of bwd_f16_fast_supported; the prep's too)
+  int64_t per = sa.nchunks > reduce_blocks ? sa.nchunks : reduce_blocks;
+  if (dq_blocks > per) per = dq_blocks;
+  return ((1ll << 31) - 1) / per;
+}
+
+// One key block (nk <= 128), max(d, v_d) <= 128, against a long query range: the prep launch_bwd_f16_fast
+// runs for the shape, the dK/dV pass split over query chunks with its reduce, then the dQ pass
+// launch_bwd_f16_fast runs for the shape (dQ is bitwise its dQ)
+hipError_t launch_bwd_f16_qsplit(const BwdQSplitArgs& sa, hipStream_t s) {
+  hipError_t e = launch_prep(sa.b, s);
+  if (e != hipSuccess) return e;
+  e = launch_dkdv_qsplit(sa, s);
+  if (e != hipSuccess) return e;
+  return launch_bwd_f16_dq(sa.b, s, -1);
 }
 
 hipError_t launch_bwd_f16_fast(const BwdArgs& a, hipStream_t s) {

@@ -63,6 +63,16 @@ struct BwdSplitArgs {
   int32_t k_end;    // one past the range's last key
 };
 
+// split-query dK/dV pass of the fp16 backward (fa_bwd_f16_fast.hip): the plan of fa_api.hip plus the partials
+struct BwdQSplitArgs {
+  BwdArgs b;
+  float* ws_part;   // [b][nchunks][d + v_d][nk] floats: unscaled fp32 dK (d rows), then dV (v_d rows) partials
+  int32_t nchunks;  // chunks of the query range, >= 2
+  int32_t chunk;    // queries per chunk (a multiple of four 32-query tiles)
+  int32_t q_first;  // first query of chunk 0 (tile-aligned, <= the range's first query)
+  int32_t q_end;    // one past the range's last query
+};
+
 // generic (any dtype) path — fa_generic.hip
 hipError_t launch_fwd_generic(int dtype, const FwdArgs& a, hipStream_t s);
 hipError_t launch_bwd_generic(int dtype, const BwdArgs& a, hipStream_t s);
@@ -134,6 +144,12 @@ hipError_t launch_bwd_f16_fast(const BwdArgs& a, hipStream_t s);
 // At most bwd_f16_split_max_batch() slices per call (grid limits).
 int64_t bwd_f16_split_max_batch(const BwdSplitArgs& sa);
 hipError_t launch_bwd_f16_split(const BwdSplitArgs& sa, hipStream_t s);
+// the mirrored shape, many queries against one key block (nk <= 128, max(d, v_d) <= 128): the prep, then the
+// dK/dV pass on one workgroup per (slice, query chunk) writing fp32 partials and a reduce kernel that sums
+// them in chunk order, then the dQ pass as above — fa_bwd_f16_fast.hip.  At most
+// bwd_f16_qsplit_max_batch() slices per call (grid limits).
+int64_t bwd_f16_qsplit_max_batch(const BwdQSplitArgs& sa);
+hipError_t launch_bwd_f16_qsplit(const BwdQSplitArgs& sa, hipStream_t s);
 
 }  // namespace fa
 

@@ -229,8 +229,9 @@ def attention_backward(policy: str, seq_dims: int, Q, K, V, O, l, m, dO, sync_mo
     prob = _lib.make_problem(dt, _POLICIES[policy], seq_dims, sid, _prod(Qb), Qs, Ks, Q_ch, V_ch,
                              window_size, log2_stride_size, is_causal)
     L = _lib.lib()
-    # few queries against a long key range: the dQ pass splits over key chunks (more scratch);
-    # everywhere else this is fa_backward and its workspace
+    # few queries against a long key range: the dQ pass splits over key chunks; many queries against
+    # one key block: the dK/dV pass splits over query chunks (more scratch either way); everywhere
+    # else this is fa_backward and its workspace
     ws_bytes = L.fa_backward_split_workspace_bytes(prob)
     ws = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=Q.device)
     with torch.cuda.device(Q.device):

@@ -281,7 +281,8 @@ class FaBackwardOp : public OpKernel {
     OP_REQUIRES_OK(ctx, ctx->allocate_output(0, Q.shape(), &dQ));
     OP_REQUIRES_OK(ctx, ctx->allocate_output(1, K.shape(), &dK));
     OP_REQUIRES_OK(ctx, ctx->allocate_output(2, V.shape(), &dV));
-    // outside the split-key envelope these are fa_backward_workspace_bytes and fa_backward
+    // outside the split-key (dQ) and split-query (dK/dV) envelopes these are fa_backward_workspace_bytes
+    // and fa_backward
     const size_t ws_bytes = fa_backward_split_workspace_bytes(&p);
     Tensor ws;
     OP_REQUIRES_OK(ctx, ctx->allocate_temp(DT_UINT8, TensorShape({static_cast<int64_t>(ws_bytes > 0 ? ws_bytes : 1)}), &ws));

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the kernels of two AMDGPU assembly files (hipcc --cuda-device-only -S) by demangled name.
 
-    tools/asm_equal.py OLD.s NEW.s          (several translation units: concatenate their .s files)
+    tools/asm_equal.py [--sub PATTERN REPL ...] OLD.s NEW.s   (several translation units: concatenate their .s files)
 
 Per kernel: IDENTICAL when the instruction stream (comments, labels and symbol names dropped) and the
 resource lines (.amdhsa_* descriptor, occupancy, register / scratch / LDS counts) are equal; otherwise
@@ -65,10 +65,18 @@ def demangle(names):
 
 
 def main():
+    # --sub PATTERN REPL (repeatable, before the files): a regex substitution on the demangled names of both
+    # sides, for a kernel whose name changed but whose code should not have (a new defaulted template flag)
+    subs = []
+    while len(sys.argv) > 4 and sys.argv[1] == "--sub":
+        subs.append((re.compile(sys.argv[2]), sys.argv[3]))
+        del sys.argv[1:4]
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     old, new = parse(sys.argv[1]), parse(sys.argv[2])
     dm = demangle(sorted(set(old) | set(new)))
+    for pat, repl in subs:
+        dm = {k: pat.sub(repl, v) for k, v in dm.items()}
     old = {dm[k]: v for k, v in old.items()}
     new = {dm[k]: v for k, v in new.items()}
     bad = 0
