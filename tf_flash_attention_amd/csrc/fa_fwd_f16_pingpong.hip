@@ -12,10 +12,12 @@
 //   interval  2i  : group 0 MFMA(i)      | group 1 VALU(i-1)
 //   interval 2i+1 : group 0 VALU(i)      | group 1 MFMA(i)
 //
-// (both groups run the same loop; group 1 enters it one barrier late)
+// (both groups run the same loop; group 1 enters it one barrier late.  The loop takes whole groups of
+// three tiles; the one or two tiles left run as iterations without staging, and the PV of the last
+// tile runs on its own after the wave's last barrier: no step past the last tile.)
 //
-//   MFMA(i) = Sᵀ MFMAs of tile i + PV MFMAs of tile i-1 (16 MFMAs, unconditional: P is zero for a
-//             skipped tile), at priority 1, each pair followed by the fragment reads it frees
+//   MFMA(i) = Sᵀ MFMAs of tile i + PV MFMAs of tile i-1 (16 MFMAs, unconditional: P is zero before
+//             the first tile), at priority 1, each pair followed by the fragment reads it frees
 //             registers for (K(i+1) after the Sᵀ pairs, V(i) after the PV pairs), one staging store
 //             and one staging load pinned after the second pair of each half (sched_group_barrier)
 //   VALU(i) = softmax of tile i (tail mask, speculative exp2, rebase check on the packed P, rare
@@ -305,8 +307,10 @@ __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong_kernel(FwdArgs a
   // the V(i) fragment reads; this wave's chunks of K(i+3) / V(i+2) into LDS (over K(i) / V(i-1),
   // whose fragments were read in MFMA(i-1)) and the loads of K(i+6) / V(i+5).  All LDS traffic sits
   // in the MFMA phase, beside the matrix pipe, so the VALU phase is the softmax alone.
-  auto mfma_phase = [&](auto C_, int it) __attribute__((always_inline)) {
+  // ST: with the staging (the loop); without it (the drain: every tile it would move is past the end).
+  auto mfma_phase = [&](auto C_, auto ST_, int it) __attribute__((always_inline)) {
     constexpr int c = decltype(C_)::value;  // it mod 3
+    constexpr bool ST = decltype(ST_)::value != 0;
     __builtin_amdgcn_s_setprio(1);
     const lds_char_t* pk = smem + kOffK + ((c + 1) % kNS) * kTile;
     const lds_char_t* pv = smem + kOffV + c * kTile;
@@ -335,28 +339,31 @@ __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong_kernel(FwdArgs a
     for (int s = 0; s < 4; ++s) {
       __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-      if (s == 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // a staging store
-      if (s == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // a staging load
+      if (ST && s == 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // a staging store
+      if (ST && s == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // a staging load
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      if (s == 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-      if (s == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      if (ST && s == 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+      if (ST && s == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
     }
-    // (unconditional: past the end these move zeros into slots nobody reads unmasked)
-    store(kOffK + c * kTile + kwo, kst[c]);
-    store(kOffV + ((c + 2) % kNS) * kTile + vwo, vst[c]);
-    kst[c] = load(krs, koff, (it + 6) * kBN);
-    vst[c] = load(vrs, voff, (it + 5) * kBN);
+    if constexpr (ST) {
+      // (unconditional: past the end these move zeros into slots nobody reads unmasked)
+      store(kOffK + c * kTile + kwo, kst[c]);
+      store(kOffV + ((c + 2) % kNS) * kTile + vwo, vst[c]);
+      kst[c] = load(krs, koff, (it + 6) * kBN);
+      vst[c] = load(vrs, voff, (it + 5) * kBN);
+    }
     // No lgkmcnt drain here: a wave's LDS operations complete in order, and each wave waits for
     // its fragment reads before the MFMAs that use them (MFMA(i+1)), which orders its stores of
     // this phase before any other wave reads those tiles (MFMA(i+2)) and its reads before any
     // wave overwrites their slots (MFMA(i+1) for itself, one interval later for the others).
     __builtin_amdgcn_s_setprio(0);
   };
-  // VALU(i): the softmax of tile i; past the end P = 0, so the next (unconditional) PV adds nothing
+  // VALU(i): the softmax of tile i; past the end (only with fewer than three tiles, see the loop)
+  // P = 0, so the PV that follows adds nothing
   auto valu_phase = [&](int it) __attribute__((always_inline)) {
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's staging stores landed
     const int cls = tcls(it);
@@ -369,8 +376,8 @@ __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong_kernel(FwdArgs a
     }
   };
 
-  // Both groups run the same loop (one code path keeps the register allocation sane); group 1
-  // enters it one barrier late and group 0 leaves it one barrier late, so every barrier
+  // Both groups run the same loop and drain (one code path keeps the register allocation sane);
+  // group 1 enters one barrier late and group 0 leaves one barrier late, so every barrier
   // interval pairs one group's MFMA(i) with the other's VALU phase.
   {
     const lds_char_t* p = smem + kOffK;
@@ -383,21 +390,53 @@ __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong_kernel(FwdArgs a
       }
   }
   if (grp == 1) __builtin_amdgcn_s_barrier();
-  auto iter = [&](auto C_, int it) __attribute__((always_inline)) {
+  auto iter = [&](auto C_, auto ST_, int it) __attribute__((always_inline)) {
     __builtin_amdgcn_s_barrier();
-    mfma_phase(C_, it);
+    mfma_phase(C_, ST_, it);
     __builtin_amdgcn_s_barrier();
     valu_phase(it);
   };
-  // Whole groups of three iterations, none conditional (the last ones past the end only move
-  // zeros): with no control flow around the staging loads, hipcc's vmcnt waits stay exact and
-  // a store waits only for the load issued three steps earlier.
-  for (int it = 0; it <= ntiles; it += kNS) {
-    iter(IC<0>{}, it);
-    iter(IC<1>{}, it + 1);
-    iter(IC<2>{}, it + 2);
-  }
+  // Whole groups of three iterations while all three carry a tile, none conditional: with no
+  // control flow around the staging loads, hipcc's vmcnt waits stay exact and a store waits only
+  // for the load issued three steps earlier.  The first group runs whatever ntiles is: a loop
+  // that may run zero times costs this one its register allocation (40 VGPRs spilled, the staging
+  // registers among them), so fewer than three tiles take one group with steps past the end, whose
+  // P is zero and whose staging moves zeros into slots nobody reads unmasked.
+  int it = 0;
+  do {
+    iter(IC<0>{}, IC<1>{}, it);
+    iter(IC<1>{}, IC<1>{}, it + 1);
+    iter(IC<2>{}, IC<1>{}, it + 2);
+    it += kNS;
+  } while (it + kNS <= ntiles);
+  // The drain: the ntiles mod 3 tiles left, at ring phases 0 and 1, without staging (it >= ntiles - 2:
+  // K(it+3), V(it+2), K(it+6) and V(it+5) all lie past the end), then the PV of the last tile on its
+  // own: its V fragments were read in MFMA(ntiles-1) and its P is this wave's, so it needs no LDS
+  // and no barrier.  Group 0 runs it after the barrier that starts group 1's last VALU phase.
+  // (ntiles < 3: the group above ran PV(ntiles-1) in MFMA(ntiles) already, and P is zero here.)
+  //
+  // Barrier parity.  Every branch here is on ntiles alone, the same for all eight waves, and no
+  // wave returns before the epilogue.  Each iteration, looped or drained, has two barriers; with
+  // n = max(ntiles, 3) there are 3·(n / 3) iterations in the loop and n mod 3 in the drain, n in all.
+  //   group 0:  2n (iterations) + 1 (below)
+  //   group 1:  1 (above) + 2n (iterations)
+  //   ntiles = 3j:    loop 3j, drain 0   -> 6j + 1 each
+  //   ntiles = 3j+1:  loop 3j, drain 1   -> 6j + 3 each     (j >= 1)
+  //   ntiles = 3j+2:  loop 3j, drain 2   -> 6j + 5 each
+  //   ntiles < 3:     loop 3,  drain 0   -> 7 each
+  // Interval 2i is group 0's MFMA(i) beside group 1's VALU(i-1), interval 2i+1 group 0's VALU(i)
+  // beside group 1's MFMA(i), as in the loop; the last barrier opens group 1's VALU(n-1).
+  if (it < ntiles) iter(IC<0>{}, IC<0>{}, it);
+  if (it + 1 < ntiles) iter(IC<1>{}, IC<0>{}, it + 1);
   if (grp == 0) __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const half8 p = __builtin_bit_cast(half8, u32x4{pw[s][0], pw[s][1], pw[s][2], pw[s][3]});
+#pragma unroll
+    for (int u = 0; u < 2; ++u) o[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[s][u], p, o[u], 0, 0, 0);
+  }
+  __builtin_amdgcn_s_setprio(0);
 
   // ---- epilogue
   if (!wave_active) return;
@@ -449,7 +488,8 @@ bool fwd_f16_pingpong_supported(const FwdArgs& a) {
 // tuned (c2, MI355X): MFMA phases at priority 1, fragment reads and staging
 // interleaved with the MFMAs (0.5526-0.5716 ms against 0.595 without), row sums in running
 // accumulators (0.5451 against 0.5552 ms), rebase check and m on the packed P (0.5395-0.5441
-// against 0.5512-0.5553 ms)
+// against 0.5512-0.5553 ms), the drain in place of the steps past the last tile (0.549-0.553 against
+// 0.557-0.569 ms)
 hipError_t launch_fwd_f16_pingpong(const FwdArgs& a, hipStream_t s) {
   const int64_t nqb = (a.rule.q.n + kBM - 1) / kBM;
   hipError_t e = set_smem_once(reinterpret_cast<const void*>(fwd_f16_pingpong_kernel), kSmem);
