@@ -165,6 +165,40 @@ int fa_backward_split(void* stream, const fa_problem* p,
                       void* dQ, void* dK, void* dV,
                       void* workspace, size_t workspace_bytes);
 
+/* Merging partial results: attention over the union of several key sets from attention over each.
+ *
+ * A partial is what any forward above writes for one key set against the shared Q, in the layouts
+ * at the top: O_i [b][v_d][nq] in T, l_i [b][nq] in L_T relative to the STORED m_i, m_i [b][nq] in T
+ * (the row max of the scaled scores, scale = 1/sqrt(d) of the shared Q in every part).  A part is
+ * empty for a row iff l_i == 0 (its m_i is then the NegInfApprox byte pattern, every byte 0xFA, and
+ * stays out of the max).  Per slice and query row, over the non-empty parts:
+ *     m = max_i m_i (exact in T)        e_i = l_i * exp(m_i - m)     L = sum_i e_i  (part order)
+ *     w_i = e_i / L (correctly rounded) O = T(sum_i w_i * O_i)  (part order)          l = L
+ * accumulated in fp32 (fp64 for FA_F64).  A row empty in every part gets O = 0, l = 0, m = NegInfApprox,
+ * as the forwards write it.  (O, l, m) is then the forward's output for the concatenated keys; a key that
+ * appears in two parts counts twice.  fa_backward called per part with the MERGED (O, l, m) gives that
+ * part's exact dK and dV, and the parts' dQ sum to the union's dQ (fa_accumulate_parts).
+ * The weights are normalised before they multiply O: one part comes back bit for bit, and a part that is
+ * empty in every row leaves the result of the others bit for bit unchanged.  The result is deterministic
+ * and a slice's bits do not depend on b.
+ *
+ * fa_merge_partials: O_parts / l_parts / m_parts are HOST arrays of n_parts device pointers, read during
+ *   the call (they travel to the kernel by value: no device pointer table, no host synchronisation, safe
+ *   inside hipGraph capture).  1 <= n_parts <= FA_MAX_PARTS.  Vector loads where nq is a multiple of
+ *   16 bytes of T and every pointer is 16-byte aligned; any other nq or alignment takes a scalar path.
+ * fa_accumulate_parts: out[i] = T(sum_p acc(parts[p][i])) for i < count, summed in part order in fp32
+ *   (fp64 for FA_F64): one rounding for dQ = sum_p dQ_p.
+ * Both return FA_ERR_INVALID_ARGUMENT (text in fa_last_error()) for an unknown dtype, n_parts outside
+ * 1..FA_MAX_PARTS, a negative size, v_d < 1, a null pointer where there is work to do, or an output pointer
+ * equal to an input pointer; all checked on the host before any device call.  b * nq == 0 (count == 0)
+ * returns FA_OK with nothing launched. */
+#define FA_MAX_PARTS 8
+int fa_merge_partials(void* stream, int32_t dtype, int64_t b, int64_t nq, int32_t v_d, int32_t n_parts,
+                      const void* const* O_parts, const void* const* l_parts, const void* const* m_parts,
+                      void* O, void* l, void* m);
+int fa_accumulate_parts(void* stream, int32_t dtype, int64_t count, int32_t n_parts,
+                        const void* const* parts, void* out);
+
 /* Algorithmic forward FLOPs 2*(d+v_d)*P, P = rule-allowed (q,k) pairs summed
  * over b (host-only; replaces EstimateForwardFlops, flash_attention.cu:2069-2144,
  * which counted issued tiles instead). */

@@ -23,6 +23,7 @@ FA_OK = 0
 FA_ERR_INVALID_ARGUMENT = -1
 FA_ERR_UNSUPPORTED = -2
 FA_ERR_WORKSPACE_TOO_SMALL = -3
+FA_MAX_PARTS = 8
 
 # every symbol include/fa_api.h declares (checked by tests/test_boundary.py)
 EXPORTED_SYMBOLS = (
@@ -38,6 +39,8 @@ EXPORTED_SYMBOLS = (
     "fa_backward_split_q_plan",
     "fa_backward_split_workspace_bytes",
     "fa_backward_split",
+    "fa_merge_partials",
+    "fa_accumulate_parts",
     "fa_estimate_forward_flops",
     "fa_allowed_pairs",
     "fa_error_string",
@@ -114,6 +117,14 @@ def _declare(lib):
     if hasattr(lib, "fa_backward_split_q_plan"):
         lib.fa_backward_split_q_plan.argtypes = [P, ctypes.POINTER(ctypes.c_int32)]
         lib.fa_backward_split_q_plan.restype = ctypes.c_int
+    # (absent from a library built before the merge of partials, as above)
+    if hasattr(lib, "fa_merge_partials"):
+        pp = ctypes.POINTER(vp)  # a host array of device pointers
+        lib.fa_merge_partials.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                          ctypes.c_int32, pp, pp, pp, vp, vp, vp]
+        lib.fa_merge_partials.restype = ctypes.c_int
+        lib.fa_accumulate_parts.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, pp, vp]
+        lib.fa_accumulate_parts.restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]
@@ -204,6 +215,14 @@ def make_problem(dtype, policy, seq_dims, sync_mode, b, q_seq, k_seq, d, v_d,
     p.d, p.v_d = int(d), int(v_d)
     p.window_size, p.log2_stride_size, p.is_causal = int(window_size), int(log2_stride_size), int(bool(is_causal))
     return p
+
+
+def pointer_array(ptrs):
+    """A host array of device pointers (``const void* const*``) for fa_merge_partials / fa_accumulate_parts,
+    or None (a null array) for ``ptrs`` None."""
+    if ptrs is None:
+        return None
+    return (ctypes.c_void_p * len(ptrs))(*[int(p) if p else None for p in ptrs])
 
 
 def source_hash(diag: bool = False) -> str:

@@ -596,6 +596,85 @@ int fa_backward_split(void* stream, const fa_problem* p, const void* Q, const vo
   return FA_OK;
 }
 
+int fa_merge_partials(void* stream, int32_t dtype, int64_t b, int64_t nq, int32_t v_d, int32_t n_parts,
+                      const void* const* O_parts, const void* const* l_parts, const void* const* m_parts, void* O,
+                      void* l, void* m) {
+  if (dtype < FA_F16 || dtype > FA_F64) return set_error(FA_ERR_INVALID_ARGUMENT, "unknown dtype");
+  if (n_parts < 1 || n_parts > FA_MAX_PARTS)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "n_parts must be in [1, " + std::to_string(FA_MAX_PARTS) + "]");
+  if (b < 0) return set_error(FA_ERR_INVALID_ARGUMENT, "negative batch size");
+  if (nq < 0) return set_error(FA_ERR_INVALID_ARGUMENT, "negative sequence extent");
+  if (nq > 0x7fffffff)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "sequence sizes are limited to the int32 range (sync_methods.h:12-14)");
+  if (v_d < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "channel dimensions must be >= 1");
+  if (b == 0 || nq == 0) return FA_OK;
+  if (!O_parts || !l_parts || !m_parts) return set_error(FA_ERR_INVALID_ARGUMENT, "null array of part pointers");
+  if (!O || !l || !m) return set_error(FA_ERR_INVALID_ARGUMENT, "null output pointer");
+  fa::MergeArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int i = 0; i < n_parts; ++i) {
+    if (!O_parts[i] || !l_parts[i] || !m_parts[i])
+      return set_error(FA_ERR_INVALID_ARGUMENT, "null pointer in part " + std::to_string(i));
+    for (const void* in : {O_parts[i], l_parts[i], m_parts[i]})
+      if (in == O || in == l || in == m)
+        return set_error(FA_ERR_INVALID_ARGUMENT, "an output aliases an input of part " + std::to_string(i));
+    a.O_parts[i] = O_parts[i]; a.l_parts[i] = l_parts[i]; a.m_parts[i] = m_parts[i];
+  }
+  const int64_t bmax = fa::merge_max_batch(dtype, nq, v_d);
+  if (bmax < 1) return set_error(FA_ERR_UNSUPPORTED, "one slice exceeds the merge kernel's grid");
+  const size_t es = elem_size(dtype), ls = dtype == FA_F16 ? sizeof(float) : es;
+  a.nq = nq; a.v_d = v_d;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // slabs of at most bmax slices: the grid's y extent
+  for (int64_t b0 = 0; b0 < b; b0 += bmax) {
+    a.b = b - b0 < bmax ? b - b0 : bmax;
+    const size_t o_off = es * (size_t)b0 * (size_t)v_d * (size_t)nq, l_off = ls * (size_t)b0 * (size_t)nq,
+                 m_off = es * (size_t)b0 * (size_t)nq;
+    for (int i = 0; i < n_parts; ++i) {
+      a.O_parts[i] = static_cast<const char*>(O_parts[i]) + o_off;
+      a.l_parts[i] = static_cast<const char*>(l_parts[i]) + l_off;
+      a.m_parts[i] = static_cast<const char*>(m_parts[i]) + m_off;
+    }
+    a.O = static_cast<char*>(O) + o_off;
+    a.l = static_cast<char*>(l) + l_off;
+    a.m = static_cast<char*>(m) + m_off;
+    const hipError_t e = fa::launch_merge(dtype, n_parts, a, s);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the merge kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
+int fa_accumulate_parts(void* stream, int32_t dtype, int64_t count, int32_t n_parts, const void* const* parts,
+                        void* out) {
+  if (dtype < FA_F16 || dtype > FA_F64) return set_error(FA_ERR_INVALID_ARGUMENT, "unknown dtype");
+  if (n_parts < 1 || n_parts > FA_MAX_PARTS)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "n_parts must be in [1, " + std::to_string(FA_MAX_PARTS) + "]");
+  if (count < 0) return set_error(FA_ERR_INVALID_ARGUMENT, "negative element count");
+  if (count == 0) return FA_OK;
+  if (!parts) return set_error(FA_ERR_INVALID_ARGUMENT, "null array of part pointers");
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null output pointer");
+  for (int i = 0; i < n_parts; ++i) {
+    if (!parts[i]) return set_error(FA_ERR_INVALID_ARGUMENT, "null pointer in part " + std::to_string(i));
+    if (parts[i] == out)
+      return set_error(FA_ERR_INVALID_ARGUMENT, "the output aliases the input of part " + std::to_string(i));
+  }
+  fa::AccumulateArgs a;
+  memset(&a, 0, sizeof(a));
+  const size_t es = elem_size(dtype);
+  const int64_t cmax = fa::accumulate_max_count();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int64_t c0 = 0; c0 < count; c0 += cmax) {
+    a.count = count - c0 < cmax ? count - c0 : cmax;
+    for (int i = 0; i < n_parts; ++i) a.parts[i] = static_cast<const char*>(parts[i]) + es * (size_t)c0;
+    a.out = static_cast<char*>(out) + es * (size_t)c0;
+    const hipError_t e = fa::launch_accumulate(dtype, n_parts, a, s);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the accumulate kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
 int64_t fa_allowed_pairs(const fa_problem* p) {
   if (fa_validate(p) != FA_OK) return -1;
   fa::Rule r;
@@ -671,7 +750,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
 }
 
 }  // extern "C"

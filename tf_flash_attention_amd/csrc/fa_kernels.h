@@ -73,6 +73,34 @@ struct BwdQSplitArgs {
   int32_t q_end;    // one past the range's last query
 };
 
+// merge of partial results over several key sets and the part-order sum (fa_merge.hip): the parts'
+// pointers travel by value in the kernel arguments (no device pointer table)
+constexpr int kMaxParts = 8;  // FA_MAX_PARTS
+
+struct MergeArgs {
+  const void* O_parts[kMaxParts];  // [b][v_d][nq] T
+  const void* l_parts[kMaxParts];  // [b][nq] L_T, relative to the stored m
+  const void* m_parts[kMaxParts];  // [b][nq] T
+  void* O;
+  void* l;
+  void* m;
+  int64_t b, nq;
+  int32_t v_d;
+};
+
+struct AccumulateArgs {
+  const void* parts[kMaxParts];  // count elements of T each
+  void* out;
+  int64_t count;
+};
+
+// Slices per launch (the grid's y extent; 0: one slice alone exceeds the 32-bit index of its threads).
+int64_t merge_max_batch(int dtype, int64_t nq, int32_t v_d);
+hipError_t launch_merge(int dtype, int n_parts, const MergeArgs& a, hipStream_t s);
+// Elements per launch, a multiple of every vector width.
+int64_t accumulate_max_count();
+hipError_t launch_accumulate(int dtype, int n_parts, const AccumulateArgs& a, hipStream_t s);
+
 // generic (any dtype) path — fa_generic.hip
 hipError_t launch_fwd_generic(int dtype, const FwdArgs& a, hipStream_t s);
 hipError_t launch_bwd_generic(int dtype, const BwdArgs& a, hipStream_t s);

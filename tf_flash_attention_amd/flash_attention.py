@@ -8,6 +8,13 @@ Public API (same names, argument meaning, defaults and return convention as
     local_1d(Q, K, V, window_size, log2_stride_size, is_causal, sync_mode, returning_l_m=False)
     full_2d / causal_2d / local_2d   (same, for 2-D sequences)
 
+Beyond the reference: attention of one ``Q`` over the union of several key sets, each under its own
+rule (a window plus global tokens, self-attention plus a prompt, key shards), with exact gradients::
+
+    combined_1d(Q, [Part('local', K, V, window_size=256), Part('full', Kg, Vg)], returning_l_m=False)
+    combined_2d(Q, parts, returning_l_m=False)
+    merge_partials(Os, ls, ms, seq_dims=1) -> (O, l, m)      (op level, no autograd)
+
 Tensors are ``torch`` tensors on a ROCm device in the reference's channel-first
 layout ``batch_shape + (C, *seq_shape)``.  Each call returns ``O`` or
 ``(O, l, m)``; autograd flows through ``O`` only (gradients of ``l``/``m`` are
@@ -36,6 +43,7 @@ from . import _lib
 __all__ = [
     "full_1d", "causal_1d", "local_1d", "full_2d", "causal_2d", "local_2d",
     "InvalidArgumentError", "InternalError", "estimate_forward_flops",
+    "Part", "combined_1d", "combined_2d", "merge_partials",
 ]
 
 
@@ -299,6 +307,176 @@ def causal_2d(Q, K, V, sync_mode, returning_l_m=False):
 def local_2d(Q, K, V, window_size, log2_stride_size, is_causal, sync_mode, returning_l_m=False):
     """Local attention on 2d sequences (flash_attention.py:312-370)."""
     return _attend("local", 2, Q, K, V, sync_mode, returning_l_m, window_size, log2_stride_size, is_causal)
+
+
+# ----------------------------------------------------------------------------
+# Combined attention: one Q over the union of several key sets, each under its own rule
+# (include/fa_api.h, "Merging partial results"; DESIGN.md §3.7)
+# ----------------------------------------------------------------------------
+MAX_PARTS = _lib.FA_MAX_PARTS
+
+
+class Part:
+    """One key set of a combined attention and the rule Q attends it under: ``policy`` in
+    {"full", "causal", "local"} with the arguments of the wrapper of that name."""
+
+    __slots__ = ("policy", "K", "V", "sync_mode", "window_size", "log2_stride_size", "is_causal")
+
+    def __init__(self, policy, K, V, sync_mode="none_front", window_size=1, log2_stride_size=0, is_causal=False):
+        if policy not in _POLICIES:
+            raise InvalidArgumentError(f"Unsupported policy: {policy}")
+        self.policy, self.K, self.V, self.sync_mode = policy, K, V, sync_mode
+        self.window_size, self.log2_stride_size, self.is_causal = int(window_size), int(log2_stride_size), bool(is_causal)
+
+    def attrs(self):
+        return self.policy, self.sync_mode, self.window_size, self.log2_stride_size, self.is_causal
+
+    def __repr__(self):
+        return (f"Part({self.policy!r}, K{_shape_str(self.K.shape)}, V{_shape_str(self.V.shape)}, "
+                f"sync_mode={self.sync_mode!r}, window_size={self.window_size}, "
+                f"log2_stride_size={self.log2_stride_size}, is_causal={self.is_causal})")
+
+
+def _check_part_count(n):
+    if not 1 <= n <= MAX_PARTS:
+        raise InvalidArgumentError(f"The number of parts should be in [1, {MAX_PARTS}], but {n} were received")
+
+
+def _same_dtype_and_device(ts):
+    """One dtype (TypeError) and one ROCm device (InvalidArgumentError) for all of ``ts``."""
+    for t in ts:
+        if t.dtype != ts[0].dtype:
+            raise TypeError(f"all tensors must share one dtype, got {ts[0].dtype} and {t.dtype}")
+    _check_device_tensors(*ts)
+
+
+def merge_partials(Os, ls, ms, seq_dims=1):
+    """Op-level merge (no autograd): the forward outputs ``(O_i, l_i, m_i)`` of one Q against several key
+    sets become ``(O, l, m)`` of Q against their union (``fa_merge_partials``).  Every part must come from
+    the same Q (scale 1/sqrt(d)); a key present in two parts counts twice.  Example: key shards under the
+    full policy, ``merge_partials(*zip(*[attention_forward("full", 1, Q, Ks, Vs, "none_front") for Ks, Vs in
+    shards]))`` equals ``full_1d`` over the concatenated keys."""
+    Os, ls, ms = list(Os), list(ls), list(ms)
+    if not (len(Os) == len(ls) == len(ms)):
+        raise InvalidArgumentError("The numbers of O, l and m partials should be equal")
+    _check_part_count(len(Os))
+    O0 = Os[0]
+    if O0.dim() < seq_dims + 1:
+        raise InvalidArgumentError(f"The number of dimensions of O should be >= {seq_dims + 1}")
+    ch = O0.dim() - seq_dims - 1
+    lm_shape = tuple(O0.shape[:ch]) + tuple(O0.shape[ch + 1:])
+    for O, l, m in zip(Os, ls, ms):
+        if tuple(O.shape) != tuple(O0.shape):
+            raise InvalidArgumentError("The shapes of all O partials should be equal, but " + _shape_str(O0.shape)
+                                       + " and " + _shape_str(O.shape) + " were received")
+        if tuple(l.shape) != lm_shape or tuple(m.shape) != lm_shape:
+            raise InvalidArgumentError(
+                "The shapes of l and m should be the one of O without its channel dimension, but O_shape = "
+                + _shape_str(O.shape) + ", l_shape = " + _shape_str(l.shape) + ", m_shape = " + _shape_str(m.shape)
+                + " were received")
+    dt = _dtype_id(O0, O0.dtype == torch.float16)
+    l_dtype = torch.float32 if dt == _lib.F16 else O0.dtype
+    for O, l, m in zip(Os, ls, ms):
+        if O.dtype != O0.dtype or m.dtype != O0.dtype:
+            raise TypeError(f"all O and m partials must have dtype {O0.dtype}, got {O.dtype} and {m.dtype}")
+        if l.dtype != l_dtype:
+            raise TypeError(f"l must be {l_dtype} for this dtype, got {l.dtype}")
+    _check_device_tensors(*Os, *ls, *ms)
+    Os, ls, ms = ([t.contiguous() for t in ts] for ts in (Os, ls, ms))
+    O, l, m = torch.empty_like(Os[0]), torch.empty_like(ls[0]), torch.empty_like(ms[0])
+    nq = _prod(O0.shape[ch + 1:])
+    with torch.cuda.device(O.device):
+        st = _lib.lib().fa_merge_partials(
+            _stream_handle(O.device), dt, _prod(O0.shape[:ch]), nq, int(O0.shape[ch]), len(Os),
+            _lib.pointer_array([t.data_ptr() for t in Os]), _lib.pointer_array([t.data_ptr() for t in ls]),
+            _lib.pointer_array([t.data_ptr() for t in ms]), O.data_ptr(), l.data_ptr(), m.data_ptr())
+    if st != _lib.FA_OK:
+        _raise_status(st, "merge")
+    return O, l, m
+
+
+def _accumulate_parts(ts):
+    """T(sum of ``ts`` in order, accumulated in fp32 / fp64): ``fa_accumulate_parts``."""
+    if len(ts) == 1:
+        return ts[0]
+    ts = [t.contiguous() for t in ts]
+    out = torch.empty_like(ts[0])
+    with torch.cuda.device(out.device):
+        st = _lib.lib().fa_accumulate_parts(_stream_handle(out.device), _DTYPES[out.dtype], out.numel(), len(ts),
+                                            _lib.pointer_array([t.data_ptr() for t in ts]), out.data_ptr())
+    if st != _lib.FA_OK:
+        _raise_status(st, "accumulate")
+    return out
+
+
+class _CombinedFn(torch.autograd.Function):
+    """Forward of every part + merge; the backward calls each part's backward op with the MERGED (O, l, m):
+    P = exp(s - m) / l is then the union's probability, so dK_i and dV_i are exact and dQ = sum_i dQ_i."""
+
+    @staticmethod
+    def forward(ctx, Q, seq_dims, attrs, *KV):
+        Os, ls, ms = [], [], []
+        for i, (policy, sync_mode, ws, ls_, causal) in enumerate(attrs):
+            O, l, m = attention_forward(policy, seq_dims, Q, KV[2 * i], KV[2 * i + 1], sync_mode, ws, ls_, causal)
+            Os.append(O); ls.append(l); ms.append(m)
+        O, l, m = merge_partials(Os, ls, ms, seq_dims)
+        ctx.save_for_backward(Q, *KV, O, l, m)  # (not the partials)
+        ctx.attrs = (seq_dims, attrs)
+        ctx.mark_non_differentiable(l, m)
+        return O, l, m
+
+    @staticmethod
+    def backward(ctx, dO, dl, dm):
+        Q, *KV, O, l, m = ctx.saved_tensors
+        seq_dims, attrs = ctx.attrs
+        if dO is None:
+            dO = torch.zeros_like(O)
+        need = ctx.needs_input_grad
+        dQs, dKV = [], []
+        for i, (policy, sync_mode, ws, ls_, causal) in enumerate(attrs):
+            if not (need[0] or need[3 + 2 * i] or need[4 + 2 * i]):
+                dKV += [None, None]
+                continue
+            # (a part whose K and V need no gradient still contributes its dQ)
+            dQ, dK, dV = attention_backward(policy, seq_dims, Q, KV[2 * i], KV[2 * i + 1], O, l, m, dO, sync_mode,
+                                            ws, ls_, causal)
+            dQs.append(dQ)
+            dKV += [dK, dV]
+        return (_accumulate_parts(dQs) if need[0] else None, None, None, *dKV)
+
+
+def _combined(seq_dims, Q, parts, returning_l_m):
+    parts = list(parts)
+    _check_part_count(len(parts))
+    for p in parts:
+        if not isinstance(p, Part):
+            raise TypeError(f"parts must be Part records, got {type(p).__name__}")
+        _sync_mode_id(p.sync_mode)
+        verify_and_extract_shapes(seq_dims, Q.shape, p.K.shape, p.V.shape)
+    ch = Q.dim() - seq_dims - 1
+    for p in parts:
+        if p.V.shape[ch] != parts[0].V.shape[ch]:
+            raise InvalidArgumentError(
+                "The channel dimension of V should be equal in all parts, but " + str(int(parts[0].V.shape[ch]))
+                + " and " + str(int(p.V.shape[ch])) + " were received")
+    KV = [t for p in parts for t in (p.K, p.V)]
+    _dtype_id(Q, Q.dtype == torch.float16)
+    _same_dtype_and_device([Q] + KV)
+    results = _CombinedFn.apply(Q, seq_dims, tuple(p.attrs() for p in parts), *KV)
+    return results if returning_l_m else results[0]
+
+
+def combined_1d(Q, parts, returning_l_m=False):
+    """Attention of Q over the union of the key sets of ``parts`` (1 to 8 :class:`Part` records), each under
+    its own rule, on 1d sequences: softmax over all the parts' allowed keys at scale 1/sqrt(d).  Every part
+    runs the forward it runs alone; the results are merged on the device.  Gradients flow to Q and to every
+    part's K and V, exactly (through each part's normaliser too).  Returns ``O`` or ``(O, l, m)``."""
+    return _combined(1, Q, parts, returning_l_m)
+
+
+def combined_2d(Q, parts, returning_l_m=False):
+    """:func:`combined_1d` for 2d sequences."""
+    return _combined(2, Q, parts, returning_l_m)
 
 
 # ----------------------------------------------------------------------------

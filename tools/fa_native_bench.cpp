@@ -4,7 +4,8 @@
 // `make -C tf_flash_attention_amd native` into tools/fa_native_bench.
 //
 //   fa_native_bench check                       small problems vs a double-precision CPU
-//                                               loop (every policy, fp16/fp32/fp64)
+//                                               loop (every policy, fp16/fp32/fp64), and one
+//                                               combined case (a window + global keys, merged)
 //   fa_native_bench time <cfg> [iters]          hipEvent-timed forward / backward of a
 //                                               BASELINE config: c2 c3 c4 c5
 // Prints one JSON line per result.
@@ -113,6 +114,120 @@ double max_rel_err(const std::vector<unsigned char>& got, int dt, const std::vec
   return err / mref;
 }
 
+// Combined attention through the C ABI only: a local window (33) over 200 keys plus 8 global keys, fp16.
+// Forward of each part, fa_merge_partials, each part's backward with the MERGED (O, l, m),
+// fa_accumulate_parts over the parts' dQ; against a dense double-precision softmax over the 208 keys
+// (the window's mask from fa_rule_mask, the global keys all allowed).  Returns the number of failures.
+int check_combined() {
+  const int dt = FA_F16, nq = 200, d = 64, nks[2] = {200, 8};
+  const int64_t b = 2;
+  fa_problem ps[2] = {};
+  for (int i = 0; i < 2; ++i) {
+    fa_problem& p = ps[i];
+    p.dtype = dt; p.policy = i == 0 ? FA_LOCAL : FA_FULL; p.seq_dims = 1; p.sync_mode = FA_NONE_FRONT; p.b = b;
+    p.q_seq[0] = nq; p.k_seq[0] = nks[i]; p.d = p.v_d = d; p.window_size = i == 0 ? 33 : 1;
+    if (fa_validate(&p) != FA_OK) { fprintf(stderr, "invalid case: %s\n", fa_last_error()); return 1; }
+  }
+  std::mt19937_64 rng(4321);
+  std::uniform_real_distribution<double> U(-2.0, 2.0);
+  auto rnd = [&](size_t n, std::vector<unsigned char>* h) {  // values already rounded to the dtype
+    std::vector<double> x(n);
+    for (auto& v : x) v = U(rng);
+    to_dtype(x, dt, h);
+    for (size_t i = 0; i < n; ++i) x[i] = from_dtype(h->data(), dt, i);
+    return x;
+  };
+  std::vector<unsigned char> hq, hg, hk[2], hv[2];
+  const std::vector<double> Q = rnd(b * d * nq, &hq), G = rnd(b * d * nq, &hg);
+  const std::vector<double> K[2] = {rnd(b * d * nks[0], &hk[0]), rnd(b * d * nks[1], &hk[1])};
+  const std::vector<double> V[2] = {rnd(b * d * nks[0], &hv[0]), rnd(b * d * nks[1], &hv[1])};
+
+  // ---- device: forwards, merge, backwards with the merged statistics, dQ sum
+  const size_t es = esize(dt), les = 4;
+  Dev q(hq.size()), g(hg.size()), o(hq.size()), l(b * nq * les), m(b * nq * es), dq(hq.size());
+  HIP_OK(hipMemcpy(q.p, hq.data(), hq.size(), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(g.p, hg.data(), hg.size(), hipMemcpyHostToDevice));
+  std::vector<Dev*> owned;
+  auto dev = [&](size_t n) { owned.push_back(new Dev(n)); return owned.back()->p; };
+  void *k[2], *v[2], *oi[2], *li[2], *mi[2], *dqi[2], *dk[2], *dv[2];
+  int rc = FA_OK;
+  for (int i = 0; i < 2 && rc == FA_OK; ++i) {
+    k[i] = dev(hk[i].size()); v[i] = dev(hv[i].size()); dk[i] = dev(hk[i].size()); dv[i] = dev(hv[i].size());
+    oi[i] = dev(hq.size()); li[i] = dev(b * nq * les); mi[i] = dev(b * nq * es); dqi[i] = dev(hq.size());
+    HIP_OK(hipMemcpy(k[i], hk[i].data(), hk[i].size(), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(v[i], hv[i].data(), hv[i].size(), hipMemcpyHostToDevice));
+    const size_t fwsb = fa_forward_workspace_bytes(&ps[i]);
+    rc = fa_forward_ws(nullptr, &ps[i], q.p, k[i], v[i], oi[i], li[i], mi[i], dev(fwsb), fwsb);
+  }
+  if (rc == FA_OK) rc = fa_merge_partials(nullptr, dt, b, nq, d, 2, oi, li, mi, o.p, l.p, m.p);
+  for (int i = 0; i < 2 && rc == FA_OK; ++i) {
+    const size_t wsb = fa_backward_split_workspace_bytes(&ps[i]);
+    rc = fa_backward_split(nullptr, &ps[i], q.p, k[i], v[i], o.p, l.p, m.p, g.p, dqi[i], dk[i], dv[i], dev(wsb), wsb);
+  }
+  if (rc == FA_OK) rc = fa_accumulate_parts(nullptr, dt, b * d * nq, 2, dqi, dq.p);
+  if (rc != FA_OK) { fprintf(stderr, "combined case failed: %s\n", fa_last_error()); return 1; }
+  HIP_OK(hipDeviceSynchronize());
+
+  // ---- host: one dense softmax over the concatenated keys
+  const int nk = nks[0] + nks[1];
+  std::vector<uint8_t> mask0((size_t)nq * nks[0]);
+  fa_rule_mask(&ps[0], mask0.data());
+  const double sc = 1.0 / std::sqrt((double)d);
+  std::vector<double> rO(b * d * nq, 0.0), rdQ(b * d * nq, 0.0), rdK[2], rdV[2];
+  for (int i = 0; i < 2; ++i) { rdK[i].assign(b * d * nks[i], 0.0); rdV[i].assign(b * d * nks[i], 0.0); }
+  auto kv = [&](const std::vector<double>* X, int64_t bi, int c, int j) {  // channel c of key j of the union
+    const int i = j < nks[0] ? 0 : 1, jj = i == 0 ? j : j - nks[0];
+    return X[i][bi * d * nks[i] + (size_t)c * nks[i] + jj];
+  };
+  std::vector<double> P(nk), dS(nk);
+  for (int64_t bi = 0; bi < b; ++bi)
+    for (int r = 0; r < nq; ++r) {
+      double mx = -INFINITY, lsum = 0, Di = 0;
+      for (int j = 0; j < nk; ++j) {
+        double s = 0;
+        for (int c = 0; c < d; ++c) s += Q[bi * d * nq + (size_t)c * nq + r] * kv(K, bi, c, j);
+        P[j] = (j >= nks[0] || mask0[(size_t)r * nks[0] + j]) ? s * sc : -INFINITY;
+        mx = std::max(mx, P[j]);
+      }
+      for (int j = 0; j < nk; ++j) { P[j] = std::exp(P[j] - mx); lsum += P[j]; }
+      for (int j = 0; j < nk; ++j) P[j] /= lsum;
+      for (int c = 0; c < d; ++c) {
+        double acc = 0;
+        for (int j = 0; j < nk; ++j) acc += P[j] * kv(V, bi, c, j);
+        rO[bi * d * nq + (size_t)c * nq + r] = acc;
+        Di += acc * G[bi * d * nq + (size_t)c * nq + r];
+      }
+      for (int j = 0; j < nk; ++j) {
+        double s = 0;
+        for (int c = 0; c < d; ++c) s += G[bi * d * nq + (size_t)c * nq + r] * kv(V, bi, c, j);
+        dS[j] = P[j] * (s - Di) * sc;
+        const int i = j < nks[0] ? 0 : 1, jj = i == 0 ? j : j - nks[0];
+        for (int c = 0; c < d; ++c) {
+          const size_t kc = bi * d * nks[i] + (size_t)c * nks[i] + jj, qc = bi * d * nq + (size_t)c * nq + r;
+          rdV[i][kc] += P[j] * G[qc];
+          rdK[i][kc] += dS[j] * Q[qc];
+          rdQ[qc] += dS[j] * kv(K, bi, c, j);
+        }
+      }
+    }
+  auto err_of = [&](void* p, size_t bytes, const std::vector<double>& ref) {
+    std::vector<unsigned char> got(bytes);
+    HIP_OK(hipMemcpy(got.data(), p, bytes, hipMemcpyDeviceToHost));
+    return max_rel_err(got, dt, ref);
+  };
+  const double tol = 2e-3;
+  const double e[6] = {err_of(o.p, hq.size(), rO), err_of(dq.p, hq.size(), rdQ),
+                       err_of(dk[0], hk[0].size(), rdK[0]), err_of(dv[0], hv[0].size(), rdV[0]),
+                       err_of(dk[1], hk[1].size(), rdK[1]), err_of(dv[1], hv[1].size(), rdV[1])};
+  bool ok = true;
+  for (double x : e) ok = ok && x <= tol;
+  printf("{\"check\": \"combined dtype=%d window=33 + 8 global keys d=%d\", \"err_O\": %.3e, \"err_dQ\": %.3e, "
+         "\"err_dK\": [%.3e, %.3e], \"err_dV\": [%.3e, %.3e], \"tol\": %.0e, \"ok\": %s}\n",
+         dt, d, e[0], e[1], e[2], e[4], e[3], e[5], tol, ok ? "true" : "false");
+  for (Dev* x : owned) delete x;
+  return ok ? 0 : 1;
+}
+
 int check() {
   struct Case { int dt, pol, sd, mode; int qs[2], ks[2]; int d, ws, ls, causal; };
   // every policy x dtype x seq_dims (the reference's registered op matrix,
@@ -192,6 +307,7 @@ int check() {
            c.dt, c.pol, c.sd, c.mode, c.d, (int)(fwsb > 0), (int)(bplan[0] > 0), e[0], e[1], e[2], e[3], tol,
            ok ? "true" : "false");
   }
+  failures += check_combined();
   return failures ? 1 : 0;
 }
 
