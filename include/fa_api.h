@@ -109,6 +109,44 @@ int fa_forward_ws(void* stream, const fa_problem* p,
                   void* workspace, size_t workspace_bytes);
 int fa_forward_split_plan(const fa_problem* p, int32_t out[4]);
 
+/* Grouped-query forward (GQA; MQA when every head shares one K/V head): kv_group = g query slices share one
+ * K/V slice.  p->b counts Q slices and must be a multiple of kv_group, else FA_ERR_INVALID_ARGUMENT with text
+ * in fa_last_error(); K and V hold b / kv_group slices, Q / O / l / m hold b.  Q slice bi attends K/V slice
+ * bi / kv_group (the repeat_interleave convention), and its (O, l, m) is what fa_forward gives for that slice
+ * against that K/V slice, to rounding.  fa_problem is unchanged.
+ *
+ * The fused path folds the g heads of a group into the 128 query rows of one workgroup, at a row pitch P =
+ * the smallest power of two >= nq: row rho of the block is query rho % P of head rho / P.  K and V stream once
+ * per group instead of once per head.  One workgroup per (K/V slice, key chunk) writes fp32 partials of its
+ * live rows, and a merge kernel folds a row's chunks in chunk order (no atomics: deterministic).  The
+ * partial-plus-merge pair is the only grouped path, also for a short key range (one chunk).
+ *
+ * Envelope: fp16, max(d, v_d) <= 128, kv_group >= 2, nq >= 1, nk >= 1, kv_group * P <= 128.
+ * Chunks: fa_forward_split_plan's formula — the first chunk starts at the key tile (64 keys) that holds kb,
+ *   chunks hold max(min_chunk, ceil(ceil(span / 64) / 64) * 64) keys, span = ke - floor(kb / 64) * 64, at most
+ *   64 chunks — with min_chunk = 512 for kv_group * P <= 64 and 1024 above.  There is no 2048-key minimum: a
+ *   short range gives one or a few chunks, at least 1.
+ *
+ * fa_forward_grouped_plan (host-only, a pure function of the problem WITHOUT b, like fa_forward_split_plan):
+ *   out[0] = key chunks, 0 outside the envelope; out[1] = keys per chunk; out[2..3] = key range [kb, ke) of
+ *   the query block [0, nq-1]; out[4] = row pitch P; out[5] = folded rows kv_group * P.
+ * fa_forward_grouped_workspace_bytes (host-only): b / kv_group * chunks * kv_group * P * (v_d + 3) floats,
+ *   rounded up to 256 bytes; 0 outside the envelope; with kv_group == 1, fa_forward_workspace_bytes(p).
+ * fa_forward_grouped: kv_group == 1 is exactly fa_forward_ws (and the plan reports 0 chunks).  Outside the
+ *   envelope it returns FA_ERR_UNSUPPORTED with nothing written: the caller expands K and V and calls
+ *   fa_forward_ws (the Python layer does).  A workspace smaller than fa_forward_grouped_workspace_bytes():
+ *   FA_ERR_WORKSPACE_TOO_SMALL and nothing written.  No host synchronisation: safe under hipGraph capture,
+ *   like the other entry points.
+ * A Q slice's bits are NOT those of fa_forward_ws on expanded K/V: the online softmax moves its reference
+ * lazily and takes that decision per wave, so a row's arithmetic depends on which rows share its wave.  The
+ * result is deterministic, and a group's bits do not depend on b. */
+int fa_forward_grouped_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]);
+size_t fa_forward_grouped_workspace_bytes(const fa_problem* p, int32_t kv_group);
+int fa_forward_grouped(void* stream, const fa_problem* p, int32_t kv_group,
+                       const void* Q, const void* K, const void* V,
+                       void* O, void* l, void* m,
+                       void* workspace, size_t workspace_bytes);
+
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);

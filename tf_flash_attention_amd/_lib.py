@@ -33,6 +33,9 @@ EXPORTED_SYMBOLS = (
     "fa_forward_workspace_bytes",
     "fa_forward_ws",
     "fa_forward_split_plan",
+    "fa_forward_grouped_plan",
+    "fa_forward_grouped_workspace_bytes",
+    "fa_forward_grouped",
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_backward_split_plan",
@@ -125,6 +128,14 @@ def _declare(lib):
         lib.fa_merge_partials.restype = ctypes.c_int
         lib.fa_accumulate_parts.argtypes = [vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, pp, vp]
         lib.fa_accumulate_parts.restype = ctypes.c_int
+    # (absent from a library built before the grouped-query forward, as above)
+    if hasattr(lib, "fa_forward_grouped"):
+        lib.fa_forward_grouped_plan.argtypes = [P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
+        lib.fa_forward_grouped_plan.restype = ctypes.c_int
+        lib.fa_forward_grouped_workspace_bytes.argtypes = [P, ctypes.c_int32]
+        lib.fa_forward_grouped_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_forward_grouped.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
+        lib.fa_forward_grouped.restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

@@ -216,6 +216,57 @@ size_t split_ws_bytes(const fa_problem* p, const SplitPlan& s) {
   return align_up((size_t)p->b * (size_t)s.nchunks * nq * (size_t)(p->v_d + 3) * sizeof(float));
 }
 
+// Grouped-query routing of the fp16 forward: kv_group query slices share a K/V slice and
+// are folded into the 128 rows of one workgroup at a row pitch of the next power of two >= nq.  A pure
+// function of the problem WITHOUT b.  The chunks follow split_plan's formula, but there is no minimum
+// range: the partial + merge pair is the only grouped path, so a short range is one chunk.
+constexpr int32_t kGroupMaxRows = 128;     // the folded rows of one workgroup
+
+struct GroupedPlan {
+  int32_t nchunks, chunk, kb, ke, k_first, pitch, rows;
+};
+
+GroupedPlan grouped_plan(const fa_problem* p, int32_t kv_group) {
+  GroupedPlan s = {0, 0, 0, 0, 0, 0, 0};
+  if (fa_validate(p) != FA_OK || kv_group < 1) return s;
+  const int64_t nq = seq_elems(p->q_seq, p->seq_dims);
+  if (nq >= 1) {  // (validated: nq <= 2^30)
+    s.pitch = next_pow2((int32_t)nq);
+    s.rows = (int64_t)kv_group * s.pitch <= 0x7fffffff ? kv_group * s.pitch : 0x7fffffff;
+  }
+  fa::Rule r;
+  build_rule(p, &r);
+  if (nq >= 1 && r.k.n >= 1) fa::k_range_for_q_block(r, 0, (int32_t)nq - 1, &s.kb, &s.ke);
+  if (p->dtype != FA_F16 || p->d > 128 || p->v_d > 128 || kv_group < 2) return s;
+  if (s.pitch == 0 || r.k.n < 1 || (int64_t)kv_group * s.pitch > kGroupMaxRows) return s;
+#ifdef FA_DIAG
+  // a pinned forward variant keeps measuring the kernel it names
+  if (fa::diag_variant("FA_FWD_VARIANT") >= 0) return s;
+#endif
+  s.k_first = s.kb / kSplitTile * kSplitTile;
+  const int32_t span = s.ke - s.k_first;
+  const int32_t min_chunk = s.rows <= 64 ? 512 : 1024;
+  const int32_t capped = ((span + kSplitMaxChunks - 1) / kSplitMaxChunks + kSplitTile - 1) / kSplitTile * kSplitTile;
+  s.chunk = capped > min_chunk ? capped : min_chunk;
+  s.nchunks = (span + s.chunk - 1) / s.chunk;
+  if (s.nchunks < 1) s.nchunks = 1;  // an empty range: one chunk without tiles, so the merge writes the empty rows
+  return s;
+}
+
+size_t grouped_ws_bytes(const fa_problem* p, int32_t kv_group, const GroupedPlan& s) {
+  return align_up((size_t)(p->b / kv_group) * (size_t)s.nchunks * (size_t)s.rows * (size_t)(p->v_d + 3) * sizeof(float));
+}
+
+int check_group(const fa_problem* p, int32_t kv_group) {
+  const int st = fa_validate(p);
+  if (st != FA_OK) return st;
+  if (kv_group < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "kv_group must be >= 1");
+  if (p->b % kv_group != 0)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "the batch size b = " + std::to_string(p->b) +
+                                                  " is not a multiple of kv_group = " + std::to_string(kv_group));
+  return FA_OK;
+}
+
 // Split-key routing of the fp16 backward's dQ pass: the forward's plan, where the
 // dQ kernel's 32-bit buffer offsets reach a slice's K / V channel rows (the b-free part of
 // bwd_f16_fast_supported).  Also a pure function of the problem WITHOUT b, and a subset of the
@@ -413,6 +464,70 @@ int fa_forward_ws(void* stream, const fa_problem* p, const void* Q, const void* 
     a.m = static_cast<uint16_t*>(m) + b0 * nq;
     sa.ws = static_cast<float*>(workspace) + b0 * sp.nchunks * (p->v_d + 3) * nq;
     const hipError_t e = fa::launch_fwd_f16_splitk(sa, s);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
+int fa_forward_grouped_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]) {
+  const int st = check_group(p, kv_group);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const GroupedPlan s = grouped_plan(p, kv_group);
+  out[0] = s.nchunks;
+  out[1] = s.chunk;
+  out[2] = s.kb;
+  out[3] = s.ke;
+  out[4] = s.pitch;
+  out[5] = s.rows;
+  return FA_OK;
+}
+
+size_t fa_forward_grouped_workspace_bytes(const fa_problem* p, int32_t kv_group) {
+  if (check_group(p, kv_group) != FA_OK) return 0;
+  if (kv_group == 1) return fa_forward_workspace_bytes(p);
+  const GroupedPlan s = grouped_plan(p, kv_group);
+  return s.nchunks ? grouped_ws_bytes(p, kv_group, s) : 0;
+}
+
+int fa_forward_grouped(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
+                       void* O, void* l, void* m, void* workspace, size_t workspace_bytes) {
+  const int st = check_group(p, kv_group);
+  if (st != FA_OK) return st;
+  if (kv_group == 1) return fa_forward_ws(stream, p, Q, K, V, O, l, m, workspace, workspace_bytes);
+  const GroupedPlan gp = grouped_plan(p, kv_group);
+  if (gp.nchunks == 0)
+    return set_error(FA_ERR_UNSUPPORTED,
+                     "grouped forward: outside the fused envelope (fp16, max(d, v_d) <= 128, kv_group * pitch <= 128, "
+                     "nq >= 1, nk >= 1); expand K and V and call fa_forward_ws");
+  if (!workspace || workspace_bytes < grouped_ws_bytes(p, kv_group, gp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
+                     "forward workspace is smaller than fa_forward_grouped_workspace_bytes()");
+  FA_DIAG_COUNT(0);
+  if (p->b == 0) return FA_OK;
+  fa::GqaArgs ga;
+  fa::SplitArgs& sa = ga.s;
+  fa::FwdArgs& a = sa.f;
+  a.d = p->d; a.v_d = p->v_d;
+  a.scale = 1.0 / sqrt((double)p->d);
+  build_rule(p, &a.rule);
+  sa.nchunks = gp.nchunks; sa.chunk = gp.chunk; sa.k_first = gp.k_first; sa.k_end = gp.ke;
+  ga.g = kv_group; ga.pitch = gp.pitch; ga.log2_pitch = ilog2(gp.pitch);
+  const int64_t nq = a.rule.q.n, nk = a.rule.k.n, bkv = p->b / kv_group;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // one launch pair covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
+  const int64_t bmax = fa::fwd_f16_gqa_max_batch(ga);
+  for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {  // b0 counts K/V slices
+    a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
+    a.Q = static_cast<const uint16_t*>(Q) + b0 * kv_group * p->d * nq;
+    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
+    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
+    a.O = static_cast<uint16_t*>(O) + b0 * kv_group * p->v_d * nq;
+    a.l = static_cast<float*>(l) + b0 * kv_group * nq;
+    a.m = static_cast<uint16_t*>(m) + b0 * kv_group * nq;
+    sa.ws = static_cast<float*>(workspace) + b0 * gp.nchunks * (p->v_d + 3) * gp.rows;
+    const hipError_t e = fa::launch_fwd_f16_gqa(ga, s);
     if (e != hipSuccess)
       return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
   }
@@ -750,7 +865,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
 }
 
 }  // extern "C"

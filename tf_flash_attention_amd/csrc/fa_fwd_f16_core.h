@@ -3,12 +3,14 @@
 // fwd_f16_core runs one workgroup's share of a (batch, head) slice: 32*NW query rows from q0
 // against the key tiles [kt0, kt0 + 64*ntiles), from the prologue loads through the last
 // ring step, and hands back each wave's unnormalised accumulator and softmax statistics
-// (WaveState).  Two
+// (WaveState).  Three
 // kernels wrap it and differ only in which block gets which rows and keys and in the epilogue:
 //   * fwd_f16_kernel (fa_fwd_f16.hip): block -> (slice, query block), the rule-bounded key
 //     range of that block, normalises and writes O, l, m;
 //   * splitk_partial_kernel (fa_fwd_f16_splitk.hip): block -> (slice, key chunk) of the single
-//     query block, writes the partial and its statistics to the workspace.
+//     query block, writes the partial and its statistics to the workspace;
+//   * gqa_partial_kernel (fa_fwd_f16_gqa.hip): block -> (K/V slice, key chunk) with the query heads that
+//     share the K/V slice folded into the block's rows (FoldedRows below), the same partial format.
 // The structure:
 //   * Sᵀ = Kᵀ·Q and Oᵀ = V·Pᵀ on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
 //     Computing the TRANSPOSED scores puts the key index in the MFMA rows, so
@@ -81,6 +83,38 @@ struct WaveRegs {
   floatx16 stA[2], stB[2], negm;                                  // scores of two tiles in flight; -m_run
 };
 
+// Row maps: which query each of the workgroup's 32*NW rows is.
+//   IdentityRows: row rho of the block at q0 is query q0 + rho of slice `bi`, which is also the K/V slice
+//     (every ungrouped kernel).
+//   FoldedRows (grouped-query attention, fa_fwd_f16_gqa.hip): the `g` query slices bkv*g .. bkv*g + g-1
+//     that share K/V slice `bkv` are folded into the rows of ONE block (q0 = 0): row rho is query
+//     i = rho % pitch of head j = rho / pitch, pitch the smallest power of two >= nq (g * pitch <= 32*NW).
+//     A row is live iff j < g and i < nq; the other rows stage zeros and are never written out.  A
+//     pitch <= 32 divides the wave's 32 rows, so a wave holds whole heads and its rule bounds are those of
+//     the queries [0, nq-1]; a larger pitch gives a wave a contiguous run of one head's queries.
+// The core asks the map, in the order of the ungrouped code: the first Q slice and the K/V slice; wave w's
+// first query; whether the wave holds a live row; lane r's query; its row of the block.
+struct IdentityRows {
+  static constexpr bool kFolded = false;
+  __device__ __forceinline__ int64_t q_slice(int64_t bi, int64_t) const { return bi; }
+  __device__ __forceinline__ int64_t kv_slice(int64_t bi, int64_t) const { return bi; }
+  __device__ __forceinline__ int wave_q0(int q0, int w) const { return q0 + 32 * w; }
+  __device__ __forceinline__ bool wave_active(int wq0, int, int nq) const { return wq0 < nq; }
+  __device__ __forceinline__ int lane_q(int wq0, int, int r) const { return wq0 + r; }
+  __device__ __forceinline__ int lane_row(int qi, int, int) const { return qi; }
+};
+struct FoldedRows {
+  static constexpr bool kFolded = true;
+  int32_t g, pitch, log2_pitch;
+  __device__ __forceinline__ int64_t q_slice(int64_t, int64_t bkv) const { return bkv * g; }
+  __device__ __forceinline__ int64_t kv_slice(int64_t, int64_t bkv) const { return bkv; }
+  // 0 for a pitch <= 32: the wave holds whole heads, so its queries are [0, nq-1]
+  __device__ __forceinline__ int wave_q0(int, int w) const { return (32 * w) & (pitch - 1); }
+  __device__ __forceinline__ bool wave_active(int wq0, int w, int nq) const { return 32 * w < g * pitch && wq0 < nq; }
+  __device__ __forceinline__ int lane_q(int, int w, int r) const { return (32 * w + r) & (pitch - 1); }
+  __device__ __forceinline__ int lane_row(int, int w, int r) const { return 32 * w + r; }
+};
+
 // What a wave holds after its last key tile.  acc_o and the row sum are relative to m_run, the
 // lazily updated softmax reference (log2 units; meaningful once m_set); m_max is the exact row max.
 // The row sum is l_run in each half-wave (add lane l^32), or with kFMfmaSum every element of acc_l.
@@ -90,8 +124,9 @@ struct WaveState {
   floatx16 acc_l;    // kFMfmaSum: the running row sum in every register (rows are identical)
   float m_run, l_run, m_max;
   bool m_set;
-  bool wave_active;  // the wave's first query row wq0 < nq
-  int qi, h;         // this lane's query row; its half-wave (channel v = 32u + (i&3) + 8(i>>2) + 4h)
+  bool wave_active;  // the wave's first query row wq0 < nq (FoldedRows: the wave holds a live row)
+  int qi, h;         // this lane's query row (FoldedRows: its row rho of the block); its half-wave
+                     // (channel v = 32u + (i&3) + 8(i>>2) + 4h)
 };
 
 // One workgroup = NW waves = 32*NW query rows [q0, q0 + 32*NW) of slice `bi`, against the key
@@ -105,6 +140,8 @@ struct WaveState {
 //   Tiles with no allowed pair for a wave are skipped by that wave (no MFMAs).
 //   FAST d == v_d == D and K/V rows 16-byte aligned (nk % 8 == 0): unguarded
 //        dwordx4 staging.
+//   Map  the row map above; with FoldedRows `bi` is unused, `bkv` is the K/V slice and the queries are
+//        those of slices bkv*g + j.  With IdentityRows `bkv` is unused: slice `bi` serves Q, K and V.
 // All waves stage K/V whatever nq is; waves whose 32 query rows lie past nq run no MFMA.
 // Scores are produced directly as exp2 arguments: Q is pre-scaled by
 // scale*log2(e) once (fp16), and the running max enters each Sᵀ MFMA chain as
@@ -114,9 +151,12 @@ struct WaveState {
 // the matrix pipe, and the PV MFMAs of tile j follow (cdna_hip_programming.md
 // T15); the K/V tile j+2 is written to LDS after the barrier and tile j+3 is
 // loaded into registers (T14).
-template <int D, int NW, int POL, bool FAST, int F>
+template <int D, int NW, int POL, bool FAST, int F, class Map = IdentityRows>
 __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem, int64_t bi, int q0, int kt0, int ntiles,
-                                             WaveRegs<D, NW>& rg, WaveState<D>& ws) {
+                                             WaveRegs<D, NW>& rg, WaveState<D>& ws, Map map = Map{},
+                                             int64_t bkv = 0) {
+  // (the map travels by value: a reference to the default argument's temporary changed the register
+  // allocation of the ungrouped kernels, profiles/gqa_core_asm_equal.txt)
   using S = Smem<D, NW>;
   constexpr int kThr = NW * 64;
   constexpr int kBM = S::kBM;
@@ -131,9 +171,9 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   const int h = lane >> 5, r = lane & 31;
   const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;  // tr-read lane roles
 
-  const __half* Q = static_cast<const __half*>(a.Q) + bi * (int64_t)d * nq;
-  const __half* K = static_cast<const __half*>(a.K) + bi * (int64_t)d * nk;
-  const __half* V = static_cast<const __half*>(a.V) + bi * (int64_t)vd * nk;
+  const __half* Q = static_cast<const __half*>(a.Q) + map.q_slice(bi, bkv) * (int64_t)d * nq;
+  const __half* K = static_cast<const __half*>(a.K) + map.kv_slice(bi, bkv) * (int64_t)d * nk;
+  const __half* V = static_cast<const __half*>(a.V) + map.kv_slice(bi, bkv) * (int64_t)vd * nk;
   const bool qvec = ((nq & 7) == 0) && ((reinterpret_cast<uintptr_t>(a.Q) & 15) == 0);
   const float c2 = (float)a.scale * kLog2e;
 
@@ -180,7 +220,20 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   for (int idx = tid; idx < D * (kBM / 8); idx += kThr) {
     const int c = idx / (kBM / 8), m = idx % (kBM / 8);
     u32x4 v = {0, 0, 0, 0};
-    if (c < d) v = load_chunk8(Q + (int64_t)c * nq, q0 + 8 * m, nq, qvec);
+    if constexpr (Map::kFolded) {
+      // column rho = 8m + e is query i of head j; below pitch 8 a chunk spans heads, so every element is
+      // a guarded load of its own (the tile is loaded once per workgroup, beside >= 128 KB of K/V)
+      uint32_t hh[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int rho = 8 * m + e, j = rho >> map.log2_pitch, i = rho & (map.pitch - 1);
+        const bool live = c < d && j < map.g && i < nq;
+        hh[e] = live ? (uint32_t)__half_as_ushort(Q[((int64_t)j * d + c) * nq + i]) : 0u;
+      }
+      v = u32x4{hh[0] | (hh[1] << 16), hh[2] | (hh[3] << 16), hh[4] | (hh[5] << 16), hh[6] | (hh[7] << 16)};
+    } else if (c < d) {
+      v = load_chunk8(Q + (int64_t)c * nq, q0 + 8 * m, nq, qvec);
+    }
     *reinterpret_cast<lds_u32x4_t*>(smem + c * S::kQRow + ((m * 16) ^ ((c & 3) << 6))) = v;
   }
   __syncthreads();
@@ -200,11 +253,12 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   }
   __syncthreads();  // the Q region is reused by the K/V ring
 
-  const int wq0 = q0 + 32 * w;
+  const int wq0 = map.wave_q0(q0, w);
   const int wq1 = min(wq0 + 31, nq - 1);
-  const bool wave_active = wq0 < nq;
-  const int qi = wq0 + r;
-  const int qo = (POL == 2 && qi < nq) ? seq_order(a.rule.q, a.rule, qi) : 0;
+  const bool wave_active = map.wave_active(wq0, w, nq);
+  const int qi = map.lane_q(wq0, w, r);
+  // (a folded block's padding rows take the rule state of query nq-1, here and in key_interval below)
+  const int qo = (POL == 2 && (Map::kFolded || qi < nq)) ? seq_order(a.rule.q, a.rule, Map::kFolded ? min(qi, nq - 1) : qi) : 0;
   // POL 1 (interval rules): this lane's allowed keys [klo, klo + kspan) and the wave's
   // bounds on them (both ends are non-decreasing in the query, so lanes 0 / last bound them)
   int klo = 0, kspan = 0, wlo_min = 0, wlo_max = 0, whi_min = 0, whi_max = 0;
@@ -235,7 +289,7 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   auto store_tile = [&](int buf) { store_from(kreg, vreg, buf); };
 
   ws.wave_active = wave_active;
-  ws.qi = qi;
+  ws.qi = map.lane_row(qi, w, r);
   ws.h = h;
 #pragma unroll
   for (int u = 0; u < D / 32; ++u)

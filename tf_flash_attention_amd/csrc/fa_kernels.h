@@ -53,6 +53,15 @@ struct SplitArgs {
   int32_t k_end;    // one past the range's last key
 };
 
+// grouped-query fp16 forward (fa_fwd_f16_gqa.hip): `g` query slices share one K/V slice and are folded into
+// the 128 rows of one workgroup.  s.f.b counts K/V slices; Q, O, l and m hold s.f.b * g slices.
+struct GqaArgs {
+  SplitArgs s;         // s.ws: [b_kv][nchunks][v_d + 3][g * pitch] floats; nchunks >= 1
+  int32_t g;           // query slices per K/V slice, >= 2
+  int32_t pitch;       // rows per head: the smallest power of two >= nq; g * pitch <= 128
+  int32_t log2_pitch;
+};
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;
@@ -143,6 +152,11 @@ hipError_t launch_fwd_f16_band(const FwdArgs& a, hipStream_t s);
 // fwd_f16_splitk_max_batch() slices per call (grid limits).
 int64_t fwd_f16_splitk_max_batch(const SplitArgs& sa);
 hipError_t launch_fwd_f16_splitk(const SplitArgs& sa, hipStream_t s);
+// grouped-query fp16 forward for few queries: one workgroup per (K/V slice, key chunk) runs the same key
+// loop over the group's folded query rows, and a merge kernel writes each query slice's O, l, m —
+// fa_fwd_f16_gqa.hip.  At most fwd_f16_gqa_max_batch() K/V slices per call (grid limits).
+int64_t fwd_f16_gqa_max_batch(const GqaArgs& ga);
+hipError_t launch_fwd_f16_gqa(const GqaArgs& ga, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

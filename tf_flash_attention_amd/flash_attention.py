@@ -15,6 +15,14 @@ rule (a window plus global tokens, self-attention plus a prompt, key shards), wi
     combined_2d(Q, parts, returning_l_m=False)
     merge_partials(Os, ls, ms, seq_dims=1) -> (O, l, m)      (op level, no autograd)
 
+and grouped-query attention (GQA / MQA), where ``Hq = g * Hk`` query heads share the K/V heads (the last
+batch axis; query head ``h`` attends K/V head ``h // g``), with gradients::
+
+    grouped_1d(Q, K, V, policy='full', sync_mode='none_front', window_size=1, log2_stride_size=0,
+               is_causal=False, returning_l_m=False)
+    grouped_2d(...)
+    attention_forward_grouped(policy, seq_dims, Q, K, V, sync_mode, ...) -> (O, l, m)   (op level)
+
 Tensors are ``torch`` tensors on a ROCm device in the reference's channel-first
 layout ``batch_shape + (C, *seq_shape)``.  Each call returns ``O`` or
 ``(O, l, m)``; autograd flows through ``O`` only (gradients of ``l``/``m`` are
@@ -33,6 +41,7 @@ on the current HIP stream.  There is no CPU / eager fallback.
 
 from __future__ import annotations
 
+import ctypes
 import re
 from types import SimpleNamespace
 
@@ -44,6 +53,7 @@ __all__ = [
     "full_1d", "causal_1d", "local_1d", "full_2d", "causal_2d", "local_2d",
     "InvalidArgumentError", "InternalError", "estimate_forward_flops",
     "Part", "combined_1d", "combined_2d", "merge_partials",
+    "grouped_1d", "grouped_2d", "attention_forward_grouped",
 ]
 
 
@@ -477,6 +487,149 @@ def combined_1d(Q, parts, returning_l_m=False):
 def combined_2d(Q, parts, returning_l_m=False):
     """:func:`combined_1d` for 2d sequences."""
     return _combined(2, Q, parts, returning_l_m)
+
+
+# ----------------------------------------------------------------------------
+# Grouped-query attention: g = Hq / Hk query heads share one K/V head
+# (include/fa_api.h, "Grouped-query forward"; DESIGN.md §3.8)
+# ----------------------------------------------------------------------------
+def verify_grouped_shapes(seq_dims, Q_shape, K_shape, V_shape):
+    """The checks of verify_and_extract_shapes, with the batch shapes allowed to differ in their last axis
+    (the heads): Q ``batch + (Hq, C, *Nq)``, K ``batch + (Hk, C, *Nk)``, V ``batch + (Hk, Cv, *Nk)``,
+    Hq = g * Hk.  Returns (Q batch shape, Q seq shape, C, K/V batch shape, K seq shape, Cv, g)."""
+    Q_shape, K_shape, V_shape = tuple(Q_shape), tuple(K_shape), tuple(V_shape)
+    if not (len(Q_shape) == len(K_shape) == len(V_shape)):
+        raise InvalidArgumentError("The number of dimensions of Q, K, and V should be equal")
+    if len(Q_shape) < seq_dims + 2:
+        raise InvalidArgumentError(f"The number of dimensions of Q, K, and V should be >= {seq_dims + 2}")
+    ch = len(Q_shape) - seq_dims - 1
+    Qb, Kb, Vb = Q_shape[:ch], K_shape[:ch], V_shape[:ch]
+    Qs, Ks, Vs = Q_shape[ch + 1:], K_shape[ch + 1:], V_shape[ch + 1:]
+    if Q_shape[ch] != K_shape[ch]:
+        raise InvalidArgumentError("The channel dimension of Q and K should be equal")
+    if Kb != Vb or Qb[:-1] != Kb[:-1]:
+        raise InvalidArgumentError(
+            "The batch shapes of K and V should be equal, and equal to the one of Q except in its last axis, "
+            "but Q_batch_shape = " + _shape_str(Qb) + ", K_batch_shape = " + _shape_str(Kb) + ", V_batch_shape = "
+            + _shape_str(Vb) + " were received")
+    if Ks != Vs:
+        raise InvalidArgumentError(
+            "The sequence shape of K and V are expected to be equal, but K_seq_shape = " + _shape_str(Ks)
+            + ", V_seq_shape = " + _shape_str(Vs) + " are detected")
+    g = 1
+    if ch > 0 and Qb[-1] != Kb[-1]:
+        if Kb[-1] < 1 or Qb[-1] % Kb[-1] != 0:
+            raise InvalidArgumentError(
+                "The last batch axis of Q should be a multiple of the one of K and V, but Q_batch_shape = "
+                + _shape_str(Qb) + ", K_batch_shape = " + _shape_str(Kb) + " were received")
+        g = int(Qb[-1]) // int(Kb[-1])
+    return Qb, Qs, Q_shape[ch], Kb, Ks, V_shape[ch], g
+
+
+def _expand_groups(t, ch, g):
+    """K or V with every head repeated g times along the last batch axis (repeat_interleave)."""
+    return t if g == 1 else t.repeat_interleave(g, dim=ch - 1)
+
+
+def attention_forward_grouped(policy: str, seq_dims: int, Q, K, V, sync_mode, window_size=1, log2_stride_size=0,
+                              is_causal=False):
+    """Op-level grouped forward: Q slice (..., h) attends K/V slice (..., h // g); returns (O, l, m) with Q's
+    batch shape.  Inside the fused envelope (``fa_forward_grouped_plan`` reports chunks) K and V stream once
+    per group; everywhere else K and V are expanded and ``attention_forward`` runs, so every dtype, rule,
+    channel count and split plan works."""
+    sid = _sync_mode_id(sync_mode)
+    Qb, Qs, Q_ch, Kb, Ks, V_ch, g = verify_grouped_shapes(seq_dims, Q.shape, K.shape, V.shape)
+    ch = len(Qb)
+    if g == 1:
+        return attention_forward(policy, seq_dims, Q, K, V, sync_mode, window_size, log2_stride_size, is_causal)
+    dt = _dtype_id(Q, Q.dtype == torch.float16)
+    if K.dtype != Q.dtype or V.dtype != Q.dtype:
+        raise TypeError("Q, K and V must share one dtype")
+    _check_device_tensors(Q, K, V)
+    prob = _lib.make_problem(dt, _POLICIES[policy], seq_dims, sid, _prod(Qb), Qs, Ks, Q_ch, V_ch,
+                             window_size, log2_stride_size, is_causal)
+    L = _lib.lib()
+    plan = (ctypes.c_int32 * 6)()
+    st = L.fa_forward_grouped_plan(prob, g, plan)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    if plan[0] == 0:  # outside the fused envelope
+        return attention_forward(policy, seq_dims, Q, _expand_groups(K, ch, g), _expand_groups(V, ch, g), sync_mode,
+                                 window_size, log2_stride_size, is_causal)
+    Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
+    O = torch.empty(Qb + (V_ch,) + Qs, dtype=Q.dtype, device=Q.device)
+    l = torch.empty(Qb + Qs, dtype=torch.float32, device=Q.device)
+    m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
+    ws_bytes = int(L.fa_forward_grouped_workspace_bytes(prob, g))
+    with torch.cuda.device(Q.device):
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
+        st = L.fa_forward_grouped(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                  O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    return O, l, m
+
+
+class _GroupedFn(torch.autograd.Function):
+    """Grouped forward + its gradient.  The backward always runs the ungrouped backward op on expanded K and V
+    with the saved (O, l, m) — also after a fused forward: the op reads only the tensors it is given — and
+    sums dK and dV over each group in fp32 (fp64 for double) with one rounding.  (There is no grouped
+    backward kernel: the fused envelope is decode, which has no backward.)"""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, policy, seq_dims, sync_mode, window_size, log2_stride_size, is_causal):
+        O, l, m = attention_forward_grouped(policy, seq_dims, Q, K, V, sync_mode, window_size, log2_stride_size,
+                                            is_causal)
+        ctx.save_for_backward(Q, K, V, O, l, m)
+        ctx.attrs = (policy, seq_dims, sync_mode, window_size, log2_stride_size, is_causal)
+        ctx.mark_non_differentiable(l, m)
+        return O, l, m
+
+    @staticmethod
+    def backward(ctx, dO, dl, dm):
+        Q, K, V, O, l, m = ctx.saved_tensors
+        policy, seq_dims, sync_mode, ws, ls, causal = ctx.attrs
+        if dO is None:
+            dO = torch.zeros_like(O)
+        ch = Q.dim() - seq_dims - 1
+        g = int(Q.shape[ch - 1]) // int(K.shape[ch - 1])
+        dQ, dKe, dVe = attention_backward(policy, seq_dims, Q, _expand_groups(K, ch, g), _expand_groups(V, ch, g),
+                                          O, l, m, dO, sync_mode, ws, ls, causal)
+        acc = torch.float64 if Q.dtype == torch.float64 else torch.float32
+
+        def fold(t, like):  # [..., Hk * g, C, N...] -> sum over g
+            s = tuple(like.shape)
+            return t.reshape(s[:ch] + (g,) + s[ch:]).sum(dim=ch, dtype=acc).to(like.dtype)
+
+        return dQ, fold(dKe, K), fold(dVe, V), None, None, None, None, None, None
+
+
+def _grouped(seq_dims, Q, K, V, policy, sync_mode, window_size, log2_stride_size, is_causal, returning_l_m):
+    if policy not in _POLICIES:
+        raise InvalidArgumentError(f"Unsupported policy: {policy}")
+    _sync_mode_id(sync_mode)
+    *_, g = verify_grouped_shapes(seq_dims, Q.shape, K.shape, V.shape)
+    if g == 1:  # bit for bit the ungrouped wrapper
+        return _attend(policy, seq_dims, Q, K, V, sync_mode, returning_l_m, window_size, log2_stride_size, is_causal)
+    results = _GroupedFn.apply(Q, K, V, policy, seq_dims, sync_mode, window_size, log2_stride_size, is_causal)
+    return results if returning_l_m else results[0]
+
+
+def grouped_1d(Q, K, V, policy="full", sync_mode="none_front", window_size=1, log2_stride_size=0, is_causal=False,
+               returning_l_m=False):
+    """Grouped-query attention on 1d sequences: Q ``batch + (Hq, C, Nq)``, K ``batch + (Hk, C, Nk)``, V ``batch +
+    (Hk, Cv, Nk)`` with Hq = g * Hk read from the shapes; query head h attends K/V head h // g (the
+    ``repeat_interleave`` convention), under ``policy`` in {"full", "causal", "local"} with the arguments of the
+    wrapper of that name.  fp16 problems with g * next_pow2(Nq) <= 128 and at most 128 channels stream K and V
+    once per group; every other problem runs on expanded K and V.  Gradients flow to Q, K and V; dK and dV are
+    the sums over each group's heads.  Returns ``O`` or ``(O, l, m)``."""
+    return _grouped(1, Q, K, V, policy, sync_mode, window_size, log2_stride_size, is_causal, returning_l_m)
+
+
+def grouped_2d(Q, K, V, policy="full", sync_mode="none_front", window_size=1, log2_stride_size=0, is_causal=False,
+               returning_l_m=False):
+    """:func:`grouped_1d` for 2d sequences."""
+    return _grouped(2, Q, K, V, policy, sync_mode, window_size, log2_stride_size, is_causal, returning_l_m)
 
 
 # ----------------------------------------------------------------------------
