@@ -147,6 +147,42 @@ int fa_forward_grouped(void* stream, const fa_problem* p, int32_t kv_group,
                        void* O, void* l, void* m,
                        void* workspace, size_t workspace_bytes);
 
+/* Ragged few-query forward (decode over a padded K/V cache): fa_forward_grouped's layout — Q / O / l / m hold
+ * p->b slices, K and V hold b / kv_group slices laid out for a CAPACITY nk = p->k_seq[0] — where K/V slice bkv
+ * holds only L = k_lens[bkv / kv_per_len] live keys.  k_lens is a DEVICE array of (b / kv_group) / kv_per_len
+ * int32 values (kv_per_len = the K/V heads of one sequence); the kernels clamp a value to [0, nk].  The host
+ * never reads k_lens: no host synchronisation, and the lengths may change between replays of a captured graph.
+ * Whatever K and V hold past L (NaN and Inf included) does not reach a result.
+ *
+ * For a slice of length L:
+ *   tail_causal == 0: the (O, l, m) fa_forward gives under FA_FULL against the first L keys, to rounding;
+ *   tail_causal != 0: the nq queries are the last nq positions of the sequence: query i sees keys
+ *     j <= L - nq + i (for nq == 1 this is the form above, bit for bit);
+ *   rows that see no key (L == 0; i < nq - L under the tail rule): O = 0, l = 0, every byte of m 0xFA.
+ *
+ * Envelope: fp16, seq_dims == 1, policy == FA_FULL, max(d, v_d) <= 128, kv_group >= 1 (ungrouped decode is
+ *   inside, unlike fa_forward_grouped), nq >= 1, nk >= 1, kv_group * P <= 128 with P the smallest power of two
+ *   >= nq.  A well-formed problem outside it: FA_ERR_UNSUPPORTED, nothing written.
+ * FA_ERR_INVALID_ARGUMENT with text in fa_last_error(): policy != FA_FULL, kv_group < 1, b % kv_group != 0,
+ *   kv_per_len < 1, kv_per_len not dividing b / kv_group, a null k_lens with b > 0.
+ *
+ * fa_forward_ragged_plan (host-only): fa_forward_grouped_plan's formula and out[6] layout over the key range
+ *   [0, nk), with kv_group == 1 planned.  A pure function of the problem WITHOUT b and without the lengths
+ *   (they are device data): a short sequence in a large cache launches the capacity's chunks, and those at or
+ *   past its length return at once.
+ * fa_forward_ragged_workspace_bytes (host-only): fa_forward_grouped_workspace_bytes's formula, b / kv_group *
+ *   chunks * kv_group * P * (v_d + 3) floats rounded up to 256 bytes; 0 outside the envelope.
+ * fa_forward_ragged: a smaller workspace returns FA_ERR_WORKSPACE_TOO_SMALL with nothing written; b == 0
+ *   returns FA_OK with nothing launched.  A slice's bits do not depend on b or on the other slices' lengths;
+ *   with every length equal to nk and kv_group >= 2 they are fa_forward_grouped's under FA_FULL. */
+int fa_forward_ragged_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]);
+size_t fa_forward_ragged_workspace_bytes(const fa_problem* p, int32_t kv_group);
+int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group,
+                      const void* Q, const void* K, const void* V,
+                      const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                      void* O, void* l, void* m,
+                      void* workspace, size_t workspace_bytes);
+
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);

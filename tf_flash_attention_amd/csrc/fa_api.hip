@@ -226,7 +226,7 @@ struct GroupedPlan {
   int32_t nchunks, chunk, kb, ke, k_first, pitch, rows;
 };
 
-GroupedPlan grouped_plan(const fa_problem* p, int32_t kv_group) {
+GroupedPlan grouped_plan(const fa_problem* p, int32_t kv_group, int32_t min_group = 2) {
   GroupedPlan s = {0, 0, 0, 0, 0, 0, 0};
   if (fa_validate(p) != FA_OK || kv_group < 1) return s;
   const int64_t nq = seq_elems(p->q_seq, p->seq_dims);
@@ -237,7 +237,7 @@ GroupedPlan grouped_plan(const fa_problem* p, int32_t kv_group) {
   fa::Rule r;
   build_rule(p, &r);
   if (nq >= 1 && r.k.n >= 1) fa::k_range_for_q_block(r, 0, (int32_t)nq - 1, &s.kb, &s.ke);
-  if (p->dtype != FA_F16 || p->d > 128 || p->v_d > 128 || kv_group < 2) return s;
+  if (p->dtype != FA_F16 || p->d > 128 || p->v_d > 128 || kv_group < min_group) return s;
   if (s.pitch == 0 || r.k.n < 1 || (int64_t)kv_group * s.pitch > kGroupMaxRows) return s;
 #ifdef FA_DIAG
   // a pinned forward variant keeps measuring the kernel it names
@@ -264,6 +264,23 @@ int check_group(const fa_problem* p, int32_t kv_group) {
   if (p->b % kv_group != 0)
     return set_error(FA_ERR_INVALID_ARGUMENT, "the batch size b = " + std::to_string(p->b) +
                                                   " is not a multiple of kv_group = " + std::to_string(kv_group));
+  return FA_OK;
+}
+
+// Ragged few-query forward: grouped_plan over the capacity [0, nk) of 1d sequences under the
+// full rule, with ungrouped decode (kv_group == 1) inside the envelope.  The lengths are device data, so the
+// plan cannot depend on them.
+GroupedPlan ragged_plan(const fa_problem* p, int32_t kv_group) {
+  GroupedPlan s = grouped_plan(p, kv_group, 1);
+  if (p->seq_dims != 1 || p->policy != FA_FULL) s.nchunks = s.chunk = 0;
+  return s;
+}
+
+int check_ragged(const fa_problem* p, int32_t kv_group) {
+  const int st = check_group(p, kv_group);
+  if (st != FA_OK) return st;
+  if (p->policy != FA_FULL)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "ragged forward: the policy must be FA_FULL (the lengths and tail_causal are the mask)");
   return FA_OK;
 }
 
@@ -528,6 +545,78 @@ int fa_forward_grouped(void* stream, const fa_problem* p, int32_t kv_group, cons
     a.m = static_cast<uint16_t*>(m) + b0 * kv_group * nq;
     sa.ws = static_cast<float*>(workspace) + b0 * gp.nchunks * (p->v_d + 3) * gp.rows;
     const hipError_t e = fa::launch_fwd_f16_gqa(ga, s);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
+int fa_forward_ragged_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]) {
+  const int st = check_ragged(p, kv_group);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const GroupedPlan s = ragged_plan(p, kv_group);
+  out[0] = s.nchunks;
+  out[1] = s.chunk;
+  out[2] = s.kb;
+  out[3] = s.ke;
+  out[4] = s.pitch;
+  out[5] = s.rows;
+  return FA_OK;
+}
+
+size_t fa_forward_ragged_workspace_bytes(const fa_problem* p, int32_t kv_group) {
+  if (check_ragged(p, kv_group) != FA_OK) return 0;
+  const GroupedPlan s = ragged_plan(p, kv_group);
+  return s.nchunks ? grouped_ws_bytes(p, kv_group, s) : 0;
+}
+
+int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
+                      const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m,
+                      void* workspace, size_t workspace_bytes) {
+  const int st = check_ragged(p, kv_group);
+  if (st != FA_OK) return st;
+  const int64_t bkv = p->b / kv_group;
+  if (kv_per_len < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "kv_per_len must be >= 1");
+  if (bkv % kv_per_len != 0)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "the number of K/V slices b / kv_group = " + std::to_string(bkv) +
+                                                  " is not a multiple of kv_per_len = " + std::to_string(kv_per_len));
+  const GroupedPlan gp = ragged_plan(p, kv_group);
+  if (gp.nchunks == 0)
+    return set_error(FA_ERR_UNSUPPORTED,
+                     "ragged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                     "kv_group * pitch <= 128, nq >= 1, nk >= 1)");
+  if (!workspace || workspace_bytes < grouped_ws_bytes(p, kv_group, gp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
+                     "forward workspace is smaller than fa_forward_ragged_workspace_bytes()");
+  FA_DIAG_COUNT(0);
+  if (p->b == 0) return FA_OK;
+  if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
+  fa::RaggedArgs ra;
+  fa::GqaArgs& ga = ra.g;
+  fa::SplitArgs& sa = ga.s;
+  fa::FwdArgs& a = sa.f;
+  a.d = p->d; a.v_d = p->v_d;
+  a.scale = 1.0 / sqrt((double)p->d);
+  build_rule(p, &a.rule);
+  sa.nchunks = gp.nchunks; sa.chunk = gp.chunk; sa.k_first = 0; sa.k_end = gp.ke;
+  ga.g = kv_group; ga.pitch = gp.pitch; ga.log2_pitch = ilog2(gp.pitch);
+  ra.k_lens = k_lens; ra.kv_per_len = kv_per_len; ra.tail_causal = tail_causal != 0;
+  const int64_t nq = a.rule.q.n, nk = a.rule.k.n;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // one launch pair covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
+  const int64_t bmax = fa::fwd_f16_gqa_max_batch(ga);
+  for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {  // b0 counts K/V slices
+    a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
+    a.Q = static_cast<const uint16_t*>(Q) + b0 * kv_group * p->d * nq;
+    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
+    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
+    a.O = static_cast<uint16_t*>(O) + b0 * kv_group * p->v_d * nq;
+    a.l = static_cast<float*>(l) + b0 * kv_group * nq;
+    a.m = static_cast<uint16_t*>(m) + b0 * kv_group * nq;
+    sa.ws = static_cast<float*>(workspace) + b0 * gp.nchunks * (p->v_d + 3) * gp.rows;
+    ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
+    const hipError_t e = fa::launch_fwd_f16_ragged(ra, s);
     if (e != hipSuccess)
       return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
   }
@@ -865,7 +954,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
 }
 
 }  // extern "C"

@@ -3,14 +3,16 @@
 // fwd_f16_core runs one workgroup's share of a (batch, head) slice: 32*NW query rows from q0
 // against the key tiles [kt0, kt0 + 64*ntiles), from the prologue loads through the last
 // ring step, and hands back each wave's unnormalised accumulator and softmax statistics
-// (WaveState).  Three
+// (WaveState).  Four
 // kernels wrap it and differ only in which block gets which rows and keys and in the epilogue:
 //   * fwd_f16_kernel (fa_fwd_f16.hip): block -> (slice, query block), the rule-bounded key
 //     range of that block, normalises and writes O, l, m;
 //   * splitk_partial_kernel (fa_fwd_f16_splitk.hip): block -> (slice, key chunk) of the single
 //     query block, writes the partial and its statistics to the workspace;
 //   * gqa_partial_kernel (fa_fwd_f16_gqa.hip): block -> (K/V slice, key chunk) with the query heads that
-//     share the K/V slice folded into the block's rows (FoldedRows below), the same partial format.
+//     share the K/V slice folded into the block's rows (FoldedRows below), the same partial format;
+//   * ragged_partial_kernel (fa_fwd_f16_ragged.hip): the same block with a per-slice key length read on
+//     the device (the row maps' key_limit / lane_interval below).
 // The structure:
 //   * Sᵀ = Kᵀ·Q and Oᵀ = V·Pᵀ on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
 //     Computing the TRANSPOSED scores puts the key index in the MFMA rows, so
@@ -70,6 +72,13 @@ constexpr int waves_per_eu(int D, int F) { return (D >= 128 || (F & kFOcc1)) ? 1
 
 __device__ __forceinline__ u32x4 load16(const __half* p) { return *reinterpret_cast<const u32x4*>(p); }
 
+// the first n of a chunk's 8 halfs, zeros behind them (integer masks: a NaN bit pattern is cleared like any other)
+__device__ __forceinline__ u32x4 keep_first(u32x4 v, int n) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] &= (2 * i < n ? 0xffffu : 0u) | (2 * i + 1 < n ? 0xffff0000u : 0u);
+  return v;
+}
+
 // The loop's register arrays.  The KERNEL declares them (and the WaveState below) and hands them
 // in: the compiler optimises fwd_f16_core as a function of its own before it inlines it, without
 // the kernel's launch bounds, and arrays that are locals of that function are then cut up under
@@ -94,8 +103,17 @@ struct WaveRegs {
 //     the queries [0, nq-1]; a larger pitch gives a wave a contiguous run of one head's queries.
 // The core asks the map, in the order of the ungrouped code: the first Q slice and the K/V slice; wave w's
 // first query; whether the wave holds a live row; lane r's query; its row of the block.
+// The map also says how many of a slice's keys are live and which of them a query may see: key_limit(nk)
+// bounds the staging guards, the whole-tile path, the tile class and the tail mask, while nk itself stays
+// the row stride of K and V; lane_interval is the POL 1 interval of query qi.  These two maps answer nk and
+// the rule's own interval.  A map with kRagged (fa_fwd_f16_ragged.hip) answers a per-slice length below nk,
+// and the core then zeroes staged K / V past it element by element: what lies there is not the caller's
+// data, and a NaN or Inf times P = 0 would poison the PV product.
 struct IdentityRows {
   static constexpr bool kFolded = false;
+  static constexpr bool kRagged = false;
+  __device__ __forceinline__ int key_limit(int nk) const { return nk; }
+  __device__ __forceinline__ void lane_interval(const Rule& r, int qi, int* klo, int* khi) const { key_interval(r, qi, klo, khi); }
   __device__ __forceinline__ int64_t q_slice(int64_t bi, int64_t) const { return bi; }
   __device__ __forceinline__ int64_t kv_slice(int64_t bi, int64_t) const { return bi; }
   __device__ __forceinline__ int wave_q0(int q0, int w) const { return q0 + 32 * w; }
@@ -105,6 +123,9 @@ struct IdentityRows {
 };
 struct FoldedRows {
   static constexpr bool kFolded = true;
+  static constexpr bool kRagged = false;
+  __device__ __forceinline__ int key_limit(int nk) const { return nk; }
+  __device__ __forceinline__ void lane_interval(const Rule& r, int qi, int* klo, int* khi) const { key_interval(r, qi, klo, khi); }
   int32_t g, pitch, log2_pitch;
   __device__ __forceinline__ int64_t q_slice(int64_t, int64_t bkv) const { return bkv * g; }
   __device__ __forceinline__ int64_t kv_slice(int64_t, int64_t bkv) const { return bkv; }
@@ -166,6 +187,7 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   __builtin_assume(kt0 % kBN == 0);  // lets key indices fold as they do where kt0 is formed in place
 
   const int nq = a.rule.q.n, nk = a.rule.k.n, d = FAST ? D : a.d, vd = FAST ? D : a.v_d;
+  const int nkl = map.key_limit(nk);  // live keys; nk stays the row stride of K and V
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, r = lane & 31;
@@ -184,15 +206,19 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
       const int idx = tid + kThr * j, c = idx >> 3, m = idx & 7;
       const bool in = (kChunks % kThr == 0) || idx < kChunks;
       const int e = k0 + 8 * m;
-      if (FAST && (kChunks % kThr == 0) && k0 + kBN <= nk) {  // whole tile in range: unguarded
+      if (FAST && (kChunks % kThr == 0) && k0 + kBN <= nkl) {  // whole tile in range: unguarded
         kr[j] = load16(K + (int64_t)c * nk + e);
         vr[j] = load16(V + (int64_t)c * nk + e);
       } else if (FAST) {
-        kr[j] = (in && e < nk) ? load16(K + (int64_t)c * nk + e) : u32x4{0, 0, 0, 0};
-        vr[j] = (in && e < nk) ? load16(V + (int64_t)c * nk + e) : u32x4{0, 0, 0, 0};
+        kr[j] = (in && e < nkl) ? load16(K + (int64_t)c * nk + e) : u32x4{0, 0, 0, 0};
+        vr[j] = (in && e < nkl) ? load16(V + (int64_t)c * nk + e) : u32x4{0, 0, 0, 0};
+        if constexpr (Map::kRagged) {  // a 16-byte chunk may straddle the length
+          kr[j] = keep_first(kr[j], nkl - e);
+          vr[j] = keep_first(vr[j], nkl - e);
+        }
       } else {
-        kr[j] = (in && c < d) ? load_chunk8(K + (int64_t)c * nk, e, nk, false) : u32x4{0, 0, 0, 0};
-        vr[j] = (in && c < vd) ? load_chunk8(V + (int64_t)c * nk, e, nk, false) : u32x4{0, 0, 0, 0};
+        kr[j] = (in && c < d) ? load_chunk8(K + (int64_t)c * nk, e, nkl, false) : u32x4{0, 0, 0, 0};
+        vr[j] = (in && c < vd) ? load_chunk8(V + (int64_t)c * nk, e, nkl, false) : u32x4{0, 0, 0, 0};
       }
     }
   };
@@ -264,7 +290,7 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   int klo = 0, kspan = 0, wlo_min = 0, wlo_max = 0, whi_min = 0, whi_max = 0;
   if (POL == 1 && wave_active) {
     int khi;
-    key_interval(a.rule, min(qi, nq - 1), &klo, &khi);
+    map.lane_interval(a.rule, min(qi, nq - 1), &klo, &khi);
     kspan = max(khi - klo + 1, 0);
     const int last = min(31, nq - 1 - wq0);
     wlo_min = __builtin_amdgcn_readfirstlane(klo);
@@ -276,13 +302,13 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   auto tcls = [&](int k0) -> int {
     const int k1 = k0 + kBN - 1;
     if (!wave_active) return 0;
-    if (POL == 0) return k1 < nk ? 2 : 1;
+    if (POL == 0) return k1 < nkl ? 2 : 1;
     if (POL == 1) {
       if (wlo_min > k1 || whi_max < k0) return 0;
       return (wlo_max <= k0 && whi_min >= k1) ? 2 : 1;
     }
-    const int c = tile_class(a.rule, wq0, wq1, k0, min(k1, nk - 1));
-    return (c == 2 && k1 >= nk) ? 1 : c;
+    const int c = tile_class(a.rule, wq0, wq1, k0, min(k1, nkl - 1));
+    return (c == 2 && k1 >= nkl) ? 1 : c;
   };
 
   auto load_tile = [&](int k0) { load_into(kreg, vreg, k0); };
@@ -339,7 +365,7 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
             ok = (unsigned)(base + off) < (unsigned)kspan;
           } else {
             const int key = k0 + off + 4 * h;
-            ok = key < nk;
+            ok = key < nkl;
             if (POL == 2) ok &= check_orders_bf(a.rule, qo, seq_order(a.rule.k, a.rule, key));
           }
           st[t][i] = ok ? st[t][i] : kNegInf;

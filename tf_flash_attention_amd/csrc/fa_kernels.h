@@ -62,6 +62,17 @@ struct GqaArgs {
   int32_t log2_pitch;
 };
 
+// ragged few-query fp16 forward (fa_fwd_f16_ragged.hip): the grouped forward's layout and plan over the
+// capacity nk = g.s.f.rule.k.n, with the live keys of each K/V slice read on the device
+struct RaggedArgs {
+  GqaArgs g;              // g.g >= 1; g.s.k_first = 0 and g.s.k_end = nk (the full rule over the capacity)
+  const int32_t* k_lens;  // device: K/V slice bkv of the whole call uses k_lens[bkv / kv_per_len], clamped to [0, nk]
+  int64_t len0;           // this launch's first K/V slice is slice len0 * kv_per_len + rem0 of the whole call, so
+  int32_t rem0;           //   its slice bkv uses k_lens[len0 + (rem0 + bkv) / kv_per_len]: a 32-bit division
+  int32_t kv_per_len;     // K/V slices that share one length, >= 1
+  int32_t tail_causal;    // != 0: query i sees keys j <= len - nq + i
+};
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;
@@ -157,6 +168,10 @@ hipError_t launch_fwd_f16_splitk(const SplitArgs& sa, hipStream_t s);
 // fa_fwd_f16_gqa.hip.  At most fwd_f16_gqa_max_batch() K/V slices per call (grid limits).
 int64_t fwd_f16_gqa_max_batch(const GqaArgs& ga);
 hipError_t launch_fwd_f16_gqa(const GqaArgs& ga, hipStream_t s);
+// the grouped forward with a per-slice key length: a chunk at or past its slice's length returns at once, and
+// the merge folds only the chunks below it — fa_fwd_f16_ragged.hip.  At most fwd_f16_gqa_max_batch(ra.g) K/V
+// slices per call (grid limits).
+hipError_t launch_fwd_f16_ragged(const RaggedArgs& ra, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

@@ -23,6 +23,11 @@ batch axis; query head ``h`` attends K/V head ``h // g``), with gradients::
     grouped_2d(...)
     attention_forward_grouped(policy, seq_dims, Q, K, V, sync_mode, ...) -> (O, l, m)   (op level)
 
+and decode over a padded K/V cache, where sequence ``s`` attends its first ``k_lens[s]`` keys and the lengths
+are an int32 tensor on the device that the kernels read (no host synchronisation; inference only)::
+
+    ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False)
+
 Tensors are ``torch`` tensors on a ROCm device in the reference's channel-first
 layout ``batch_shape + (C, *seq_shape)``.  Each call returns ``O`` or
 ``(O, l, m)``; autograd flows through ``O`` only (gradients of ``l``/``m`` are
@@ -54,6 +59,7 @@ __all__ = [
     "InvalidArgumentError", "InternalError", "estimate_forward_flops",
     "Part", "combined_1d", "combined_2d", "merge_partials",
     "grouped_1d", "grouped_2d", "attention_forward_grouped",
+    "ragged_1d",
 ]
 
 
@@ -630,6 +636,69 @@ def grouped_2d(Q, K, V, policy="full", sync_mode="none_front", window_size=1, lo
                returning_l_m=False):
     """:func:`grouped_1d` for 2d sequences."""
     return _grouped(2, Q, K, V, policy, sync_mode, window_size, log2_stride_size, is_causal, returning_l_m)
+
+
+# ----------------------------------------------------------------------------
+# Ragged few-query forward: decode over a padded K/V cache with per-sequence key lengths on the device
+# (include/fa_api.h, "Ragged few-query forward"; DESIGN.md §3.9)
+# ----------------------------------------------------------------------------
+_RAGGED_ENVELOPE = ("float16, 1d sequences, at most 128 channels, Nq >= 1, capacity >= 1 and "
+                    "g * next_pow2(Nq) <= 128 with g = Hq / Hk")
+
+
+def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False):
+    """Attention of a few queries over a padded K/V cache: Q ``batch + (Hq, C, Nq)``, K ``batch + (Hk, C, cap)``,
+    V ``batch + (Hk, Cv, cap)`` with Hq = g * Hk read from the shapes (query head h attends K/V head h // g), and
+    ``k_lens`` an int32 tensor of shape ``batch`` on the same device (0-d without a leading batch axis): sequence
+    s attends only its first ``k_lens[s]`` keys, clamped to [0, cap]; what K and V hold behind them is ignored.
+    With ``tail_causal`` the Nq queries are the last Nq positions of the sequence: query i sees keys
+    j <= k_lens[s] - Nq + i.  Rows that see no key get O = 0, l = 0 and m of bytes 0xFA.
+
+    The lengths are read by the kernels, never on the host: no synchronisation, and a captured graph may be
+    replayed after ``k_lens`` was overwritten in place.  Inference only (no gradient); float16 only; outside the
+    fused envelope the call raises NotImplementedError (a fallback would have to read the lengths on the host).
+    Returns ``O`` or ``(O, l, m)``."""
+    Qb, Qs, Q_ch, Kb, Ks, V_ch, g = verify_grouped_shapes(1, Q.shape, K.shape, V.shape)
+    dt = _dtype_id(Q, True)
+    if K.dtype != Q.dtype or V.dtype != Q.dtype:
+        raise TypeError("Q, K and V must share one dtype")
+    if not isinstance(k_lens, torch.Tensor) or k_lens.dtype != torch.int32:
+        raise TypeError(f"k_lens must be an int32 tensor, got {getattr(k_lens, 'dtype', type(k_lens).__name__)}")
+    batch = Qb[:-1]
+    if tuple(k_lens.shape) != tuple(batch):
+        raise InvalidArgumentError("The shape of k_lens should be the batch shape without the heads, but k_lens_shape = "
+                                   + _shape_str(k_lens.shape) + ", batch_shape = " + _shape_str(batch)
+                                   + " were received")
+    if k_lens.device != Q.device:
+        raise InvalidArgumentError("k_lens must be on the device of Q, K and V")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, K, V)):
+        raise RuntimeError("ragged_1d is inference only and has no gradient; call it under torch.no_grad() or "
+                           "detach its inputs")
+    prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(Qb), Qs, Ks, Q_ch, V_ch)
+    L = _lib.lib()
+    plan = (ctypes.c_int32 * 6)()
+    st = L.fa_forward_ragged_plan(prob, g, plan)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    if plan[0] == 0:
+        raise NotImplementedError("ragged_1d: outside the fused envelope (" + _RAGGED_ENVELOPE + "), got Q_shape = "
+                                  + _shape_str(Q.shape) + ", K_shape = " + _shape_str(K.shape) + ", V_shape = "
+                                  + _shape_str(V.shape))
+    _check_device_tensors(Q, K, V)
+    Q, K, V, k_lens = Q.contiguous(), K.contiguous(), V.contiguous(), k_lens.contiguous()
+    O = torch.empty(Qb + (V_ch,) + Qs, dtype=Q.dtype, device=Q.device)
+    l = torch.empty(Qb + Qs, dtype=torch.float32, device=Q.device)
+    m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
+    ws_bytes = int(L.fa_forward_ragged_workspace_bytes(prob, g))
+    kv_per_len = int(Kb[-1]) if Kb else 1
+    with torch.cuda.device(Q.device):
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
+        st = L.fa_forward_ragged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                 k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)), O.data_ptr(), l.data_ptr(),
+                                 m.data_ptr(), ws.data_ptr(), ws_bytes)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    return (O, l, m) if returning_l_m else O
 
 
 # ----------------------------------------------------------------------------
