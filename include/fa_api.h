@@ -183,6 +183,44 @@ int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group,
                       void* O, void* l, void* m,
                       void* workspace, size_t workspace_bytes);
 
+/* Paged few-query forward (decode over a PAGED K/V cache): fa_forward_ragged with K and V held in pools of
+ * fixed-size pages and a per-sequence block table on the device.
+ *   K_pool [num_pages][Hk][d][page], V_pool [num_pages][Hk][v_d][page] fp16, the key axis contiguous: a page
+ *     holds `page` consecutive key positions of all Hk = kv_per_len K/V heads of one sequence.
+ *   block_table: DEVICE int32 [sequences][max_pages], sequences = (b / kv_group) / kv_per_len.  Entry [s][p] is
+ *     the pool page that holds keys [p * page, (p + 1) * page) of sequence s.  Several sequences may name the
+ *     same page (a shared prefix): the forward only reads the pools.
+ *   k_lens, kv_per_len, tail_causal, the empty rows and Q / O / l / m: as in fa_forward_ragged.  K/V slice bkv
+ *     of the call is head bkv % kv_per_len of sequence bkv / kv_per_len.
+ *   p->k_seq[0] = nk = max_pages * page is the CAPACITY; the kernels clamp a length to [0, nk].
+ * The host reads neither k_lens nor block_table: no host synchronisation, and either may be overwritten in
+ * place between replays of a captured graph.  The kernels load only the table entries of pages that hold a live
+ * key: entries at or past ceil(len / page) may hold anything.  Every entry that is loaded is clamped to
+ * [0, num_pages - 1] before it forms an address, as the lengths are clamped: a corrupt table gives a wrong
+ * answer, never an access outside the pools.
+ *
+ * Envelope: fa_forward_ragged's, plus page % 64 == 0 (a 64-key tile never straddles two pages; page need not be
+ *   a power of two).  A well-formed problem outside it, a smaller page included: FA_ERR_UNSUPPORTED, nothing
+ *   written; there is no gather fallback.
+ * FA_ERR_INVALID_ARGUMENT with text in fa_last_error(): fa_forward_ragged's own argument errors, page < 1,
+ *   max_pages < 1, max_pages * page != nk (the plan functions: nk % page != 0), num_pages < 1, and with b > 0 a
+ *   null block_table, pool or k_lens.
+ *
+ * fa_forward_paged_plan / fa_forward_paged_workspace_bytes (host-only): fa_forward_ragged_plan's and
+ *   fa_forward_ragged_workspace_bytes's values over the capacity inside the envelope, out[0] == 0 / 0 bytes
+ *   outside it (page % 64 != 0).  Pure functions of the problem WITHOUT b, the lengths or the table.
+ * fa_forward_paged: a smaller workspace returns FA_ERR_WORKSPACE_TOO_SMALL with nothing written; b == 0 returns
+ *   FA_OK with nothing launched.  Same plan, same tiles, same staged values: the (O, l, m) bits are those of
+ *   fa_forward_ragged on the cache gathered into [b / kv_group][channels][nk] with the same lengths. */
+int fa_forward_paged_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]);
+size_t fa_forward_paged_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page);
+int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group,
+                     const void* Q, const void* K_pool, const void* V_pool,
+                     const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                     const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                     void* O, void* l, void* m,
+                     void* workspace, size_t workspace_bytes);
+
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);

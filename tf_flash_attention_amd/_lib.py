@@ -39,6 +39,9 @@ EXPORTED_SYMBOLS = (
     "fa_forward_ragged_plan",
     "fa_forward_ragged_workspace_bytes",
     "fa_forward_ragged",
+    "fa_forward_paged_plan",
+    "fa_forward_paged_workspace_bytes",
+    "fa_forward_paged",
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_backward_split_plan",
@@ -148,6 +151,16 @@ def _declare(lib):
         lib.fa_forward_ragged.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32,
                                           vp, vp, vp, vp, ctypes.c_size_t]
         lib.fa_forward_ragged.restype = ctypes.c_int
+    # (absent from a library built before the paged forward, as above)
+    if hasattr(lib, "fa_forward_paged"):
+        lib.fa_forward_paged_plan.argtypes = [P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
+        lib.fa_forward_paged_plan.restype = ctypes.c_int
+        lib.fa_forward_paged_workspace_bytes.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
+        lib.fa_forward_paged_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_forward_paged.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp,
+                                         ctypes.c_size_t]
+        lib.fa_forward_paged.restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

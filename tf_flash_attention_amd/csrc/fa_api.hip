@@ -284,6 +284,24 @@ int check_ragged(const fa_problem* p, int32_t kv_group) {
   return FA_OK;
 }
 
+// Paged few-query forward: ragged_plan over the capacity nk = max_pages * page, where a page
+// is a multiple of the 64-key tile.  Neither the lengths nor the block table (device data) enter the plan.
+GroupedPlan paged_plan(const fa_problem* p, int32_t kv_group, int32_t page) {
+  GroupedPlan s = ragged_plan(p, kv_group);
+  if (page % kSplitTile != 0) s.nchunks = s.chunk = 0;
+  return s;
+}
+
+int check_paged(const fa_problem* p, int32_t kv_group, int32_t page) {
+  const int st = check_ragged(p, kv_group);
+  if (st != FA_OK) return st;
+  if (page < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: page must be >= 1");
+  if (p->seq_dims == 1 && p->k_seq[0] % page != 0)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: the capacity k_seq[0] = " + std::to_string(p->k_seq[0]) +
+                                                  " is not a multiple of page = " + std::to_string(page));
+  return FA_OK;
+}
+
 // Split-key routing of the fp16 backward's dQ pass: the forward's plan, where the
 // dQ kernel's 32-bit buffer offsets reach a slice's K / V channel rows (the b-free part of
 // bwd_f16_fast_supported).  Also a pure function of the problem WITHOUT b, and a subset of the
@@ -623,6 +641,88 @@ int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const
   return FA_OK;
 }
 
+int fa_forward_paged_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]) {
+  const int st = check_paged(p, kv_group, page);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const GroupedPlan s = paged_plan(p, kv_group, page);
+  out[0] = s.nchunks;
+  out[1] = s.chunk;
+  out[2] = s.kb;
+  out[3] = s.ke;
+  out[4] = s.pitch;
+  out[5] = s.rows;
+  return FA_OK;
+}
+
+size_t fa_forward_paged_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page) {
+  if (check_paged(p, kv_group, page) != FA_OK) return 0;
+  const GroupedPlan s = paged_plan(p, kv_group, page);
+  return s.nchunks ? grouped_ws_bytes(p, kv_group, s) : 0;
+}
+
+int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
+                     const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                     const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m,
+                     void* workspace, size_t workspace_bytes) {
+  const int st = check_paged(p, kv_group, page);
+  if (st != FA_OK) return st;
+  const int64_t bkv = p->b / kv_group;
+  if (kv_per_len < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "kv_per_len must be >= 1");
+  if (bkv % kv_per_len != 0)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "the number of K/V slices b / kv_group = " + std::to_string(bkv) +
+                                                  " is not a multiple of kv_per_len = " + std::to_string(kv_per_len));
+  if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages must be >= 1");
+  if ((int64_t)max_pages * page != p->k_seq[0])
+    return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages * page = " + std::to_string((int64_t)max_pages * page) +
+                                                  " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
+  if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: num_pages must be >= 1");
+  const GroupedPlan gp = paged_plan(p, kv_group, page);
+  if (gp.nchunks == 0)
+    return set_error(FA_ERR_UNSUPPORTED,
+                     "paged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                     "kv_group * pitch <= 128, nq >= 1, nk >= 1, page % 64 == 0)");
+  if (!workspace || workspace_bytes < grouped_ws_bytes(p, kv_group, gp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
+                     "forward workspace is smaller than fa_forward_paged_workspace_bytes()");
+  FA_DIAG_COUNT(0);
+  if (p->b == 0) return FA_OK;
+  if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
+  if (!block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null block_table");
+  if (!K_pool || !V_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null K_pool or V_pool");
+  fa::PagedArgs pa;
+  fa::RaggedArgs& ra = pa.r;
+  fa::GqaArgs& ga = ra.g;
+  fa::SplitArgs& sa = ga.s;
+  fa::FwdArgs& a = sa.f;
+  a.d = p->d; a.v_d = p->v_d;
+  a.scale = 1.0 / sqrt((double)p->d);
+  build_rule(p, &a.rule);
+  sa.nchunks = gp.nchunks; sa.chunk = gp.chunk; sa.k_first = 0; sa.k_end = gp.ke;
+  ga.g = kv_group; ga.pitch = gp.pitch; ga.log2_pitch = ilog2(gp.pitch);
+  ra.k_lens = k_lens; ra.kv_per_len = kv_per_len; ra.tail_causal = tail_causal != 0;
+  pa.block_table = block_table; pa.max_pages = max_pages; pa.page = page;
+  pa.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
+  a.K = K_pool; a.V = V_pool;  // the pools are not sliced per launch: the table says where a slice's keys are
+  const int64_t nq = a.rule.q.n;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // fa_forward_ragged's launches: one pair covers every realistic batch
+  const int64_t bmax = fa::fwd_f16_gqa_max_batch(ga);
+  for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {  // b0 counts K/V slices
+    a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
+    a.Q = static_cast<const uint16_t*>(Q) + b0 * kv_group * p->d * nq;
+    a.O = static_cast<uint16_t*>(O) + b0 * kv_group * p->v_d * nq;
+    a.l = static_cast<float*>(l) + b0 * kv_group * nq;
+    a.m = static_cast<uint16_t*>(m) + b0 * kv_group * nq;
+    sa.ws = static_cast<float*>(workspace) + b0 * gp.nchunks * (p->v_d + 3) * gp.rows;
+    ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
+    const hipError_t e = fa::launch_fwd_f16_paged(pa, s);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
 size_t fa_backward_workspace_bytes(const fa_problem* p) {
   if (fa_validate(p) != FA_OK) return 0;
   return ws_layout(p).total;
@@ -954,7 +1054,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
 }
 
 }  // extern "C"

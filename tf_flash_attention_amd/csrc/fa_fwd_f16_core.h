@@ -3,7 +3,7 @@
 // fwd_f16_core runs one workgroup's share of a (batch, head) slice: 32*NW query rows from q0
 // against the key tiles [kt0, kt0 + 64*ntiles), from the prologue loads through the last
 // ring step, and hands back each wave's unnormalised accumulator and softmax statistics
-// (WaveState).  Four
+// (WaveState).  Five
 // kernels wrap it and differ only in which block gets which rows and keys and in the epilogue:
 //   * fwd_f16_kernel (fa_fwd_f16.hip): block -> (slice, query block), the rule-bounded key
 //     range of that block, normalises and writes O, l, m;
@@ -12,7 +12,9 @@
 //   * gqa_partial_kernel (fa_fwd_f16_gqa.hip): block -> (K/V slice, key chunk) with the query heads that
 //     share the K/V slice folded into the block's rows (FoldedRows below), the same partial format;
 //   * ragged_partial_kernel (fa_fwd_f16_ragged.hip): the same block with a per-slice key length read on
-//     the device (the row maps' key_limit / lane_interval below).
+//     the device (the row maps' key_limit / lane_interval below);
+//   * paged_partial_kernel (fa_fwd_f16_paged.hip): the ragged block with each key tile read from a page pool
+//     through a device block table (the row maps' tile below).
 // The structure:
 //   * Sᵀ = Kᵀ·Q and Oᵀ = V·Pᵀ on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
 //     Computing the TRANSPOSED scores puts the key index in the MFMA rows, so
@@ -109,9 +111,17 @@ struct WaveRegs {
 // the rule's own interval.  A map with kRagged (fa_fwd_f16_ragged.hip) answers a per-slice length below nk,
 // and the core then zeroes staged K / V past it element by element: what lies there is not the caller's
 // data, and a NaN or Inf times P = 0 would poison the PV product.
+// Last, where a key tile lies: for a tile-aligned k0, the K and V pointers of channel row 0 at key k0 and the row
+// stride there.  For these maps and RaggedRows (kPaged false) that is K + k0, V + k0 and nk, the contiguous slice,
+// and load_into keeps indexing the slice's rows from key 0 as it always has: a hook that had every map hand back
+// K + k0, V + k0 and nk moved the register allocation of 72 of the 75 existing kernels
+// (profiles/paged_core_asm_equal.txt).  A map with kPaged (fa_fwd_f16_paged.hip) is asked, tile(K, V, k0, ...):
+// it looks the tile's page up in a block table and answers a pointer into a page pool with the page as the
+// stride; a page is a multiple of the 64-key tile, so a tile never straddles two pages.
 struct IdentityRows {
   static constexpr bool kFolded = false;
   static constexpr bool kRagged = false;
+  static constexpr bool kPaged = false;
   __device__ __forceinline__ int key_limit(int nk) const { return nk; }
   __device__ __forceinline__ void lane_interval(const Rule& r, int qi, int* klo, int* khi) const { key_interval(r, qi, klo, khi); }
   __device__ __forceinline__ int64_t q_slice(int64_t bi, int64_t) const { return bi; }
@@ -124,6 +134,7 @@ struct IdentityRows {
 struct FoldedRows {
   static constexpr bool kFolded = true;
   static constexpr bool kRagged = false;
+  static constexpr bool kPaged = false;
   __device__ __forceinline__ int key_limit(int nk) const { return nk; }
   __device__ __forceinline__ void lane_interval(const Rule& r, int qi, int* klo, int* khi) const { key_interval(r, qi, klo, khi); }
   int32_t g, pitch, log2_pitch;
@@ -201,24 +212,32 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
 
   // ---- register staging of one K/V tile (16-B chunks; chunk = 8 keys of one channel row)
   auto load_into = [&](u32x4 (&kr)[kCPT], u32x4 (&vr)[kCPT], int k0) {
+    // channel row 0 of the slice, the row stride and the key that index 0 stands for; a paged map moves all three
+    // to the tile (for the other maps these are new names for K, V, nk and 0, and the code below is unchanged)
+    const __half *Kt = K, *Vt = V;
+    int ts = nk, kb = 0;
+    if constexpr (Map::kPaged) {
+      map.tile(K, V, k0, &Kt, &Vt, &ts);
+      kb = k0;
+    }
 #pragma unroll
     for (int j = 0; j < kCPT; ++j) {
       const int idx = tid + kThr * j, c = idx >> 3, m = idx & 7;
       const bool in = (kChunks % kThr == 0) || idx < kChunks;
       const int e = k0 + 8 * m;
       if (FAST && (kChunks % kThr == 0) && k0 + kBN <= nkl) {  // whole tile in range: unguarded
-        kr[j] = load16(K + (int64_t)c * nk + e);
-        vr[j] = load16(V + (int64_t)c * nk + e);
+        kr[j] = load16(Kt + (int64_t)c * ts + (e - kb));
+        vr[j] = load16(Vt + (int64_t)c * ts + (e - kb));
       } else if (FAST) {
-        kr[j] = (in && e < nkl) ? load16(K + (int64_t)c * nk + e) : u32x4{0, 0, 0, 0};
-        vr[j] = (in && e < nkl) ? load16(V + (int64_t)c * nk + e) : u32x4{0, 0, 0, 0};
+        kr[j] = (in && e < nkl) ? load16(Kt + (int64_t)c * ts + (e - kb)) : u32x4{0, 0, 0, 0};
+        vr[j] = (in && e < nkl) ? load16(Vt + (int64_t)c * ts + (e - kb)) : u32x4{0, 0, 0, 0};
         if constexpr (Map::kRagged) {  // a 16-byte chunk may straddle the length
           kr[j] = keep_first(kr[j], nkl - e);
           vr[j] = keep_first(vr[j], nkl - e);
         }
       } else {
-        kr[j] = (in && c < d) ? load_chunk8(K + (int64_t)c * nk, e, nkl, false) : u32x4{0, 0, 0, 0};
-        vr[j] = (in && c < vd) ? load_chunk8(V + (int64_t)c * nk, e, nkl, false) : u32x4{0, 0, 0, 0};
+        kr[j] = (in && c < d) ? load_chunk8(Kt + (int64_t)c * ts, e - kb, nkl - kb, false) : u32x4{0, 0, 0, 0};
+        vr[j] = (in && c < vd) ? load_chunk8(Vt + (int64_t)c * ts, e - kb, nkl - kb, false) : u32x4{0, 0, 0, 0};
       }
     }
   };

@@ -18,7 +18,7 @@
 // nq positions of the sequence, query i sees keys [0, len - nq + i]; queries i < nq - len see nothing.
 // With every length equal to the capacity and g >= 2 the full form runs gqa_partial_kernel's loop over the
 // same chunks, and the result is bitwise fa_forward_grouped's.
-#include "fa_fwd_f16_core.h"
+#include "fa_fwd_f16_ragged.h"
 
 namespace fa {
 namespace {
@@ -27,32 +27,6 @@ using namespace f16core;
 
 constexpr int kNW = 4;       // waves per workgroup: 128 folded rows
 constexpr int kF = kFDot2;   // the core's structure flags: fwd_f16_kernel's default form
-
-// FoldedRows with a per-slice key length (fa_fwd_f16_core.h: the row maps)
-struct RaggedRows {
-  static constexpr bool kFolded = true;
-  static constexpr bool kRagged = true;
-  int32_t g, pitch, log2_pitch;
-  int32_t len, nq;
-  __device__ __forceinline__ int64_t q_slice(int64_t, int64_t bkv) const { return bkv * g; }
-  __device__ __forceinline__ int64_t kv_slice(int64_t, int64_t bkv) const { return bkv; }
-  __device__ __forceinline__ int wave_q0(int, int w) const { return (32 * w) & (pitch - 1); }
-  __device__ __forceinline__ bool wave_active(int wq0, int w, int nq_) const { return 32 * w < g * pitch && wq0 < nq_; }
-  __device__ __forceinline__ int lane_q(int, int w, int r) const { return (32 * w + r) & (pitch - 1); }
-  __device__ __forceinline__ int lane_row(int, int w, int r) const { return 32 * w + r; }
-  __device__ __forceinline__ int key_limit(int) const { return len; }
-  // the tail-causal interval (POL 1): empty (khi < 0) for a query before the sequence's first position
-  __device__ __forceinline__ void lane_interval(const Rule&, int qi, int* klo, int* khi) const {
-    *klo = 0;
-    *khi = len - nq + qi;
-  }
-};
-
-// the length of K/V slice bkv of this launch, clamped to [0, nk]; the same value in every lane
-__device__ __forceinline__ int slice_len(const RaggedArgs& ra, uint32_t bkv) {
-  const int len = ra.k_lens[ra.len0 + ((uint32_t)ra.rem0 + bkv) / (uint32_t)ra.kv_per_len];
-  return min(max(len, 0), ra.g.s.f.rule.k.n);
-}
 
 template <int D, int POL, bool FAST>
 __global__ __launch_bounds__(kNW * 64, waves_per_eu(D, kF)) void ragged_partial_kernel(RaggedArgs ra) {
@@ -170,15 +144,21 @@ hipError_t launch_partial_t(const RaggedArgs& ra, hipStream_t s) {
 
 }  // namespace
 
+// (also the merge of the paged forward, fa_fwd_f16_paged.hip: the same records, lengths and outputs)
+hipError_t launch_fwd_f16_ragged_merge(const RaggedArgs& ra, hipStream_t s) {
+  const FwdArgs& a = ra.g.s.f;
+  const int64_t threads = a.b * (int64_t)a.v_d * ra.g.g * a.rule.q.n;
+  hipLaunchKernelGGL(ragged_merge_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ra);
+  return hipGetLastError();
+}
+
 hipError_t launch_fwd_f16_ragged(const RaggedArgs& ra, hipStream_t s) {
   const FwdArgs& a = ra.g.s.f;
   const int dm = max(a.d, a.v_d);
   hipError_t e = dm <= 32 ? launch_partial_t<32>(ra, s) : dm <= 64 ? launch_partial_t<64>(ra, s)
                                                                      : launch_partial_t<128>(ra, s);
   if (e != hipSuccess) return e;
-  const int64_t threads = a.b * (int64_t)a.v_d * ra.g.g * a.rule.q.n;
-  hipLaunchKernelGGL(ragged_merge_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ra);
-  return hipGetLastError();
+  return launch_fwd_f16_ragged_merge(ra, s);
 }
 
 }  // namespace fa

@@ -73,6 +73,18 @@ struct RaggedArgs {
   int32_t tail_causal;    // != 0: query i sees keys j <= len - nq + i
 };
 
+// paged few-query fp16 forward (fa_fwd_f16_paged.hip): the ragged forward over a capacity of max_pages * page
+// keys, with K and V held in pools of pages, [num_pages][Hk][channels][page] halfs, and a block table on the
+// device.  r.g.s.f.K / V are the POOLS' base pointers (never advanced per launch) and r.kv_per_len is Hk:
+// K/V slice bkv of the whole call is head bkv % Hk of sequence bkv / Hk.
+struct PagedArgs {
+  RaggedArgs r;
+  const int32_t* block_table;  // device: [sequences][max_pages]; entry [s][p] holds keys [p*page, (p+1)*page) of s
+  int32_t max_pages;           // >= 1; max_pages * page = nk
+  int32_t page;                // keys per page, a multiple of 64
+  int32_t last_page;           // num_pages - 1: every loaded entry is clamped to [0, last_page]
+};
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;
@@ -172,6 +184,10 @@ hipError_t launch_fwd_f16_gqa(const GqaArgs& ga, hipStream_t s);
 // the merge folds only the chunks below it — fa_fwd_f16_ragged.hip.  At most fwd_f16_gqa_max_batch(ra.g) K/V
 // slices per call (grid limits).
 hipError_t launch_fwd_f16_ragged(const RaggedArgs& ra, hipStream_t s);
+hipError_t launch_fwd_f16_ragged_merge(const RaggedArgs& ra, hipStream_t s);  // its second kernel alone
+// the ragged forward over a page pool and a device block table: the same chunks, records and merge, with each
+// key tile's address looked up in the table — fa_fwd_f16_paged.hip.  The same batch limit.
+hipError_t launch_fwd_f16_paged(const PagedArgs& pa, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

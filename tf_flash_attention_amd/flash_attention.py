@@ -28,6 +28,11 @@ are an int32 tensor on the device that the kernels read (no host synchronisation
 
     ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False)
 
+or over a paged cache: pools ``[num_pages, Hk, C, page]`` of fixed-size pages and an int32 block table on the device
+that says which page holds which keys of which sequence (also read by the kernels only)::
+
+    paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False)
+
 Tensors are ``torch`` tensors on a ROCm device in the reference's channel-first
 layout ``batch_shape + (C, *seq_shape)``.  Each call returns ``O`` or
 ``(O, l, m)``; autograd flows through ``O`` only (gradients of ``l``/``m`` are
@@ -59,7 +64,7 @@ __all__ = [
     "InvalidArgumentError", "InternalError", "estimate_forward_flops",
     "Part", "combined_1d", "combined_2d", "merge_partials",
     "grouped_1d", "grouped_2d", "attention_forward_grouped",
-    "ragged_1d",
+    "ragged_1d", "paged_1d",
 ]
 
 
@@ -696,6 +701,106 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False):
         st = L.fa_forward_ragged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
                                  k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)), O.data_ptr(), l.data_ptr(),
                                  m.data_ptr(), ws.data_ptr(), ws_bytes)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    return (O, l, m) if returning_l_m else O
+
+
+# ----------------------------------------------------------------------------
+# Paged few-query forward: decode over a pool of K/V pages with a block table on the device
+# (include/fa_api.h, "Paged few-query forward")
+# ----------------------------------------------------------------------------
+_PAGE_CONDITION = "the page size (the last axis of K_pool and V_pool) must be a multiple of 64 keys"
+
+
+def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False):
+    """``ragged_1d`` over a paged K/V cache: Q ``batch + (Hq, C, Nq)``, ``K_pool`` ``[num_pages, Hk, C, page]``,
+    ``V_pool`` ``[num_pages, Hk, Cv, page]`` with Hq = g * Hk read from the shapes, ``block_table`` an int32 tensor
+    ``batch + (max_pages,)`` and ``k_lens`` an int32 tensor of shape ``batch``, both on the device of Q.  A page
+    holds ``page`` consecutive key positions of all Hk heads of one sequence; ``block_table[s, p]`` is the pool page
+    with keys ``[p * page, (p + 1) * page)`` of sequence s, which attends its first ``k_lens[s]`` keys, clamped to
+    ``[0, max_pages * page]``.  ``tail_causal`` and the rows without a key are ``ragged_1d``'s.  Sequences may share
+    pages (a common prefix).
+
+    Neither tensor is read on the host: no synchronisation, and a captured graph may be replayed after ``k_lens`` or
+    ``block_table`` was overwritten in place.  Table entries of pages without a live key are never loaded; a loaded
+    entry is clamped to ``[0, num_pages - 1]``.  Appending token ``new`` (``[Hk, C]``) of sequence s at position
+    ``pos`` (a device tensor) needs no host read either, it is an ``index_put`` with device indices::
+
+        K_pool[block_table[s, pos // page], :, :, pos % page] = new
+
+    Inference only (no gradient); float16 only; the page size must be a multiple of 64; outside the envelope the
+    call raises NotImplementedError (there is no gather fallback).  Returns ``O`` or ``(O, l, m)``."""
+    if len(K_pool.shape) != 4 or len(V_pool.shape) != 4:
+        raise InvalidArgumentError("K_pool and V_pool should be [num_pages, Hk, channels, page], but K_pool_shape = "
+                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
+                                   + " were received")
+    num_pages, hk, k_ch, page = (int(x) for x in K_pool.shape)
+    if (int(V_pool.shape[0]), int(V_pool.shape[1]), int(V_pool.shape[3])) != (num_pages, hk, page):
+        raise InvalidArgumentError("K_pool and V_pool should agree in num_pages, Hk and page, but K_pool_shape = "
+                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
+                                   + " were received")
+    v_ch = int(V_pool.shape[2])
+    if len(Q.shape) < 3:
+        raise InvalidArgumentError("Q should be batch + (Hq, C, Nq), but Q_shape = " + _shape_str(Q.shape)
+                                   + " was received")
+    batch, hq, q_ch, nq = tuple(Q.shape[:-3]), int(Q.shape[-3]), int(Q.shape[-2]), int(Q.shape[-1])
+    if q_ch != k_ch:
+        raise InvalidArgumentError("The channels of Q and K_pool should be the same, but Q_shape = "
+                                   + _shape_str(Q.shape) + ", K_pool_shape = " + _shape_str(K_pool.shape)
+                                   + " were received")
+    if num_pages < 1 or hk < 1 or hq % hk != 0:
+        raise InvalidArgumentError("The heads of Q should be a multiple of the heads of a page, and the pools should "
+                                   "hold a page, but Q_shape = " + _shape_str(Q.shape) + ", K_pool_shape = "
+                                   + _shape_str(K_pool.shape) + " were received")
+    dt = _dtype_id(Q, True)
+    if K_pool.dtype != Q.dtype or V_pool.dtype != Q.dtype:
+        raise TypeError("Q, K_pool and V_pool must share one dtype")
+    for name, t in (("block_table", block_table), ("k_lens", k_lens)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if tuple(block_table.shape[:-1]) != batch or len(block_table.shape) != len(batch) + 1 or block_table.shape[-1] < 1:
+        raise InvalidArgumentError("The shape of block_table should be the batch shape without the heads plus "
+                                   "(max_pages,), but block_table_shape = " + _shape_str(block_table.shape)
+                                   + ", batch_shape = " + _shape_str(batch) + " were received")
+    if tuple(k_lens.shape) != batch:
+        raise InvalidArgumentError("The shape of k_lens should be the batch shape without the heads, but k_lens_shape = "
+                                   + _shape_str(k_lens.shape) + ", batch_shape = " + _shape_str(batch)
+                                   + " were received")
+    if block_table.device != Q.device or k_lens.device != Q.device:
+        raise InvalidArgumentError("block_table and k_lens must be on the device of Q, K_pool and V_pool")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, K_pool, V_pool)):
+        raise RuntimeError("paged_1d is inference only and has no gradient; call it under torch.no_grad() or "
+                           "detach its inputs")
+    if page < 1 or page % 64 != 0:
+        raise NotImplementedError("paged_1d: " + _PAGE_CONDITION + ", got page = " + str(page))
+    g, max_pages = hq // hk, int(block_table.shape[-1])
+    cap = max_pages * page
+    if cap > 2 ** 30:
+        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_ch)
+    L = _lib.lib()
+    plan = (ctypes.c_int32 * 6)()
+    st = L.fa_forward_paged_plan(prob, g, page, plan)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    if plan[0] == 0:
+        raise NotImplementedError("paged_1d: outside the fused envelope (" + _RAGGED_ENVELOPE + "; and "
+                                  + _PAGE_CONDITION + "), got Q_shape = " + _shape_str(Q.shape) + ", K_pool_shape = "
+                                  + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape))
+    _check_device_tensors(Q, K_pool, V_pool)
+    Q, K_pool, V_pool = Q.contiguous(), K_pool.contiguous(), V_pool.contiguous()
+    block_table, k_lens = block_table.contiguous(), k_lens.contiguous()
+    O = torch.empty(batch + (hq, v_ch, nq), dtype=Q.dtype, device=Q.device)
+    l = torch.empty(batch + (hq, nq), dtype=torch.float32, device=Q.device)
+    m = torch.empty(batch + (hq, nq), dtype=Q.dtype, device=Q.device)
+    ws_bytes = int(L.fa_forward_paged_workspace_bytes(prob, g, page))
+    with torch.cuda.device(Q.device):
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
+        st = L.fa_forward_paged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(), V_pool.data_ptr(),
+                                block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(), hk,
+                                int(bool(tail_causal)), O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(),
+                                ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
