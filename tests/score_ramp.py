@@ -48,7 +48,9 @@ instead of 2^-12; the forward and the dQ pass pre-scale Q, the dK / dV pass pre-
 
 Also here: a numpy model of the lazy rebase (which tiles of which rows take the branch), an emulation of
 the documented fp16 deviation with the checks run_case applies, and the table of cases that
-tests/test_gpu_score_range.py runs and tests/test_score_ramp_inputs.py vets on the CPU.
+tests/test_gpu_score_range.py runs and tests/test_score_ramp_inputs.py vets on the CPU; and, at the end, the
+same for the few-query decode forwards (DECODE_CASES: tests/test_gpu_decode_score_range.py,
+tests/test_decode_score_ramp_inputs.py).
 """
 
 import math
@@ -116,8 +118,10 @@ def row_tops(mask):
     return kmax, kmin, has
 
 
-def ramp_inputs(prob, dtype, batch, d, vd, qs, ks, ramp, seed=0):
-    """(Q, K, V, dO) of the given dtype and a dict with the row kinds, each row's top key and the mask."""
+def ramp_inputs(prob, dtype, batch, d, vd, qs, ks, ramp, seed=0, mask=None, row0=0):
+    """(Q, K, V, dO) of the given dtype and a dict with the row kinds, each row's top key and the mask.
+    mask (optional, bool [nq, nk]) stands in for the one derived from prob; row0 shifts the cycle of the row
+    kinds (row q is of kind KIND_CYCLE[(row0 + q) % 4]: the decode cases cycle over the folded row index)."""
     assert d >= 6 and float(ramp.u) == 2.0 ** round(math.log2(ramp.u))
     rng = np.random.default_rng(seed)
     batch, qs, ks = tuple(batch), tuple(qs), tuple(ks)
@@ -127,10 +131,10 @@ def ramp_inputs(prob, dtype, batch, d, vd, qs, ks, ramp, seed=0):
     K = rng.uniform(-ramp.a, ramp.a, (b, d, nk))
     V = rng.uniform(-2, 2, (b, vd, nk))
     dO = rng.uniform(-2, 2, (b, vd, nq))
-    mask = O.problem_mask(prob, qs, ks)
+    mask = O.problem_mask(prob, qs, ks) if mask is None else np.asarray(mask, dtype=bool)
     kmax, kmin, has = row_tops(mask)
     e, f = plateau_exponents(nk, ramp), plateau_exponents(nk, ramp, mirror=True)
-    kind = np.array(KIND_CYCLE)[np.arange(nq) % 4]
+    kind = np.array(KIND_CYCLE)[(row0 + np.arange(nq)) % 4]
     kind = np.where(has, kind, FLAT)            # rows that attend nothing keep their sentinels
     top = np.where(kind == FALL, kmin, kmax)
     K[:, 0, :], K[:, 3, :] = -ramp.u * 2.0 ** e, -ramp.u * 2.0 ** f
@@ -366,7 +370,7 @@ def _ramp(d, W, dtype, big=False, E=None):
     lift sets (at 24 the fp32 dQ of the zero-valued special channels, sums of K·dS terms near 8192·|dS|
     that cancel, missed the unchanged backward gate on a few elements in 1e5)."""
     f64 = dtype == np.float64
-    q0, u, E0 = {(32, False): (3.0, 4, 10), (64, False): (2.0, 8, 10), (128, False): (3.0, 8, 9),
+    q0, u, E0 = {(32, False): (3.0, 4, 10), (64, False): (2.0, 8, 10), (96, False): (3.0, 8, 9), (128, False): (3.0, 8, 9),
                 (256, False): (2.0, 16, 9), (300, False): (2.5, 16, 8),
                 (32, True): (2.0, 16, 9), (64, True): (3.0, 16, 8), (128, True): (2.0, 32, 8),
                 (256, True): (3.0, 32, 7), (300, True): (3.0, 32, 7)}[(d, f64)]
@@ -465,3 +469,265 @@ CASE_BY_ID = {c.id: c for c in CASES}
 # FA_FWD_VARIANT=2116: the ping-pong study kernel without its rebase (kANoRebase); this case must FAIL there
 NO_REBASE_CASE = _c("diag-2116-no-rebase", F16, "full", "none_front", 64, 64, 300, 776, 64, 64, variant="2116",
                     bwd=False)
+
+
+# --------------------------------------------------------------------------- the few-query decode forwards
+# fa_forward_ragged / fa_forward_paged / fa_forward_grouped (csrc/fa_fwd_f16_ragged.hip, _paged.hip, _gqa.hip): one
+# workgroup per (K/V slice, key chunk) folds the g heads of the slice into rows rho = head * pitch + query, wave w
+# holds rows [32 w, 32 w + 32), every chunk seeds afresh from its first 64-key tile, and a merge kernel weighs the
+# chunks by 2^(m_chunk - max).  The K/V slice s attends its first L_s keys, so its staircase is that of a problem
+# with L_s keys under ragged_ref.ragged_mask, embedded into capacity-wide K / V.  Past L_s the special channels are
+# K[0] = K[3] = 0, K[1] = K[4] = 1 (a climb or fall row's score there lies σ0·2^e(top) ABOVE its top), the lift
+# channel continues and V is 65504: a row max, a rebase decision or a PV term taken from a key past the length
+# misses the gate by orders of magnitude.
+DECODE_TILE, DECODE_THR = 64, 8.0
+
+
+def decode_plan(nq, cap, g):
+    """(chunks, chunk, pitch) of the fused plan over keys [0, cap): the arithmetic tests/test_grouped_plan.py and
+    tests/test_ragged_plan.py hold the library to."""
+    from tests.test_grouped_plan import _chunks
+    pitch = 1
+    while pitch < nq:
+        pitch *= 2
+    chunks, chunk = _chunks(0, cap, g * pitch)
+    return chunks, chunk, pitch
+
+
+@dataclass
+class DecodeCase:
+    """One staircase case of the decode family.  lens: one length per K/V slice (grouped: every slice has the
+    capacity).  tail: the tail-causal form (grouped: the causal rule under scale_end, the same mask at L = cap).
+    lift < 0: the sign is carried by Q[2]."""
+    id: str
+    entry: str                 # "ragged", "paged" (the same inputs through a block table) or "grouped"
+    d: int
+    vd: int
+    g: int
+    nq: int
+    cap: int
+    lens: tuple
+    tail: bool = False         # grouped: the causal rule under scale_end
+    big: bool = False
+    lift: float = 24.0
+    pages: tuple = ()          # paged: the page sizes the case runs at
+    W: int = 64                # keys a plateau
+    seed: int = 0
+    waive: tuple = field(default_factory=tuple)
+
+    @property
+    def plan(self):
+        return decode_plan(self.nq, self.cap, self.g)
+
+    @property
+    def ramp(self):
+        return _ramp(self.d, self.W, np.float16, self.big)
+
+    def mask(self, L):
+        """bool [nq, L]: the keys each query sees in a slice of L live keys (grouped, tail: the causal rule under
+        scale_end, whose rows top out at evenly spaced keys)."""
+        from tests import ragged_ref
+        if self.entry == "grouped" and self.tail:
+            return O.problem_mask(O.Problem("causal", 1, "scale_end"), (self.nq,), (L,))
+        return ragged_ref.ragged_mask(self.nq, L, L, self.tail)
+
+
+def _past_fill(K, V, L, ramp, rng):
+    kappa = K[2, 0]
+    K[:, L:] = rng.uniform(-ramp.a, ramp.a, K[:, L:].shape)
+    K[2, L:] = kappa
+    K[0, L:] = K[3, L:] = 0.0
+    K[1, L:] = K[4, L:] = 1.0
+    V[:, L:] = 65504.0
+
+
+def decode_inputs(case):
+    """Q [bkv * g, d, nq], K [bkv, d, cap], V [bkv, v_d, cap] (fp16), and per Q slice the row kinds [nq], the info
+    dict of ramp_inputs over the slice's L keys (None for L = 0) and the bound of m_rounding_bound [nq]."""
+    d, vd, g, nq, cap, ramp = case.d, case.vd, case.g, case.nq, case.cap, case.ramp
+    lens = [min(max(int(L), 0), cap) for L in case.lens]
+    bkv = len(lens)
+    rng = np.random.default_rng(case.seed + 991)
+    Q = rng.uniform(-2, 2, (bkv * g, d, nq)).astype(np.float16)
+    K = np.zeros((bkv, d, cap), np.float16)
+    V = np.zeros((bkv, vd, cap), np.float16)
+    Lq, kappa = lift_pair(d, abs(ramp.lift))
+    kinds, infos, bound = [], [], np.zeros((bkv * g, nq))
+    prob = O.Problem("full", 1, "none_front")
+    for s, L in enumerate(lens):
+        k64, v64 = np.zeros((d, cap)), np.zeros((vd, cap))
+        k64[2] = kappa
+        _past_fill(k64, v64, L, ramp, rng)
+        mask = case.mask(L) if L else None
+        for h in range(g):
+            bi = s * g + h
+            if L == 0:
+                Q[bi, 2] = np.float16(Lq)
+                kinds.append(np.full(nq, FLAT)); infos.append(None)
+                continue
+            (Qh, Kh, Vh, _), info = ramp_inputs(prob, np.float16, (1,), d, vd, (nq,), (L,), ramp, seed=case.seed + 100 * s + h,
+                                                mask=mask, row0=h * nq)
+            if h == 0:
+                k64[:, :L], v64[:, :L] = Kh[0], Vh[0]
+                K[s], V[s] = k64, v64
+            assert np.array_equal(Kh[0, :N_SPECIAL], K[s, :N_SPECIAL, :L])   # the special channels do not depend on the seed
+            Q[bi] = Qh[0]
+            kinds.append(info["kind"]); infos.append(info)
+            bound[bi] = m_rounding_bound(Qh, K[s:s + 1, :, :L], info, np.float16, d)[0]
+        if L == 0:
+            K[s], V[s] = k64, v64
+    if case.lift < 0:
+        Q[:, 2] = -Q[:, 2]
+    return dict(Q=Q, K=K, V=V, lens=lens, kinds=kinds, infos=infos, bound=bound)
+
+
+def decode_chunk_model(case, made):
+    """The rebase model per (Q slice, chunk): every chunk seeds afresh from its first tile.  Returns a list of
+    dicts (s, h, c, rebased [nq, tiles], active, kind, last: the chunk holds the slice's ragged last tile) and the
+    merge weights [(s, h, q, [float32 weight of every chunk that holds a key of the row])]."""
+    chunks, chunk, _ = case.plan
+    out, weights = [], []
+    for bi, info in enumerate(made["infos"]):
+        s, h = divmod(bi, case.g)
+        L = made["lens"][s]
+        if info is None:
+            continue
+        scores = kernel_scores(made["Q"][bi][None], made["K"][s][None, :, :L], case.d, True)
+        mask = info["mask"]
+        cmax = []
+        for c in range(chunks):
+            k0, k1 = c * chunk, min((c + 1) * chunk, L)
+            if k0 >= L:
+                break
+            rebased, active = rebase_tiles(scores[:, k0:k1], mask[:, k0:k1], DECODE_TILE, DECODE_THR)
+            out.append(dict(s=s, h=h, c=c, rebased=rebased, active=active, kind=info["kind"],
+                            last=(k1 == L and L % DECODE_TILE != 0)))
+            cmax.append(np.where(mask[:, k0:k1], scores[:, k0:k1], -np.inf).max(axis=1))
+        cmax = np.stack(cmax, axis=1)                               # [nq, live chunks]
+        for q in np.nonzero(info["has"])[0]:
+            live = np.isfinite(cmax[q])
+            weights.append((s, h, int(q), np.exp2(cmax[q, live] - cmax[q, live].max()).astype(np.float32)))
+    return out, weights
+
+
+def decode_conditions(case, made):
+    """The conditions a decode case must meet (tests/test_decode_score_ramp_inputs.py), as a dict of booleans."""
+    per_chunk, weights = decode_chunk_model(case, made)
+    _, _, pitch = case.plan
+    cond = dict(consecutive=False, last=False, quiet=False, others_still=True, n=0, waves_hold_a_still_row=True,
+                fired_waves=0, idle=False)
+    fired = {}                                                       # (s, c) -> bool [g * pitch]: the row rebased
+    still = {}                                                       # (s, c) -> bool [g * pitch]: must not move
+    for r in per_chunk:
+        c = rebase_conditions(r["rebased"], r["active"], r["kind"])
+        cond["consecutive"] |= c["consecutive"]
+        cond["quiet"] |= c["quiet"]
+        cond["last"] |= c["last"] and r["last"]
+        cond["others_still"] &= c["others_still"]
+        cond["n"] += c["n"]
+        key = (r["s"], r["c"])
+        f = fired.setdefault(key, np.zeros(case.g * pitch, bool))
+        st = still.setdefault(key, np.ones(case.g * pitch, bool))  # padding rows and the rows of absent heads stay
+        rows = r["h"] * pitch + np.arange(case.nq)
+        f[rows] = r["rebased"].any(axis=1)
+        st[rows] = (r["kind"] != CLIMB) | ~r["active"].any(axis=1)
+        # a row without an allowed key in a tile on which a wave-mate rebases (never seeded, or the tile is masked)
+        for w in range(0, case.nq, 32) if pitch > 32 else [0]:
+            rows_w = slice(w, w + 32) if pitch > 32 else slice(0, case.nq)
+            tiles = r["rebased"][rows_w].any(axis=0)
+            cond["idle"] |= bool((~r["active"][rows_w][:, tiles]).any())
+    for key, f in fired.items():
+        assert not (f & still[key]).any()
+        for w in range(0, case.g * pitch, 32):
+            if f[w:w + 32].any():
+                cond["fired_waves"] += 1
+                cond["waves_hold_a_still_row"] &= bool(still[key][w:w + 32].any())
+    ws = np.concatenate([w[3] for w in weights if w[3].size >= 2] or [np.ones(1, np.float32)])
+    cond["merge_zero"] = bool((ws == 0).any())
+    cond["merge_between"] = bool(((ws > 0) & (ws < 1)).any())
+    return cond
+
+
+def emulate_ragged_f16(Q, K, V, kv_lens, g, tail):
+    """emulate_f16's forward over the ragged rule: (O fp16 [b, v_d, nq], l f32 [b, nq], m fp16 [b, nq]) with the
+    documented roundings and, for the rows without a key, O = 0, l = 0 and m = bytes 0xFA as the kernels store."""
+    from tests import ragged_ref
+    b, d, nq = Q.shape
+    vd, cap = V.shape[1], V.shape[2]
+    c2 = np.float32(np.float32(1.0 / math.sqrt(d)) * np.float32(LOG2E))
+    o = np.zeros((b, vd, nq), np.float16)
+    l = np.zeros((b, nq), np.float32)
+    m = np.full((b, nq), 0xFAFA, np.uint16).view(np.float16)
+    for i in range(b):
+        L = min(max(int(kv_lens[i // g]), 0), cap)
+        mask = ragged_ref.ragged_mask(nq, cap, L, tail)[:, :L]
+        has = mask.any(axis=1)
+        if not has.any():
+            continue
+        qs16 = (Q[i].astype(np.float32) * c2).astype(np.float16).astype(np.float64)
+        k, v = K[i // g][:, :L].astype(np.float64), V[i // g][:, :L].astype(np.float64)
+        s2 = np.where(mask, qs16.T @ k, -np.inf)
+        m2 = np.where(has, s2.max(axis=1), 0.0)
+        p16 = np.exp2(s2 - m2[:, None]).astype(np.float16).astype(np.float64)
+        l_run = np.where(has, p16.sum(axis=1), 1.0)
+        o16 = ((v @ p16.T) / l_run).astype(np.float16)
+        m16 = (m2 / LOG2E).astype(np.float16)
+        l32 = (l_run * np.exp2(m2 - m16.astype(np.float64) * LOG2E)).astype(np.float32)
+        o[i][:, has], l[i][has], m[i][has] = o16[:, has], l32[has], m16[has]
+    return o, l, m
+
+
+# The decode cases.  Plateaus of one 64-key tile.  Chunks are 512 keys up to 64 folded rows and 1024 above (g = 2,
+# nq = 33: pitch 64, 128 rows), so three chunks need a capacity past 1024 / 2048 keys.  Each case holds, in ONE call:
+#   c2 + 148  a length that ends mid-tile with three live tiles in the last chunk (e = 2, 1, 0: the seed, a quiet 2σ0
+#             step and the ragged last tile's σ0 step, which rebases because 3σ0 has accumulated); in the chunk before
+#             it every tile after the first steps by >= 4σ0 (consecutive rebases), and chunk 0 is one level (quiet);
+#   c2        a length exactly on the edge of chunk 2;
+#   c2 + 1    one key past it: the top plateau's only key sits alone in its chunk, chunk 1 ends σ0 under it (a merge
+#             weight strictly between 0 and 1) and chunk 0 more than 500σ0 (weight exactly 0 in fp32);
+#   40        under one tile;   0  no key;   and under the tail rule
+#   nq - 1    row 0 never seeds while the seed tile moves its wave-mates' m_run by the lift (a row without any key has
+#             L - nq + i < 0, so a wave-mate within 32 rows tops out below key 32: no later tile can rebase beside it);
+#   c2 + 132  only the last four queries see the last tile's four keys; the climb rows among them rebase there (3σ0
+#             accumulated) while that tile is masked for the other rows of their wave ("idle": asserted for the tail
+#             cases; under the full form every row of a slice sees every live key).
+# (c2 = 2 * chunk.)
+def _d(id, entry, d, vd, g, nq, cap, tail=False, lens=None, **kw):
+    chunk = decode_plan(nq, cap, g)[1]
+    if lens is None:
+        lens = (2 * chunk + 148, 2 * chunk, 2 * chunk + 1, 40, 0) + ((nq - 1, 2 * chunk + 132) if tail else ())
+    return DecodeCase(id, entry, d, vd, g, nq, cap, tuple(lens), tail, **kw)
+
+
+DECODE_CASES = [
+    # ---- fa_forward_ragged, full form, 16-byte staging (ragged_partial_kernel<D, 0, true> + ragged_merge_kernel);
+    # the d = 64 case runs through fa_forward_paged as well (paged_partial_kernel, pages of 64 and 192 keys)
+    _d("ragged-d64-g4q4-full", "ragged", 64, 64, 4, 4, 1344, pages=(64, 192)),
+    _d("ragged-d128-g2q33-full", "ragged", 128, 128, 2, 33, 2568),     # pitch 64: a wave holds a run of one head's queries
+    _d("ragged-d32-g8q1-full", "ragged", 32, 32, 8, 1, 1336),         # decode: eight heads side by side in one wave
+    # ---- element-wise staging (capacity % 8 != 0, d != v_d): ragged_partial_kernel<128, 0, false>
+    _d("ragged-d96v40-g3q3-elem", "ragged", 96, 40, 3, 3, 1341),
+    # ---- tail-causal: ragged_partial_kernel<D, 1, .> through RaggedRows::lane_interval
+    _d("ragged-d64-g2q16-tail", "ragged", 64, 64, 2, 16, 1344, tail=True, pages=(64, 192)),
+    _d("ragged-d128-g1q33-tail", "ragged", 128, 128, 1, 33, 1336, tail=True),
+    # the doubled σ0 where the rows' tops differ: at c2 + 1, + 65 and + 129 the window of the last 16 keys lies across
+    # a plateau edge, so rows 0 .. 14 top out one plateau (2σ0 > 8: a rebase of their own) below row 15.  The last
+    # tile's step alone (σ0 <= 8) never fires, and every row sees the tile before it: "idle" waived.  Capacity % 8 != 0:
+    # the tail rule with element-wise staging at d = v_d = 64
+    _d("ragged-d64-g2q16-tail-big", "ragged", 64, 64, 2, 16, 1341, tail=True, big=True,
+       lens=(1025, 1089, 1153, 1172, 1024, 40, 0, 15), waive=("idle",)),
+    # 128 queries of one head, plateaus of 16 keys: L = 127 leaves row 0 without a key and rows 1 .. 64 without one in
+    # the second tile while the rows past 64 step up by 15σ0 there.  One chunk: nothing to merge, no quiet stretch
+    DecodeCase("ragged-d64-g1q128-tail-w16", "ragged", 64, 64, 1, 128, 1344, (127, 128, 0), True, W=16,
+               waive=("consecutive", "quiet", "merge")),
+    # ---- the lift negated: every score lies far below m_run's initial 0, the seed moves down, the stored m is negative
+    _d("ragged-d64-g4q4-full-neglift", "ragged", 64, 64, 4, 4, 1344, lift=-24.0),
+    # ---- fa_forward_grouped (gqa_partial_kernel + gqa_merge_kernel): every slice has the capacity, c2 + 136 / + 141
+    # keys.  nq = 7 and 3: under the causal rule only the last query reaches the ragged last tile, and folded row
+    # 0 * nq + nq - 1 is then a climb row
+    _d("grouped-d128-g4q7-full", "grouped", 128, 128, 4, 7, 1160, lens=(1160, 1160)),
+    _d("grouped-d128-g4q7-causal", "grouped", 128, 128, 4, 7, 1160, tail=True, lens=(1160, 1160)),
+    _d("grouped-d32-g8q3-full-elem", "grouped", 32, 32, 8, 3, 1165, lens=(1165, 1165)),
+    _d("grouped-d32-g8q3-causal-elem", "grouped", 32, 32, 8, 3, 1165, tail=True, lens=(1165, 1165)),
+]
+DECODE_CASE_BY_ID = {c.id: c for c in DECODE_CASES}

@@ -101,10 +101,12 @@ def _check_full_by_run_case(monkeypatch, got, Q, K, V, kv_lens, g):
         print(f"L = {L}: {len(sub)} slices, O max err / scale {res['O']:.3e}")
 
 
-def _check_ref(got, Q, K, V, kv_lens, g, tail):
+def _check_ref(got, Q, K, V, kv_lens, g, tail, m_bound=None):
     """Against tests/ragged_ref.py under run_case's fp16 forward rule: O and l within TOL[float16]['fwd'] (l
     relative to the stored m), m within 2 ulp plus the larger of 1e-3 * max(|m|, 1) and the rounding a score can
-    carry from the fp16 pre-scaled Q, (2^-11 + d 2^-24) * max_j sum_c |q_c k_jc| / sqrt(d) + 4.9e-4."""
+    carry from the fp16 pre-scaled Q, (2^-11 + d 2^-24) * max_j sum_c |q_c k_jc| / sqrt(d) + 4.9e-4.  m_bound
+    (optional, [b, nq]) replaces that dot-product term only, as run_case(m_bound=...) does (gate.m_tol_bounded).
+    Returns the worst |error| / allowance of O, l and m (for the records of a sweep; every check is an assertion)."""
     O64, L64, M64, ha = ragged_ref.forward_f64(Q, K, V, kv_lens, g, tail)
     o, l, m = (t.cpu().numpy() for t in got)
     b, d, nq = Q.shape
@@ -114,17 +116,25 @@ def _check_ref(got, Q, K, V, kv_lens, g, tail):
     live = ha[:, None, :] & np.ones_like(O64, bool)
     parity._close("O", np.where(live, o, 0.0), O64, rtol, atol)
     assert np.isfinite(o.astype(np.float64)).all()
+    res = {"O": float((np.abs(np.where(live, o, 0.0) - O64) / gate.plain_bound(O64, rtol, atol)).max())}
     if not ha.any():
-        return
-    rowdot = np.zeros((b, nq))
-    for bi in range(b):
-        mask = ragged_ref.ragged_mask(nq, cap, kv_lens[bi // g], tail)
-        rowdot[bi] = gate.max_abs_dot(Q[bi][None], K[bi // g][None], mask)[0] / math.sqrt(d)
+        return res
     m_f, M = m.astype(np.float64)[ha], M64[ha]
-    ulp = np.abs(np.spacing(np.abs(M).astype(np.float16))).astype(np.float64)
-    m_tol = 2 * ulp + np.maximum(1e-3 * np.maximum(np.abs(M), 1.0), (2.0 ** -11 + d * 2.0 ** -24) * rowdot[ha] + 4.9e-4)
+    if m_bound is None:
+        rowdot = np.zeros((b, nq))
+        for bi in range(b):
+            mask = ragged_ref.ragged_mask(nq, cap, kv_lens[bi // g], tail)
+            rowdot[bi] = gate.max_abs_dot(Q[bi][None], K[bi // g][None], mask)[0] / math.sqrt(d)
+        ulp = np.abs(np.spacing(np.abs(M).astype(np.float16))).astype(np.float64)
+        m_tol = 2 * ulp + np.maximum(1e-3 * np.maximum(np.abs(M), 1.0), (2.0 ** -11 + d * 2.0 ** -24) * rowdot[ha] + 4.9e-4)
+    else:
+        m_tol = gate.m_tol_bounded(M, np.float16, np.asarray(m_bound, dtype=np.float64)[ha])
     assert (np.abs(m_f - M) <= m_tol).all(), f"m: max err {np.abs(m_f - M).max():.3e}"
-    parity._close("l", l.astype(np.float64)[ha], L64[ha] * np.exp(M - m_f), max(rtol, 1e-6), atol)
+    l_ref = L64[ha] * np.exp(M - m_f)
+    parity._close("l", l.astype(np.float64)[ha], l_ref, max(rtol, 1e-6), atol)
+    res["m"] = float((np.abs(m_f - M) / m_tol).max())
+    res["l"] = float((np.abs(l.astype(np.float64)[ha] - l_ref) / gate.plain_bound(l_ref, max(rtol, 1e-6), atol)).max())
+    return res
 
 
 # ------------------------------------------------------------------ tile, chunk and 16-byte edges
