@@ -212,8 +212,8 @@ SplitPlan split_plan(const fa_problem* p) {
 }
 
 size_t split_ws_bytes(const fa_problem* p, const SplitPlan& s) {
-  const size_t nq = (size_t)seq_elems(p->q_seq, p->seq_dims);
-  return align_up((size_t)p->b * (size_t)s.nchunks * nq * (size_t)(p->v_d + 3) * sizeof(float));
+  const int64_t nq = seq_elems(p->q_seq, p->seq_dims);
+  return align_up((size_t)p->b * (size_t)s.nchunks * (size_t)fa::fewq_record_floats(p->v_d, nq) * sizeof(float));
 }
 
 // Grouped-query routing of the fp16 forward: kv_group query slices share a K/V slice and
@@ -222,12 +222,12 @@ size_t split_ws_bytes(const fa_problem* p, const SplitPlan& s) {
 // range: the partial + merge pair is the only grouped path, so a short range is one chunk.
 constexpr int32_t kGroupMaxRows = 128;     // the folded rows of one workgroup
 
-struct GroupedPlan {
-  int32_t nchunks, chunk, kb, ke, k_first, pitch, rows;
+struct GroupedPlan : SplitPlan {
+  int32_t pitch, rows;
 };
 
 GroupedPlan grouped_plan(const fa_problem* p, int32_t kv_group, int32_t min_group = 2) {
-  GroupedPlan s = {0, 0, 0, 0, 0, 0, 0};
+  GroupedPlan s = {};
   if (fa_validate(p) != FA_OK || kv_group < 1) return s;
   const int64_t nq = seq_elems(p->q_seq, p->seq_dims);
   if (nq >= 1) {  // (validated: nq <= 2^30)
@@ -254,7 +254,7 @@ GroupedPlan grouped_plan(const fa_problem* p, int32_t kv_group, int32_t min_grou
 }
 
 size_t grouped_ws_bytes(const fa_problem* p, int32_t kv_group, const GroupedPlan& s) {
-  return align_up((size_t)(p->b / kv_group) * (size_t)s.nchunks * (size_t)s.rows * (size_t)(p->v_d + 3) * sizeof(float));
+  return align_up((size_t)(p->b / kv_group) * (size_t)s.nchunks * (size_t)fa::fewq_record_floats(p->v_d, s.rows) * sizeof(float));
 }
 
 int check_group(const fa_problem* p, int32_t kv_group) {
@@ -372,6 +372,128 @@ size_t bwd_qsplit_part_bytes(const fa_problem* p, const QSplitPlan& s) {
   return align_up((size_t)p->b * (size_t)s.nchunks * (size_t)(p->d + p->v_d) * nk * sizeof(float));
 }
 
+// ---- what the entry points below share
+
+// b, d, v_d, the scale and the rule of a problem (FwdArgs or BwdArgs; the pointers are the caller's)
+template <class Args>
+void fill_problem(const fa_problem* p, Args* a) {
+  a->b = p->b; a->d = p->d; a->v_d = p->v_d;
+  a->scale = 1.0 / sqrt((double)p->d);
+  build_rule(p, &a->rule);
+}
+
+// the problem and a plan's chunks as the few-query kernels take them
+void fill_split(const fa_problem* p, const SplitPlan& sp, fa::SplitArgs* sa) {
+  fill_problem(p, &sa->f);
+  sa->nchunks = sp.nchunks; sa->chunk = sp.chunk; sa->k_first = sp.k_first; sa->k_end = sp.ke;
+}
+
+void fill_grouped(const fa_problem* p, const GroupedPlan& gp, int32_t kv_group, fa::GqaArgs* ga) {
+  fill_split(p, gp, &ga->s);
+  ga->g = kv_group; ga->pitch = gp.pitch; ga->log2_pitch = ilog2(gp.pitch);
+}
+
+// (the lengths bound the keys: the chunks start at key 0; len0 / rem0 are set per launch)
+void fill_ragged(const fa_problem* p, const GroupedPlan& gp, int32_t kv_group, const int32_t* k_lens, int32_t kv_per_len,
+                 int32_t tail_causal, fa::RaggedArgs* ra) {
+  fill_grouped(p, gp, kv_group, &ra->g);
+  ra->g.s.k_first = 0;
+  ra->k_lens = k_lens; ra->kv_per_len = kv_per_len; ra->tail_causal = tail_causal != 0;
+}
+
+// the four leading fields every plan export has; the grouped plans add the fold
+void write_plan(int32_t out[4], int32_t nchunks, int32_t chunk, int32_t first, int32_t end) {
+  out[0] = nchunks;
+  out[1] = chunk;
+  out[2] = first;
+  out[3] = end;
+}
+void write_plan(int32_t out[4], const SplitPlan& s) { write_plan(out, s.nchunks, s.chunk, s.kb, s.ke); }
+void write_plan(int32_t out[6], const GroupedPlan& s) {
+  write_plan(out, static_cast<const SplitPlan&>(s));
+  out[4] = s.pitch;
+  out[5] = s.rows;
+}
+
+int check_kv_per_len(int64_t bkv, int32_t kv_per_len) {
+  if (kv_per_len < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "kv_per_len must be >= 1");
+  if (bkv % kv_per_len != 0)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "the number of K/V slices b / kv_group = " + std::to_string(bkv) +
+                                                  " is not a multiple of kv_per_len = " + std::to_string(kv_per_len));
+  return FA_OK;
+}
+
+// A few-query forward call's pointers.  K and V null: not sliced per launch (the paged pools, set by the caller).
+struct FewqPtrs {
+  const void *Q, *K, *V;
+  void *O, *l, *m, *workspace;
+};
+
+// The launches of a few-query forward over the p->b / g K/V slices, g query slices each, in slabs of at most
+// fwd_f16_fewq_max_batch slices: one launch pair covers every realistic batch; the loop only keeps the grids
+// inside 2^31 blocks.  Sets b, the slab's pointers and the workspace (records of `rows` floats a row) in *sa,
+// which lies inside the arguments that launch(b0) sends; b0 is the slab's first K/V slice.
+template <class Launch>
+int fewq_slabs(const fa_problem* p, const FewqPtrs& t, int32_t g, int64_t rows, fa::SplitArgs* sa, Launch&& launch) {
+  fa::FwdArgs& a = sa->f;
+  const int64_t nq = a.rule.q.n, nk = a.rule.k.n, bkv = p->b / g;
+  const int64_t bmax = fa::fwd_f16_fewq_max_batch(sa->nchunks, p->v_d, g * nq);
+  for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {
+    a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
+    a.Q = static_cast<const uint16_t*>(t.Q) + b0 * g * p->d * nq;
+    if (t.K) a.K = static_cast<const uint16_t*>(t.K) + b0 * p->d * nk;
+    if (t.V) a.V = static_cast<const uint16_t*>(t.V) + b0 * p->v_d * nk;
+    a.O = static_cast<uint16_t*>(t.O) + b0 * g * p->v_d * nq;
+    a.l = static_cast<float*>(t.l) + b0 * g * nq;
+    a.m = static_cast<uint16_t*>(t.m) + b0 * g * nq;
+    sa->ws = static_cast<float*>(t.workspace) + b0 * sa->nchunks * fa::fewq_record_floats(p->v_d, rows);
+    const hipError_t e = launch(b0);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
+// the problem, a backward call's pointers and the regions of its workspace
+void fill_bwd(const fa_problem* p, const WsLayout& w, const void* Q, const void* K, const void* V, const void* O,
+              const void* l, const void* m, const void* dO, void* dQ, void* dK, void* dV, void* workspace, fa::BwdArgs* a) {
+  a->Q = Q; a->K = K; a->V = V; a->O = O; a->l = l; a->m = m; a->dO = dO;
+  a->dQ = dQ; a->dK = dK; a->dV = dV;
+  char* ws = static_cast<char*>(workspace);
+  a->ws_dQ = ws + w.dq;
+  a->ws_D = ws + w.D;
+  a->ws_lse = ws + w.lse;
+  fill_problem(p, a);
+}
+
+// The launches of a split fp16 backward in slabs of at most bmax slices (grid limits, as above): *a receives
+// `whole`, the whole call's arguments, advanced to the slab; launch(b0) sets its partials and sends them.
+template <class Launch>
+int bwd_slabs(const fa_problem* p, const fa::BwdArgs& whole, int64_t bmax, fa::BwdArgs* a, Launch&& launch) {
+  const int64_t nq = whole.rule.q.n, nk = whole.rule.k.n;
+  for (int64_t b0 = 0; b0 < p->b; b0 += bmax) {
+    *a = whole;
+    a->b = p->b - b0 < bmax ? p->b - b0 : bmax;
+    a->Q = static_cast<const uint16_t*>(whole.Q) + b0 * p->d * nq;
+    a->K = static_cast<const uint16_t*>(whole.K) + b0 * p->d * nk;
+    a->V = static_cast<const uint16_t*>(whole.V) + b0 * p->v_d * nk;
+    a->O = static_cast<const uint16_t*>(whole.O) + b0 * p->v_d * nq;
+    a->l = static_cast<const float*>(whole.l) + b0 * nq;
+    a->m = static_cast<const uint16_t*>(whole.m) + b0 * nq;
+    a->dO = static_cast<const uint16_t*>(whole.dO) + b0 * p->v_d * nq;
+    a->dQ = static_cast<uint16_t*>(whole.dQ) + b0 * p->d * nq;
+    a->dK = static_cast<uint16_t*>(whole.dK) + b0 * p->d * nk;
+    a->dV = static_cast<uint16_t*>(whole.dV) + b0 * p->v_d * nk;
+    // (ws_dQ stays: the two-pass kernels keep no dQ accumulator)
+    a->ws_D = static_cast<float*>(whole.ws_D) + b0 * nq;
+    a->ws_lse = static_cast<float*>(whole.ws_lse) + b0 * nq;
+    const hipError_t e = launch(b0);
+    if (e != hipSuccess)
+      return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
+  }
+  return FA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -432,9 +554,7 @@ int fa_forward(void* stream, const fa_problem* p, const void* Q, const void* K, 
   FA_DIAG_COUNT(0);
   fa::FwdArgs a;
   a.Q = Q; a.K = K; a.V = V; a.O = O; a.l = l; a.m = m;
-  a.b = p->b; a.d = p->d; a.v_d = p->v_d;
-  a.scale = 1.0 / sqrt((double)p->d);
-  build_rule(p, &a.rule);
+  fill_problem(p, &a);
   if (a.b == 0 || a.rule.q.n == 0) return FA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e;
@@ -463,11 +583,7 @@ int fa_forward_split_plan(const fa_problem* p, int32_t out[4]) {
   int st = fa_validate(p);
   if (st != FA_OK) return st;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  const SplitPlan s = split_plan(p);
-  out[0] = s.nchunks;
-  out[1] = s.chunk;
-  out[2] = s.kb;
-  out[3] = s.ke;
+  write_plan(out, split_plan(p));
   return FA_OK;
 }
 
@@ -480,42 +596,17 @@ int fa_forward_ws(void* stream, const fa_problem* p, const void* Q, const void* 
   FA_DIAG_COUNT(0);
   if (p->b == 0) return FA_OK;
   fa::SplitArgs sa;
-  fa::FwdArgs& a = sa.f;
-  a.d = p->d; a.v_d = p->v_d;
-  a.scale = 1.0 / sqrt((double)p->d);
-  build_rule(p, &a.rule);
-  sa.nchunks = sp.nchunks; sa.chunk = sp.chunk; sa.k_first = sp.k_first; sa.k_end = sp.ke;
-  const int64_t nq = a.rule.q.n, nk = a.rule.k.n;
+  fill_split(p, sp, &sa);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // one launch pair covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
-  const int64_t bmax = fa::fwd_f16_splitk_max_batch(sa);
-  for (int64_t b0 = 0; b0 < p->b; b0 += bmax) {
-    a.b = p->b - b0 < bmax ? p->b - b0 : bmax;
-    a.Q = static_cast<const uint16_t*>(Q) + b0 * p->d * nq;
-    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
-    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
-    a.O = static_cast<uint16_t*>(O) + b0 * p->v_d * nq;
-    a.l = static_cast<float*>(l) + b0 * nq;
-    a.m = static_cast<uint16_t*>(m) + b0 * nq;
-    sa.ws = static_cast<float*>(workspace) + b0 * sp.nchunks * (p->v_d + 3) * nq;
-    const hipError_t e = fa::launch_fwd_f16_splitk(sa, s);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
-  }
-  return FA_OK;
+  return fewq_slabs(p, {Q, K, V, O, l, m, workspace}, 1, sa.f.rule.q.n, &sa,
+                    [&](int64_t) { return fa::launch_fwd_f16_splitk(sa, s); });
 }
 
 int fa_forward_grouped_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]) {
   const int st = check_group(p, kv_group);
   if (st != FA_OK) return st;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  const GroupedPlan s = grouped_plan(p, kv_group);
-  out[0] = s.nchunks;
-  out[1] = s.chunk;
-  out[2] = s.kb;
-  out[3] = s.ke;
-  out[4] = s.pitch;
-  out[5] = s.rows;
+  write_plan(out, grouped_plan(p, kv_group));
   return FA_OK;
 }
 
@@ -542,44 +633,17 @@ int fa_forward_grouped(void* stream, const fa_problem* p, int32_t kv_group, cons
   FA_DIAG_COUNT(0);
   if (p->b == 0) return FA_OK;
   fa::GqaArgs ga;
-  fa::SplitArgs& sa = ga.s;
-  fa::FwdArgs& a = sa.f;
-  a.d = p->d; a.v_d = p->v_d;
-  a.scale = 1.0 / sqrt((double)p->d);
-  build_rule(p, &a.rule);
-  sa.nchunks = gp.nchunks; sa.chunk = gp.chunk; sa.k_first = gp.k_first; sa.k_end = gp.ke;
-  ga.g = kv_group; ga.pitch = gp.pitch; ga.log2_pitch = ilog2(gp.pitch);
-  const int64_t nq = a.rule.q.n, nk = a.rule.k.n, bkv = p->b / kv_group;
+  fill_grouped(p, gp, kv_group, &ga);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // one launch pair covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
-  const int64_t bmax = fa::fwd_f16_gqa_max_batch(ga);
-  for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {  // b0 counts K/V slices
-    a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
-    a.Q = static_cast<const uint16_t*>(Q) + b0 * kv_group * p->d * nq;
-    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
-    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
-    a.O = static_cast<uint16_t*>(O) + b0 * kv_group * p->v_d * nq;
-    a.l = static_cast<float*>(l) + b0 * kv_group * nq;
-    a.m = static_cast<uint16_t*>(m) + b0 * kv_group * nq;
-    sa.ws = static_cast<float*>(workspace) + b0 * gp.nchunks * (p->v_d + 3) * gp.rows;
-    const hipError_t e = fa::launch_fwd_f16_gqa(ga, s);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
-  }
-  return FA_OK;
+  return fewq_slabs(p, {Q, K, V, O, l, m, workspace}, kv_group, gp.rows, &ga.s,
+                    [&](int64_t) { return fa::launch_fwd_f16_gqa(ga, s); });
 }
 
 int fa_forward_ragged_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]) {
   const int st = check_ragged(p, kv_group);
   if (st != FA_OK) return st;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  const GroupedPlan s = ragged_plan(p, kv_group);
-  out[0] = s.nchunks;
-  out[1] = s.chunk;
-  out[2] = s.kb;
-  out[3] = s.ke;
-  out[4] = s.pitch;
-  out[5] = s.rows;
+  write_plan(out, ragged_plan(p, kv_group));
   return FA_OK;
 }
 
@@ -594,11 +658,8 @@ int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const
                       void* workspace, size_t workspace_bytes) {
   const int st = check_ragged(p, kv_group);
   if (st != FA_OK) return st;
-  const int64_t bkv = p->b / kv_group;
-  if (kv_per_len < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "kv_per_len must be >= 1");
-  if (bkv % kv_per_len != 0)
-    return set_error(FA_ERR_INVALID_ARGUMENT, "the number of K/V slices b / kv_group = " + std::to_string(bkv) +
-                                                  " is not a multiple of kv_per_len = " + std::to_string(kv_per_len));
+  const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
+  if (kst != FA_OK) return kst;
   const GroupedPlan gp = ragged_plan(p, kv_group);
   if (gp.nchunks == 0)
     return set_error(FA_ERR_UNSUPPORTED,
@@ -611,47 +672,19 @@ int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const
   if (p->b == 0) return FA_OK;
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
   fa::RaggedArgs ra;
-  fa::GqaArgs& ga = ra.g;
-  fa::SplitArgs& sa = ga.s;
-  fa::FwdArgs& a = sa.f;
-  a.d = p->d; a.v_d = p->v_d;
-  a.scale = 1.0 / sqrt((double)p->d);
-  build_rule(p, &a.rule);
-  sa.nchunks = gp.nchunks; sa.chunk = gp.chunk; sa.k_first = 0; sa.k_end = gp.ke;
-  ga.g = kv_group; ga.pitch = gp.pitch; ga.log2_pitch = ilog2(gp.pitch);
-  ra.k_lens = k_lens; ra.kv_per_len = kv_per_len; ra.tail_causal = tail_causal != 0;
-  const int64_t nq = a.rule.q.n, nk = a.rule.k.n;
+  fill_ragged(p, gp, kv_group, k_lens, kv_per_len, tail_causal, &ra);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // one launch pair covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
-  const int64_t bmax = fa::fwd_f16_gqa_max_batch(ga);
-  for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {  // b0 counts K/V slices
-    a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
-    a.Q = static_cast<const uint16_t*>(Q) + b0 * kv_group * p->d * nq;
-    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
-    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
-    a.O = static_cast<uint16_t*>(O) + b0 * kv_group * p->v_d * nq;
-    a.l = static_cast<float*>(l) + b0 * kv_group * nq;
-    a.m = static_cast<uint16_t*>(m) + b0 * kv_group * nq;
-    sa.ws = static_cast<float*>(workspace) + b0 * gp.nchunks * (p->v_d + 3) * gp.rows;
+  return fewq_slabs(p, {Q, K, V, O, l, m, workspace}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
-    const hipError_t e = fa::launch_fwd_f16_ragged(ra, s);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
-  }
-  return FA_OK;
+    return fa::launch_fwd_f16_ragged(ra, s);
+  });
 }
 
 int fa_forward_paged_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]) {
   const int st = check_paged(p, kv_group, page);
   if (st != FA_OK) return st;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  const GroupedPlan s = paged_plan(p, kv_group, page);
-  out[0] = s.nchunks;
-  out[1] = s.chunk;
-  out[2] = s.kb;
-  out[3] = s.ke;
-  out[4] = s.pitch;
-  out[5] = s.rows;
+  write_plan(out, paged_plan(p, kv_group, page));
   return FA_OK;
 }
 
@@ -667,11 +700,8 @@ int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const 
                      void* workspace, size_t workspace_bytes) {
   const int st = check_paged(p, kv_group, page);
   if (st != FA_OK) return st;
-  const int64_t bkv = p->b / kv_group;
-  if (kv_per_len < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "kv_per_len must be >= 1");
-  if (bkv % kv_per_len != 0)
-    return set_error(FA_ERR_INVALID_ARGUMENT, "the number of K/V slices b / kv_group = " + std::to_string(bkv) +
-                                                  " is not a multiple of kv_per_len = " + std::to_string(kv_per_len));
+  const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
+  if (kst != FA_OK) return kst;
   if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages must be >= 1");
   if ((int64_t)max_pages * page != p->k_seq[0])
     return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages * page = " + std::to_string((int64_t)max_pages * page) +
@@ -692,35 +722,15 @@ int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const 
   if (!K_pool || !V_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null K_pool or V_pool");
   fa::PagedArgs pa;
   fa::RaggedArgs& ra = pa.r;
-  fa::GqaArgs& ga = ra.g;
-  fa::SplitArgs& sa = ga.s;
-  fa::FwdArgs& a = sa.f;
-  a.d = p->d; a.v_d = p->v_d;
-  a.scale = 1.0 / sqrt((double)p->d);
-  build_rule(p, &a.rule);
-  sa.nchunks = gp.nchunks; sa.chunk = gp.chunk; sa.k_first = 0; sa.k_end = gp.ke;
-  ga.g = kv_group; ga.pitch = gp.pitch; ga.log2_pitch = ilog2(gp.pitch);
-  ra.k_lens = k_lens; ra.kv_per_len = kv_per_len; ra.tail_causal = tail_causal != 0;
+  fill_ragged(p, gp, kv_group, k_lens, kv_per_len, tail_causal, &ra);
   pa.block_table = block_table; pa.max_pages = max_pages; pa.page = page;
   pa.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
-  a.K = K_pool; a.V = V_pool;  // the pools are not sliced per launch: the table says where a slice's keys are
-  const int64_t nq = a.rule.q.n;
+  ra.g.s.f.K = K_pool; ra.g.s.f.V = V_pool;  // the pools are not sliced per launch: the table says where a slice's keys are
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // fa_forward_ragged's launches: one pair covers every realistic batch
-  const int64_t bmax = fa::fwd_f16_gqa_max_batch(ga);
-  for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {  // b0 counts K/V slices
-    a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
-    a.Q = static_cast<const uint16_t*>(Q) + b0 * kv_group * p->d * nq;
-    a.O = static_cast<uint16_t*>(O) + b0 * kv_group * p->v_d * nq;
-    a.l = static_cast<float*>(l) + b0 * kv_group * nq;
-    a.m = static_cast<uint16_t*>(m) + b0 * kv_group * nq;
-    sa.ws = static_cast<float*>(workspace) + b0 * gp.nchunks * (p->v_d + 3) * gp.rows;
+  return fewq_slabs(p, {Q, nullptr, nullptr, O, l, m, workspace}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
-    const hipError_t e = fa::launch_fwd_f16_paged(pa, s);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
-  }
-  return FA_OK;
+    return fa::launch_fwd_f16_paged(pa, s);
+  });
 }
 
 size_t fa_backward_workspace_bytes(const fa_problem* p) {
@@ -738,15 +748,7 @@ int fa_backward(void* stream, const fa_problem* p, const void* Q, const void* K,
     return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "backward workspace is smaller than fa_backward_workspace_bytes()");
   FA_DIAG_COUNT(1);
   fa::BwdArgs a;
-  a.Q = Q; a.K = K; a.V = V; a.O = O; a.l = l; a.m = m; a.dO = dO;
-  a.dQ = dQ; a.dK = dK; a.dV = dV;
-  char* ws = static_cast<char*>(workspace);
-  a.ws_dQ = ws + w.dq;
-  a.ws_D = ws + w.D;
-  a.ws_lse = ws + w.lse;
-  a.b = p->b; a.d = p->d; a.v_d = p->v_d;
-  a.scale = 1.0 / sqrt((double)p->d);
-  build_rule(p, &a.rule);
+  fill_bwd(p, w, Q, K, V, O, l, m, dO, dQ, dK, dV, workspace, &a);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.b == 0) return FA_OK;
   hipError_t e = hipSuccess;
@@ -776,11 +778,7 @@ int fa_backward_split_plan(const fa_problem* p, int32_t out[4]) {
   int st = fa_validate(p);
   if (st != FA_OK) return st;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  const SplitPlan s = bwd_split_plan(p);
-  out[0] = s.nchunks;
-  out[1] = s.chunk;
-  out[2] = s.kb;
-  out[3] = s.ke;
+  write_plan(out, bwd_split_plan(p));
   return FA_OK;
 }
 
@@ -789,10 +787,7 @@ int fa_backward_split_q_plan(const fa_problem* p, int32_t out[4]) {
   if (st != FA_OK) return st;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
   const QSplitPlan s = bwd_qsplit_plan(p);
-  out[0] = s.nchunks;
-  out[1] = s.chunk;
-  out[2] = s.qb;
-  out[3] = s.qe;
+  write_plan(out, s.nchunks, s.chunk, s.qb, s.qe);
   return FA_OK;
 }
 
@@ -816,37 +811,16 @@ int backward_split_q(void* stream, const fa_problem* p, const QSplitPlan& qp, co
   FA_DIAG_COUNT(1);
   if (p->b == 0) return FA_OK;
   fa::BwdQSplitArgs sa;
-  fa::BwdArgs& a = sa.b;
-  a.d = p->d; a.v_d = p->v_d;
-  a.scale = 1.0 / sqrt((double)p->d);
-  build_rule(p, &a.rule);
+  fa::BwdArgs whole;
+  fill_bwd(p, w, Q, K, V, O, l, m, dO, dQ, dK, dV, workspace, &whole);
+  sa.b = whole;  // (the batch limit below reads the problem)
   sa.nchunks = qp.nchunks; sa.chunk = qp.chunk; sa.q_first = qp.q_first; sa.q_end = qp.qe;
-  const int64_t nq = a.rule.q.n, nk = a.rule.k.n;
-  char* ws = static_cast<char*>(workspace);
+  float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + w.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // one call covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
-  const int64_t bmax = fa::bwd_f16_qsplit_max_batch(sa);
-  for (int64_t b0 = 0; b0 < p->b; b0 += bmax) {
-    a.b = p->b - b0 < bmax ? p->b - b0 : bmax;
-    a.Q = static_cast<const uint16_t*>(Q) + b0 * p->d * nq;
-    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
-    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
-    a.O = static_cast<const uint16_t*>(O) + b0 * p->v_d * nq;
-    a.l = static_cast<const float*>(l) + b0 * nq;
-    a.m = static_cast<const uint16_t*>(m) + b0 * nq;
-    a.dO = static_cast<const uint16_t*>(dO) + b0 * p->v_d * nq;
-    a.dQ = static_cast<uint16_t*>(dQ) + b0 * p->d * nq;
-    a.dK = static_cast<uint16_t*>(dK) + b0 * p->d * nk;
-    a.dV = static_cast<uint16_t*>(dV) + b0 * p->v_d * nk;
-    a.ws_dQ = ws + w.dq;  // (the two-pass kernels keep no dQ accumulator)
-    a.ws_D = reinterpret_cast<float*>(ws + w.D) + b0 * nq;
-    a.ws_lse = reinterpret_cast<float*>(ws + w.lse) + b0 * nq;
-    sa.ws_part = reinterpret_cast<float*>(ws + w.total) + b0 * qp.nchunks * (p->d + p->v_d) * nk;
-    const hipError_t e = fa::launch_bwd_f16_qsplit(sa, s);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
-  }
-  return FA_OK;
+  return bwd_slabs(p, whole, fa::bwd_f16_qsplit_max_batch(sa), &sa.b, [&](int64_t b0) {
+    sa.ws_part = part + b0 * qp.nchunks * (p->d + p->v_d) * whole.rule.k.n;
+    return fa::launch_bwd_f16_qsplit(sa, s);
+  });
 }
 
 }  // namespace
@@ -867,37 +841,16 @@ int fa_backward_split(void* stream, const fa_problem* p, const void* Q, const vo
   FA_DIAG_COUNT(1);
   if (p->b == 0) return FA_OK;
   fa::BwdSplitArgs sa;
-  fa::BwdArgs& a = sa.b;
-  a.d = p->d; a.v_d = p->v_d;
-  a.scale = 1.0 / sqrt((double)p->d);
-  build_rule(p, &a.rule);
+  fa::BwdArgs whole;
+  fill_bwd(p, w, Q, K, V, O, l, m, dO, dQ, dK, dV, workspace, &whole);
+  sa.b = whole;  // (the batch limit below reads the problem)
   sa.nchunks = sp.nchunks; sa.chunk = sp.chunk; sa.k_first = sp.k_first; sa.k_end = sp.ke;
-  const int64_t nq = a.rule.q.n, nk = a.rule.k.n;
-  char* ws = static_cast<char*>(workspace);
+  float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + w.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // one call covers every realistic batch; the loop only keeps the grids inside 2^31 blocks
-  const int64_t bmax = fa::bwd_f16_split_max_batch(sa);
-  for (int64_t b0 = 0; b0 < p->b; b0 += bmax) {
-    a.b = p->b - b0 < bmax ? p->b - b0 : bmax;
-    a.Q = static_cast<const uint16_t*>(Q) + b0 * p->d * nq;
-    a.K = static_cast<const uint16_t*>(K) + b0 * p->d * nk;
-    a.V = static_cast<const uint16_t*>(V) + b0 * p->v_d * nk;
-    a.O = static_cast<const uint16_t*>(O) + b0 * p->v_d * nq;
-    a.l = static_cast<const float*>(l) + b0 * nq;
-    a.m = static_cast<const uint16_t*>(m) + b0 * nq;
-    a.dO = static_cast<const uint16_t*>(dO) + b0 * p->v_d * nq;
-    a.dQ = static_cast<uint16_t*>(dQ) + b0 * p->d * nq;
-    a.dK = static_cast<uint16_t*>(dK) + b0 * p->d * nk;
-    a.dV = static_cast<uint16_t*>(dV) + b0 * p->v_d * nk;
-    a.ws_dQ = ws + w.dq;  // (the two-pass kernels keep no dQ accumulator)
-    a.ws_D = reinterpret_cast<float*>(ws + w.D) + b0 * nq;
-    a.ws_lse = reinterpret_cast<float*>(ws + w.lse) + b0 * nq;
-    sa.ws_part = reinterpret_cast<float*>(ws + w.total) + b0 * sp.nchunks * p->d * nq;
-    const hipError_t e = fa::launch_bwd_f16_split(sa, s);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
-  }
-  return FA_OK;
+  return bwd_slabs(p, whole, fa::bwd_f16_split_max_batch(sa), &sa.b, [&](int64_t b0) {
+    sa.ws_part = part + b0 * sp.nchunks * p->d * whole.rule.q.n;
+    return fa::launch_bwd_f16_split(sa, s);
+  });
 }
 
 int fa_merge_partials(void* stream, int32_t dtype, int64_t b, int64_t nq, int32_t v_d, int32_t n_parts,

@@ -15,6 +15,7 @@
 //     the device (the row maps' key_limit / lane_interval below);
 //   * paged_partial_kernel (fa_fwd_f16_paged.hip): the ragged block with each key tile read from a page pool
 //     through a device block table (the row maps' tile below).
+// The four partial kernels share what surrounds the core, and their merge, in fa_fwd_f16_fewq.h.
 // The structure:
 //   * Sᵀ = Kᵀ·Q and Oᵀ = V·Pᵀ on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
 //     Computing the TRANSPOSED scores puts the key index in the MFMA rows, so
@@ -118,6 +119,8 @@ struct WaveRegs {
 // (profiles/paged_core_asm_equal.txt).  A map with kPaged (fa_fwd_f16_paged.hip) is asked, tile(K, V, k0, ...):
 // it looks the tile's page up in a block table and answers a pointer into a page pool with the page as the
 // stride; a page is a multiple of the 64-key tile, so a tile never straddles two pages.
+// The core asks none of the next two; the few-query partial and merge kernels (fa_fwd_f16_fewq.h) do: whether
+// row rho of the block is a live query (row_live), and the floats per row of a partial record (rec_stride).
 struct IdentityRows {
   static constexpr bool kFolded = false;
   static constexpr bool kRagged = false;
@@ -130,6 +133,8 @@ struct IdentityRows {
   __device__ __forceinline__ bool wave_active(int wq0, int, int nq) const { return wq0 < nq; }
   __device__ __forceinline__ int lane_q(int wq0, int, int r) const { return wq0 + r; }
   __device__ __forceinline__ int lane_row(int qi, int, int) const { return qi; }
+  __device__ __forceinline__ bool row_live(int row, int nq) const { return row < nq; }
+  __device__ __forceinline__ int rec_stride(int nq) const { return nq; }
 };
 struct FoldedRows {
   static constexpr bool kFolded = true;
@@ -145,6 +150,8 @@ struct FoldedRows {
   __device__ __forceinline__ bool wave_active(int wq0, int w, int nq) const { return 32 * w < g * pitch && wq0 < nq; }
   __device__ __forceinline__ int lane_q(int, int w, int r) const { return (32 * w + r) & (pitch - 1); }
   __device__ __forceinline__ int lane_row(int, int w, int r) const { return 32 * w + r; }
+  __device__ __forceinline__ bool row_live(int rho, int nq) const { return rho < g * pitch && (rho & (pitch - 1)) < nq; }
+  __device__ __forceinline__ int rec_stride(int) const { return g * pitch; }
 };
 
 // What a wave holds after its last key tile.  acc_o and the row sum are relative to m_run, the
@@ -520,12 +527,19 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
 
 }
 
+// host: whether these arguments take the FAST staging at channel tile D, where K / V channel rows are `row_keys`
+// keys apart: every row then starts 16-byte aligned
+template <int D>
+bool fast_staging(const FwdArgs& a, int row_keys) {
+  return a.d == D && a.v_d == D && (row_keys % 8 == 0) && (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) &&
+         (reinterpret_cast<uintptr_t>(a.V) % 16 == 0);
+}
+
 // host: the <POL, FAST> instantiation these arguments take at channel tile D.  `launch(pol, fast)`
 // receives them as IC<POL> and IC<FAST> (types, so they can be template arguments).
 template <int D, class Launch>
 hipError_t with_pol_fast(const FwdArgs& a, Launch&& launch) {
-  const bool fast = a.d == D && a.v_d == D && (a.rule.k.n % 8 == 0) &&
-                    (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) && (reinterpret_cast<uintptr_t>(a.V) % 16 == 0);
+  const bool fast = fast_staging<D>(a, a.rule.k.n);
   const int pol = a.rule.policy == 0 ? 0 : (rule_is_interval(a.rule) ? 1 : 2);
   return pol == 0 ? (fast ? launch(IC<0>{}, IC<1>{}) : launch(IC<0>{}, IC<0>{}))
        : pol == 1 ? (fast ? launch(IC<1>{}, IC<1>{}) : launch(IC<1>{}, IC<0>{}))

@@ -6,7 +6,7 @@
 // the device: entry [s][p] is the pool page that holds keys [p*page, (p+1)*page) of all Hk heads of sequence s.
 // This is fa_fwd_f16_ragged.hip with that indirection: the same chunks over the capacity max_pages * page, the
 // same length handling (dead chunks return, staged K / V past the length are zeroed, key_limit = len), the same
-// partial records, and ragged_merge_kernel itself as the merge.  What differs is where a key tile is read from:
+// partial records (fa_fwd_f16_fewq.h), and ragged_merge_kernel itself as the merge.  What differs is where a key tile is read from:
 //   * page % 64 == 0, so a 64-key tile lies inside one page.  For tile k0 of (sequence s, head hk) PagedRows
 //     loads block_table[s * max_pages + k0 / page] as a wave-uniform value, clamps it to [0, num_pages - 1], and
 //     answers the core's tile() question with pool + ((entry * Hk + hk) * channels * page) + k0 % page and the
@@ -18,17 +18,14 @@
 //     pool.  The kernels only read the pools and the table; their stores are the partial records and (O, l, m).
 // With the pages of every sequence laid out in order this is the ragged forward tile for tile, and the results
 // are bitwise fa_forward_ragged's on the gathered cache.
-#include "fa_fwd_f16_ragged.h"
+#include "fa_fwd_f16_fewq.h"
 
 namespace fa {
 namespace {
 
 using namespace f16core;
 
-constexpr int kNW = 4;       // waves per workgroup: 128 folded rows
-constexpr int kF = kFDot2;   // the core's structure flags: fwd_f16_kernel's default form
-
-// RaggedRows plus the block table (fa_fwd_f16_core.h: the row maps).  K and V handed to tile() are the pools.
+// RaggedRows plus the block table (fa_fwd_f16_core.h: the row maps; fa_fwd_f16_fewq.h).  K and V handed to tile() are the pools.
 // The core asks for its tiles in ascending order, one per key-loop step, and the entry is a dependent load in
 // front of the tile's K / V loads; asked for on the spot it stalls the wave for a memory round trip per tile
 // (2 to 12 % over the ragged forward).  So tile() loads the entry of the NEXT tile's page, a whole
@@ -61,88 +58,39 @@ struct PagedRows : RaggedRows {
 };
 
 template <int D, int POL, bool FAST>
-__global__ __launch_bounds__(kNW * 64, waves_per_eu(D, kF)) void paged_partial_kernel(PagedArgs pa) {
+__global__ __launch_bounds__(kFewqNW * 64, waves_per_eu(D, kFewqF)) void paged_partial_kernel(PagedArgs pa) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const RaggedArgs& ra = pa.r;
   const GqaArgs& ga = ra.g;
   const SplitArgs& sa = ga.s;
   const FwdArgs& a = sa.f;
-  constexpr float kNegInf = -__builtin_huge_valf();
-
-  const int nq = a.rule.q.n, vd = FAST ? D : a.v_d;
-  const uint32_t bid = xcd_remap(blockIdx.x, gridDim.x);
-  const uint32_t bkv32 = bid / (uint32_t)sa.nchunks;
-  const int64_t bkv = bkv32;
-  const int ch = (int)(bid % (uint32_t)sa.nchunks);
-
-  // ---- this chunk's share [kt0, ce) of the slice's live keys [0, len) (kt0 is tile-aligned)
-  const int len = __builtin_amdgcn_readfirstlane(slice_len(ra, bkv32));
-  const int kt0 = ch * sa.chunk;
+  uint32_t bkv;
+  int ch, kt0;
+  fewq_block(sa, 0, &bkv, &ch, &kt0);
+  const int len = __builtin_amdgcn_readfirstlane(slice_len(ra, bkv));
   if (kt0 >= len) return;  // a dead chunk: the merge does not read its record
-  const int ce = min(kt0 + sa.chunk, len);
-  const int ntiles = (ce - kt0 + kBN - 1) / kBN;
+  const int ntiles = chunk_tiles(sa, kt0, len);
 
   // ---- the slice's sequence and head, as slice_len forms its k_lens index (kv_per_len = Hk)
-  const uint32_t idx = (uint32_t)ra.rem0 + bkv32, seq = idx / (uint32_t)ra.kv_per_len;
+  const uint32_t idx = (uint32_t)ra.rem0 + bkv, seq = idx / (uint32_t)ra.kv_per_len;
   const int hk = (int)(idx - seq * (uint32_t)ra.kv_per_len);
   const int32_t* row = pa.block_table + (ra.len0 + (int64_t)seq) * pa.max_pages;
 
-  const PagedRows map = {{ga.g, ga.pitch, ga.log2_pitch, len, nq}, row, (int)((uint32_t)(len - 1) / (uint32_t)pa.page),
-                         pa.page, pa.last_page, ra.kv_per_len, hk, FAST ? D : a.d, vd,
+  const PagedRows map = {{folded_rows(ga), len, a.rule.q.n}, row, (int)((uint32_t)(len - 1) / (uint32_t)pa.page),
+                         pa.page, pa.last_page, ra.kv_per_len, hk, FAST ? D : a.d, FAST ? D : a.v_d,
                          row[(uint32_t)kt0 / (uint32_t)pa.page]};  // (kt0 < len: a page with a live key)
-  WaveRegs<D, kNW> rg;
+  WaveRegs<D, kFewqNW> rg;
   WaveState<D> ws;
-  fwd_f16_core<D, kNW, POL, FAST, kF, PagedRows>(a, (lds_char_t*)smem_raw, 0, 0, kt0, ntiles, rg, ws, map, bkv);
-
-  // ---- epilogue: the unnormalised partial of the live rows; stores coalesce along the rows
-  const int rho = ws.qi, gp = ga.g * ga.pitch;
-  if (!ws.wave_active || rho >= gp || (rho & (ga.pitch - 1)) >= nq) return;
-  const float l_tot = ws.l_run + xor32(ws.l_run);
-  float* rec = sa.ws + (bkv * sa.nchunks + ch) * (int64_t)(vd + 3) * gp;
-#pragma unroll
-  for (int u = 0; u < D / 32; ++u)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int v = 32 * u + (i & 3) + 8 * (i >> 2) + 4 * ws.h;
-      if (FAST || v < vd) rec[(int64_t)v * gp + rho] = ws.acc_o[u][i];
-    }
-  if (ws.h == 0) {
-    float* st = rec + (int64_t)vd * gp;
-    st[rho] = ws.m_set ? ws.m_run : kNegInf;  // sentinel: the row sees no key of this chunk (tail-causal)
-    st[gp + rho] = ws.m_set ? l_tot : 0.f;
-    st[2 * gp + rho] = ws.m_max;
-  }
-}
-
-template <int D, int POL, bool FAST>
-hipError_t launch_partial_pf(const PagedArgs& pa, hipStream_t s) {
-  auto kern = paged_partial_kernel<D, POL, FAST>;
-  const int smem = Smem<D, kNW>::kTotal;
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), smem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(pa.r.g.s.f.b * pa.r.g.s.nchunks)), dim3(kNW * 64), smem, s, pa);
-  return hipGetLastError();
-}
-
-// FAST: d == v_d == D and 16-byte aligned pools; every page row then starts 16-byte aligned, since a page is a
-// multiple of 8 keys.  One query under the tail rule sees [0, len): the full form, as in the ragged forward.
-template <int D>
-hipError_t launch_partial_t(const PagedArgs& pa, hipStream_t s) {
-  const FwdArgs& a = pa.r.g.s.f;
-  const bool fast = a.d == D && a.v_d == D && (pa.page % 8 == 0) &&
-                    (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) && (reinterpret_cast<uintptr_t>(a.V) % 16 == 0);
-  const bool tail = pa.r.tail_causal != 0 && a.rule.q.n > 1;
-  return tail ? (fast ? launch_partial_pf<D, 1, true>(pa, s) : launch_partial_pf<D, 1, false>(pa, s))
-              : (fast ? launch_partial_pf<D, 0, true>(pa, s) : launch_partial_pf<D, 0, false>(pa, s));
+  fewq_partial<D, POL, FAST>(sa, (lds_char_t*)smem_raw, map, bkv, ch, kt0, ntiles, rg, ws);
 }
 
 }  // namespace
 
 hipError_t launch_fwd_f16_paged(const PagedArgs& pa, hipStream_t s) {
-  const FwdArgs& a = pa.r.g.s.f;
-  const int dm = max(a.d, a.v_d);
-  hipError_t e = dm <= 32 ? launch_partial_t<32>(pa, s) : dm <= 64 ? launch_partial_t<64>(pa, s)
-                                                                     : launch_partial_t<128>(pa, s);
+  // a page is a multiple of 8 keys, so with 16-byte aligned pools every page row starts 16-byte aligned
+  const hipError_t e = with_fewq_tail(pa.r, pa.page, [&](auto d, auto pol, auto fast) {
+    return launch_fewq_partial(d, paged_partial_kernel<d.value, pol.value, fast.value != 0>, pa, pa.r.g.s, s);
+  });
   if (e != hipSuccess) return e;
   return launch_fwd_f16_ragged_merge(pa.r, s);  // the merge reads neither K / V nor the table
 }

@@ -43,10 +43,14 @@ struct BwdArgs {
   Rule rule;
 };
 
+// floats of one (slice, chunk) record of the few-query forwards' workspace: v_d channel rows and three
+// statistics rows of `stride` floats (the format: fa_fwd_f16_fewq.h)
+constexpr int64_t fewq_record_floats(int32_t v_d, int64_t stride) { return (int64_t)(v_d + 3) * stride; }
+
 // split-key fp16 forward (fa_fwd_f16_splitk.hip): the plan of fa_api.hip plus the workspace
 struct SplitArgs {
   FwdArgs f;
-  float* ws;        // [b][nchunks][v_d + 3][nq] floats
+  float* ws;        // [b][nchunks] records of stride nq
   int32_t nchunks;  // chunks of the key range, >= 2
   int32_t chunk;    // keys per chunk (a multiple of the 64-key tile)
   int32_t k_first;  // first key of chunk 0 (tile-aligned, <= the range's first key)
@@ -56,7 +60,7 @@ struct SplitArgs {
 // grouped-query fp16 forward (fa_fwd_f16_gqa.hip): `g` query slices share one K/V slice and are folded into
 // the 128 rows of one workgroup.  s.f.b counts K/V slices; Q, O, l and m hold s.f.b * g slices.
 struct GqaArgs {
-  SplitArgs s;         // s.ws: [b_kv][nchunks][v_d + 3][g * pitch] floats; nchunks >= 1
+  SplitArgs s;         // s.ws: [b_kv][nchunks] records of stride g * pitch; nchunks >= 1
   int32_t g;           // query slices per K/V slice, >= 2
   int32_t pitch;       // rows per head: the smallest power of two >= nq; g * pitch <= 128
   int32_t log2_pitch;
@@ -169,24 +173,21 @@ hipError_t launch_fwd_f16_wide(const FwdArgs& a, hipStream_t s);
 // persistent band forward for 1d unit-stride local windows, 32 < max(d, v_d) <= 64 — fa_fwd_f16_band.hip
 bool fwd_f16_band_supported(const FwdArgs& a);
 hipError_t launch_fwd_f16_band(const FwdArgs& a, hipStream_t s);
-// split-key fp16 forward for one query block against a long key range: a partial kernel per
-// (slice, key chunk), which runs the general kernel's key loop (fa_fwd_f16_core.h) over its chunk,
-// and a merge kernel — fa_fwd_f16_splitk.hip.  At most
-// fwd_f16_splitk_max_batch() slices per call (grid limits).
-int64_t fwd_f16_splitk_max_batch(const SplitArgs& sa);
+// The few-query fp16 forwards: a partial kernel per (slice, key chunk), which runs the general kernel's key
+// loop (fa_fwd_f16_core.h) over its chunk, and a merge kernel (the pair: fa_fwd_f16_fewq.h).  At most
+// fwd_f16_fewq_max_batch() slices per call (grid limits), rows_out the (head, query) rows a slice's merge writes.
+int64_t fwd_f16_fewq_max_batch(int32_t nchunks, int32_t v_d, int64_t rows_out);
+// split-key: one query block against a long key range — fa_fwd_f16_splitk.hip
 hipError_t launch_fwd_f16_splitk(const SplitArgs& sa, hipStream_t s);
-// grouped-query fp16 forward for few queries: one workgroup per (K/V slice, key chunk) runs the same key
-// loop over the group's folded query rows, and a merge kernel writes each query slice's O, l, m —
-// fa_fwd_f16_gqa.hip.  At most fwd_f16_gqa_max_batch() K/V slices per call (grid limits).
-int64_t fwd_f16_gqa_max_batch(const GqaArgs& ga);
+// grouped-query: the same over the group's folded query rows, one workgroup per (K/V slice, key chunk), and the
+// merge writes each query slice's O, l, m — fa_fwd_f16_gqa.hip
 hipError_t launch_fwd_f16_gqa(const GqaArgs& ga, hipStream_t s);
 // the grouped forward with a per-slice key length: a chunk at or past its slice's length returns at once, and
-// the merge folds only the chunks below it — fa_fwd_f16_ragged.hip.  At most fwd_f16_gqa_max_batch(ra.g) K/V
-// slices per call (grid limits).
+// the merge folds only the chunks below it — fa_fwd_f16_ragged.hip
 hipError_t launch_fwd_f16_ragged(const RaggedArgs& ra, hipStream_t s);
 hipError_t launch_fwd_f16_ragged_merge(const RaggedArgs& ra, hipStream_t s);  // its second kernel alone
 // the ragged forward over a page pool and a device block table: the same chunks, records and merge, with each
-// key tile's address looked up in the table — fa_fwd_f16_paged.hip.  The same batch limit.
+// key tile's address looked up in the table — fa_fwd_f16_paged.hip
 hipError_t launch_fwd_f16_paged(const PagedArgs& pa, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
