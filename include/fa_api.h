@@ -221,6 +221,46 @@ int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group,
                      void* O, void* l, void* m,
                      void* workspace, size_t workspace_bytes);
 
+/* The ragged and the paged forward over an FP8 K/V cache: fa_forward_ragged / fa_forward_paged with K and V (or
+ * the pools) held as OCP e4m3fn bytes (NOT fnuz), one byte per element, in the same layouts:
+ *   ragged: K8 [b / kv_group][d][nk], V8 [b / kv_group][v_d][nk];
+ *   paged:  K_pool8 [num_pages][Hk][d][page], V_pool8 [num_pages][Hk][v_d][page], the key axis contiguous.
+ * p->dtype stays FA_F16: it is the dtype of Q, O and m; l stays fp32.  Half the cache bytes per decode step and
+ * twice the context per byte of cache; the matrix work is fp16 (e4m3fn -> fp16 is exact).
+ *   k_scale, v_scale: DEVICE fp32 arrays of kv_per_len values, one per K/V head of a sequence, shared by all
+ *     sequences; a null pointer means 1.0.  The true key of head h is k_scale[h] * K8 and the true value
+ *     v_scale[h] * V8 (a per-tensor scale is the array with one value repeated).  Only the kernels read them: no
+ *     host synchronisation, and they may be overwritten in place between replays of a captured graph, like
+ *     k_lens and block_table.  A scale must be finite and positive; any other value gives NaN output, never an
+ *     access outside the buffers.
+ *   Arithmetic: k_scale = 2^e * r with e = round(log2 k_scale) clamped to [-8, 7].  K8 * 2^e is formed exactly in
+ *     the conversion to fp16, r multiplies the fp32 factor 1/sqrt(d) * log2(e) before Q is rounded to fp16, and
+ *     v_scale multiplies the fp32 accumulator of each key chunk before the chunks are merged.
+ * Everything else is the fp16 twin's: envelope, argument errors, the empty rows, b == 0, FA_ERR_UNSUPPORTED /
+ * FA_ERR_WORKSPACE_TOO_SMALL with nothing written, the launches.  The plan and the workspace ARE the twin's: use
+ * fa_forward_ragged_plan / fa_forward_ragged_workspace_bytes and fa_forward_paged_plan /
+ * fa_forward_paged_workspace_bytes (the chunks do not depend on the element size).
+ * Guarantees:
+ *   what lies past a length does not reach a result, whatever byte it is, the NaN codes 0x7F / 0xFF included
+ *     (staged bytes past the length are cleared as integers before they are converted);
+ *   table entries of pages without a live key are never loaded, and a loaded entry is clamped as in
+ *     fa_forward_paged;
+ *   a slice's bits do not depend on b or on the other slices' lengths;
+ *   with both scales null or 1.0 the (O, l, m) bits are the fp16 twin's on the cache converted to fp16. */
+int fa_forward_ragged_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                          const void* Q, const void* K8, const void* V8,
+                          const float* k_scale, const float* v_scale,
+                          const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                          void* O, void* l, void* m,
+                          void* workspace, size_t workspace_bytes);
+int fa_forward_paged_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                         const void* Q, const void* K_pool8, const void* V_pool8,
+                         const float* k_scale, const float* v_scale,
+                         const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                         const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                         void* O, void* l, void* m,
+                         void* workspace, size_t workspace_bytes);
+
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);

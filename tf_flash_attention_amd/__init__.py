@@ -6,8 +6,9 @@ See ``flash_attention.py`` for the public API (mirrors the reference's
 from . import flash_attention
 from .flash_attention import (full_1d, causal_1d, local_1d, full_2d, causal_2d, local_2d,  # noqa: F401
                               InvalidArgumentError, InternalError, Part, combined_1d, combined_2d,
-                              merge_partials, grouped_1d, grouped_2d, attention_forward_grouped, ragged_1d, paged_1d)
+                              merge_partials, grouped_1d, grouped_2d, attention_forward_grouped, ragged_1d, paged_1d,
+                              quantize_kv_fp8)
 
 __all__ = ["flash_attention", "full_1d", "causal_1d", "local_1d", "full_2d", "causal_2d", "local_2d",
            "InvalidArgumentError", "InternalError", "Part", "combined_1d", "combined_2d", "merge_partials",
-           "grouped_1d", "grouped_2d", "attention_forward_grouped", "ragged_1d", "paged_1d"]
+           "grouped_1d", "grouped_2d", "attention_forward_grouped", "ragged_1d", "paged_1d", "quantize_kv_fp8"]

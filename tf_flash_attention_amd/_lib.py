@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = (
     "fa_forward_paged_plan",
     "fa_forward_paged_workspace_bytes",
     "fa_forward_paged",
+    "fa_forward_ragged_fp8",
+    "fa_forward_paged_fp8",
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_backward_split_plan",
@@ -161,6 +163,15 @@ def _declare(lib):
                                          ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp,
                                          ctypes.c_size_t]
         lib.fa_forward_paged.restype = ctypes.c_int
+    # (absent from a library built before the FP8 K/V cache, as above)
+    if hasattr(lib, "fa_forward_ragged_fp8"):
+        lib.fa_forward_ragged_fp8.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32,
+                                              ctypes.c_int32, vp, vp, vp, vp, ctypes.c_size_t]
+        lib.fa_forward_ragged_fp8.restype = ctypes.c_int
+        lib.fa_forward_paged_fp8.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32,
+                                             vp, vp, vp, vp, ctypes.c_size_t]
+        lib.fa_forward_paged_fp8.restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

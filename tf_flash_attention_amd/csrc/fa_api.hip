@@ -424,9 +424,11 @@ int check_kv_per_len(int64_t bkv, int32_t kv_per_len) {
 }
 
 // A few-query forward call's pointers.  K and V null: not sliced per launch (the paged pools, set by the caller).
+// kv_bytes: the size of a K / V element, 2 (fp16) or 1 (an FP8 cache).
 struct FewqPtrs {
   const void *Q, *K, *V;
   void *O, *l, *m, *workspace;
+  int kv_bytes = 2;
 };
 
 // The launches of a few-query forward over the p->b / g K/V slices, g query slices each, in slabs of at most
@@ -441,8 +443,8 @@ int fewq_slabs(const fa_problem* p, const FewqPtrs& t, int32_t g, int64_t rows, 
   for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {
     a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
     a.Q = static_cast<const uint16_t*>(t.Q) + b0 * g * p->d * nq;
-    if (t.K) a.K = static_cast<const uint16_t*>(t.K) + b0 * p->d * nk;
-    if (t.V) a.V = static_cast<const uint16_t*>(t.V) + b0 * p->v_d * nk;
+    if (t.K) a.K = static_cast<const char*>(t.K) + b0 * p->d * nk * t.kv_bytes;
+    if (t.V) a.V = static_cast<const char*>(t.V) + b0 * p->v_d * nk * t.kv_bytes;
     a.O = static_cast<uint16_t*>(t.O) + b0 * g * p->v_d * nq;
     a.l = static_cast<float*>(t.l) + b0 * g * nq;
     a.m = static_cast<uint16_t*>(t.m) + b0 * g * nq;
@@ -653,9 +655,15 @@ size_t fa_forward_ragged_workspace_bytes(const fa_problem* p, int32_t kv_group) 
   return s.nchunks ? grouped_ws_bytes(p, kv_group, s) : 0;
 }
 
-int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
-                      const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m,
-                      void* workspace, size_t workspace_bytes) {
+// An FP8 K/V cache of the ragged / paged forward: null for an fp16 cache, else the scales (either may be null)
+struct Kv8 {
+  const float *k_scale, *v_scale;
+};
+
+// fa_forward_ragged, and fa_forward_ragged_fp8 with kv8: the same checks, plan, workspace and launches
+static int forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
+                          const Kv8* kv8, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l,
+                          void* m, void* workspace, size_t workspace_bytes) {
   const int st = check_ragged(p, kv_group);
   if (st != FA_OK) return st;
   const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
@@ -671,13 +679,31 @@ int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const
   FA_DIAG_COUNT(0);
   if (p->b == 0) return FA_OK;
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
-  fa::RaggedArgs ra;
+  fa::RaggedFp8Args fa8;  // (ra alone for an fp16 cache)
+  fa::RaggedArgs& ra = fa8.r;
   fill_ragged(p, gp, kv_group, k_lens, kv_per_len, tail_causal, &ra);
+  if (kv8) { fa8.k_scale = kv8->k_scale; fa8.v_scale = kv8->v_scale; }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return fewq_slabs(p, {Q, K, V, O, l, m, workspace}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
+  return fewq_slabs(p, {Q, K, V, O, l, m, workspace, kv8 ? 1 : 2}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
-    return fa::launch_fwd_f16_ragged(ra, s);
+    return kv8 ? fa::launch_fwd_f16_ragged_fp8(fa8, s) : fa::launch_fwd_f16_ragged(ra, s);
   });
+}
+
+int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
+                      const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m,
+                      void* workspace, size_t workspace_bytes) {
+  return forward_ragged(stream, p, kv_group, Q, K, V, nullptr, k_lens, kv_per_len, tail_causal, O, l, m, workspace,
+                        workspace_bytes);
+}
+
+int fa_forward_ragged_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K8,
+                          const void* V8, const float* k_scale, const float* v_scale, const int32_t* k_lens,
+                          int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m, void* workspace,
+                          size_t workspace_bytes) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_ragged(stream, p, kv_group, Q, K8, V8, &kv8, k_lens, kv_per_len, tail_causal, O, l, m, workspace,
+                        workspace_bytes);
 }
 
 int fa_forward_paged_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]) {
@@ -694,10 +720,11 @@ size_t fa_forward_paged_workspace_bytes(const fa_problem* p, int32_t kv_group, i
   return s.nchunks ? grouped_ws_bytes(p, kv_group, s) : 0;
 }
 
-int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
-                     const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
-                     const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m,
-                     void* workspace, size_t workspace_bytes) {
+// fa_forward_paged, and fa_forward_paged_fp8 with kv8
+static int forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
+                         const void* V_pool, const Kv8* kv8, const int32_t* block_table, int32_t max_pages, int32_t page,
+                         int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
+                         void* l, void* m, void* workspace, size_t workspace_bytes) {
   const int st = check_paged(p, kv_group, page);
   if (st != FA_OK) return st;
   const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
@@ -720,8 +747,10 @@ int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const 
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
   if (!block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null block_table");
   if (!K_pool || !V_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null K_pool or V_pool");
-  fa::PagedArgs pa;
+  fa::PagedFp8Args pa8;  // (pa alone for fp16 pools)
+  fa::PagedArgs& pa = pa8.p;
   fa::RaggedArgs& ra = pa.r;
+  if (kv8) { pa8.k_scale = kv8->k_scale; pa8.v_scale = kv8->v_scale; }
   fill_ragged(p, gp, kv_group, k_lens, kv_per_len, tail_causal, &ra);
   pa.block_table = block_table; pa.max_pages = max_pages; pa.page = page;
   pa.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
@@ -729,8 +758,25 @@ int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const 
   hipStream_t s = static_cast<hipStream_t>(stream);
   return fewq_slabs(p, {Q, nullptr, nullptr, O, l, m, workspace}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
-    return fa::launch_fwd_f16_paged(pa, s);
+    return kv8 ? fa::launch_fwd_f16_paged_fp8(pa8, s) : fa::launch_fwd_f16_paged(pa, s);
   });
+}
+
+int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
+                     const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                     const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m,
+                     void* workspace, size_t workspace_bytes) {
+  return forward_paged(stream, p, kv_group, Q, K_pool, V_pool, nullptr, block_table, max_pages, page, num_pages, k_lens,
+                       kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_paged_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool8,
+                         const void* V_pool8, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                         int32_t max_pages, int32_t page, int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len,
+                         int32_t tail_causal, void* O, void* l, void* m, void* workspace, size_t workspace_bytes) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_paged(stream, p, kv_group, Q, K_pool8, V_pool8, &kv8, block_table, max_pages, page, num_pages, k_lens,
+                       kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 size_t fa_backward_workspace_bytes(const fa_problem* p) {
@@ -1007,7 +1053,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 // fwd_f16_core runs one workgroup's share of a (batch, head) slice: 32*NW query rows from q0
 // against the key tiles [kt0, kt0 + 64*ntiles), from the prologue loads through the last
 // ring step, and hands back each wave's unnormalised accumulator and softmax statistics
-// (WaveState).  Five
+// (WaveState).  Seven
 // kernels wrap it and differ only in which block gets which rows and keys and in the epilogue:
 //   * fwd_f16_kernel (fa_fwd_f16.hip): block -> (slice, query block), the rule-bounded key
 //     range of that block, normalises and writes O, l, m;
@@ -14,8 +14,10 @@
 //   * ragged_partial_kernel (fa_fwd_f16_ragged.hip): the same block with a per-slice key length read on
 //     the device (the row maps' key_limit / lane_interval below);
 //   * paged_partial_kernel (fa_fwd_f16_paged.hip): the ragged block with each key tile read from a page pool
-//     through a device block table (the row maps' tile below).
-// The four partial kernels share what surrounds the core, and their merge, in fa_fwd_f16_fewq.h.
+//     through a device block table (the row maps' tile below);
+//   * ragged_fp8_partial_kernel / paged_fp8_partial_kernel (fa_fwd_f16_ragged_fp8.hip, _paged_fp8.hip): the last
+//     two over a K/V cache of e4m3fn bytes, converted to fp16 on the way into LDS (KvOf below).
+// The partial kernels share what surrounds the core, and their merge, in fa_fwd_f16_fewq.h.
 // The structure:
 //   * Sᵀ = Kᵀ·Q and Oᵀ = V·Pᵀ on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
 //     Computing the TRANSPOSED scores puts the key index in the MFMA rows, so
@@ -73,7 +75,9 @@ struct Smem {
 
 constexpr int waves_per_eu(int D, int F) { return (D >= 128 || (F & kFOcc1)) ? 1 : ((F & kFOcc3) ? 3 : 2); }
 
-__device__ __forceinline__ u32x4 load16(const __half* p) { return *reinterpret_cast<const u32x4*>(p); }
+// one staging chunk, 8 keys of one channel row: 16 bytes of fp16, or 8 bytes of an 8-bit cache (below)
+__device__ __forceinline__ u32x4 load_chunk(const __half* p) { return *reinterpret_cast<const u32x4*>(p); }
+__device__ __forceinline__ u32x2 load_chunk(const uint8_t* p) { return *reinterpret_cast<const u32x2*>(p); }
 
 // the first n of a chunk's 8 halfs, zeros behind them (integer masks: a NaN bit pattern is cleared like any other)
 __device__ __forceinline__ u32x4 keep_first(u32x4 v, int n) {
@@ -81,16 +85,53 @@ __device__ __forceinline__ u32x4 keep_first(u32x4 v, int n) {
   for (int i = 0; i < 4; ++i) v[i] &= (2 * i < n ? 0xffffu : 0u) | (2 * i + 1 < n ? 0xffff0000u : 0u);
   return v;
 }
+// the same of a chunk's 8 bytes: byte 0 is +0.0 in e4m3fn, and the NaN codes 0x7F / 0xFF are cleared like any other
+__device__ __forceinline__ u32x2 keep_first(u32x2 v, int n) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int k = n - 4 * i;  // bytes of this word that are kept
+    v[i] &= k >= 4 ? 0xffffffffu : k <= 0 ? 0u : (1u << (8 * k)) - 1u;
+  }
+  return v;
+}
+// The element format of K / V.  fp16 unless the row map says kKv8 (fa_fwd_f16_ragged_fp8.hip, _paged_fp8.hip): then
+// K and V are OCP e4m3fn bytes in the same layouts, a staged chunk is its 8 raw bytes (half the staging registers),
+// and store_from converts it to the fp16 LDS image that the key loop reads, so nothing after the staging knows.
+// The conversion is exact (v_cvt_scalef32_pk_f16_fp8: every e4m3fn value times a power of two 2^e, -8 <= e <= 7,
+// is an fp16 value: |x| <= 448 * 128 < 65504, and the smallest subnormal 2^-9 becomes 2^-17 >= 2^-24).  Such a map
+// also carries the scales: kmul = 2^e multiplies K in that conversion, qmul multiplies the Q pre-scale in fp32
+// (k_scale = kmul * qmul), and vmul multiplies the accumulator where fewq_partial writes it (fa_fwd_f16_fewq.h).
+template <class Map, class = void>
+struct KvOf {
+  static constexpr bool k8 = false;
+  using Elem = __half;
+  using Reg = u32x4;
+};
+template <class Map>
+struct KvOf<Map, typename std::enable_if<Map::kKv8>::type> {
+  static constexpr bool k8 = true;
+  using Elem = uint8_t;
+  using Reg = u32x2;
+};
+__device__ __forceinline__ u32x4 chunk_f16(u32x4 v, float) { return v; }
+__device__ __forceinline__ u32x4 chunk_f16(u32x2 v, float mul) {
+  u32x4 o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    o[i] = __builtin_bit_cast(uint32_t, i & 1 ? __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v[i >> 1], mul, true)
+                                               : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v[i >> 1], mul, false));
+  return o;
+}
 
 // The loop's register arrays.  The KERNEL declares them (and the WaveState below) and hands them
 // in: the compiler optimises fwd_f16_core as a function of its own before it inlines it, without
 // the kernel's launch bounds, and arrays that are locals of that function are then cut up under
 // a smaller register budget than the kernel's (measured: 16 more AGPRs and 0.8 % slower at
 // D = 128).  Arrays that belong to the kernel are promoted there, under its bounds.
-template <int D, int NW>
+template <int D, int NW, class KvReg = u32x4>
 struct WaveRegs {
-  static constexpr int kCPT = (D * 8 + NW * 64 - 1) / (NW * 64);  // 16-B K (or V) chunks per thread and tile
-  u32x4 kreg[kCPT], vreg[kCPT], kreg1[kCPT], vreg1[kCPT];        // staged K / V tiles
+  static constexpr int kCPT = (D * 8 + NW * 64 - 1) / (NW * 64);  // 8-key K (or V) chunks per thread and tile
+  KvReg kreg[kCPT], vreg[kCPT], kreg1[kCPT], vreg1[kCPT];        // staged K / V tiles (KvOf<Map>::Reg)
   half8 qf[D / 16];                                               // scaled Q fragments
   floatx16 stA[2], stB[2], negm;                                  // scores of two tiles in flight; -m_run
 };
@@ -178,7 +219,7 @@ struct WaveState {
 //        2: other local rules (2d, strided): tile_class + per-element rule check
 //   Tiles with no allowed pair for a wave are skipped by that wave (no MFMAs).
 //   FAST d == v_d == D and K/V rows 16-byte aligned (nk % 8 == 0): unguarded
-//        dwordx4 staging.
+//        dwordx4 staging (an 8-bit cache: rows 8-byte aligned, dwordx2).
 //   Map  the row map above; with FoldedRows `bi` is unused, `bkv` is the K/V slice and the queries are
 //        those of slices bkv*g + j.  With IdentityRows `bkv` is unused: slice `bi` serves Q, K and V.
 // All waves stage K/V whatever nq is; waves whose 32 query rows lie past nq run no MFMA.
@@ -192,7 +233,7 @@ struct WaveState {
 // loaded into registers (T14).
 template <int D, int NW, int POL, bool FAST, int F, class Map = IdentityRows>
 __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem, int64_t bi, int q0, int kt0, int ntiles,
-                                             WaveRegs<D, NW>& rg, WaveState<D>& ws, Map map = Map{},
+                                             WaveRegs<D, NW, typename KvOf<Map>::Reg>& rg, WaveState<D>& ws, Map map = Map{},
                                              int64_t bkv = 0) {
   // (the map travels by value: a reference to the default argument's temporary changed the register
   // allocation of the ungrouped kernels, profiles/gqa_core_asm_equal.txt)
@@ -201,6 +242,8 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   constexpr int kBM = S::kBM;
   constexpr int kChunks = D * 8;                                   // 16-B chunks per K (or V) tile
   constexpr int kCPT = WaveRegs<D, NW>::kCPT;                      // chunks per thread
+  using KvT = typename KvOf<Map>::Elem;
+  using KvReg = typename KvOf<Map>::Reg;
   constexpr float kNegInf = -__builtin_huge_valf();
   __builtin_assume(kt0 % kBN == 0);  // lets key indices fold as they do where kt0 is formed in place
 
@@ -212,16 +255,20 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;  // tr-read lane roles
 
   const __half* Q = static_cast<const __half*>(a.Q) + map.q_slice(bi, bkv) * (int64_t)d * nq;
-  const __half* K = static_cast<const __half*>(a.K) + map.kv_slice(bi, bkv) * (int64_t)d * nk;
-  const __half* V = static_cast<const __half*>(a.V) + map.kv_slice(bi, bkv) * (int64_t)vd * nk;
+  const KvT* K = static_cast<const KvT*>(a.K) + map.kv_slice(bi, bkv) * (int64_t)d * nk;
+  const KvT* V = static_cast<const KvT*>(a.V) + map.kv_slice(bi, bkv) * (int64_t)vd * nk;
   const bool qvec = ((nq & 7) == 0) && ((reinterpret_cast<uintptr_t>(a.Q) & 15) == 0);
-  const float c2 = (float)a.scale * kLog2e;
+  float c2 = (float)a.scale * kLog2e, kmul = 1.f;
+  if constexpr (KvOf<Map>::k8) {  // (qmul == 1 leaves c2's bits alone)
+    c2 *= map.qmul;
+    kmul = map.kmul;
+  }
 
   // ---- register staging of one K/V tile (16-B chunks; chunk = 8 keys of one channel row)
-  auto load_into = [&](u32x4 (&kr)[kCPT], u32x4 (&vr)[kCPT], int k0) {
+  auto load_into = [&](KvReg (&kr)[kCPT], KvReg (&vr)[kCPT], int k0) {
     // channel row 0 of the slice, the row stride and the key that index 0 stands for; a paged map moves all three
     // to the tile (for the other maps these are new names for K, V, nk and 0, and the code below is unchanged)
-    const __half *Kt = K, *Vt = V;
+    const KvT *Kt = K, *Vt = V;
     int ts = nk, kb = 0;
     if constexpr (Map::kPaged) {
       map.tile(K, V, k0, &Kt, &Vt, &ts);
@@ -233,33 +280,34 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
       const bool in = (kChunks % kThr == 0) || idx < kChunks;
       const int e = k0 + 8 * m;
       if (FAST && (kChunks % kThr == 0) && k0 + kBN <= nkl) {  // whole tile in range: unguarded
-        kr[j] = load16(Kt + (int64_t)c * ts + (e - kb));
-        vr[j] = load16(Vt + (int64_t)c * ts + (e - kb));
+        kr[j] = load_chunk(Kt + (int64_t)c * ts + (e - kb));
+        vr[j] = load_chunk(Vt + (int64_t)c * ts + (e - kb));
       } else if (FAST) {
-        kr[j] = (in && e < nkl) ? load16(Kt + (int64_t)c * ts + (e - kb)) : u32x4{0, 0, 0, 0};
-        vr[j] = (in && e < nkl) ? load16(Vt + (int64_t)c * ts + (e - kb)) : u32x4{0, 0, 0, 0};
-        if constexpr (Map::kRagged) {  // a 16-byte chunk may straddle the length
+        kr[j] = (in && e < nkl) ? load_chunk(Kt + (int64_t)c * ts + (e - kb)) : KvReg{};
+        vr[j] = (in && e < nkl) ? load_chunk(Vt + (int64_t)c * ts + (e - kb)) : KvReg{};
+        if constexpr (Map::kRagged) {  // a chunk may straddle the length
           kr[j] = keep_first(kr[j], nkl - e);
           vr[j] = keep_first(vr[j], nkl - e);
         }
       } else {
-        kr[j] = (in && c < d) ? load_chunk8(Kt + (int64_t)c * ts, e - kb, nkl - kb, false) : u32x4{0, 0, 0, 0};
-        vr[j] = (in && c < vd) ? load_chunk8(Vt + (int64_t)c * ts, e - kb, nkl - kb, false) : u32x4{0, 0, 0, 0};
+        kr[j] = (in && c < d) ? load_chunk8(Kt + (int64_t)c * ts, e - kb, nkl - kb, false) : KvReg{};
+        vr[j] = (in && c < vd) ? load_chunk8(Vt + (int64_t)c * ts, e - kb, nkl - kb, false) : KvReg{};
       }
     }
   };
-  auto store_from = [&](const u32x4 (&kr)[kCPT], const u32x4 (&vr)[kCPT], int buf) {
+  auto store_from = [&](const KvReg (&kr)[kCPT], const KvReg (&vr)[kCPT], int buf) {
     lds_char_t* kbuf = smem + buf * S::kBuf;
     lds_char_t* vbuf = kbuf + S::kK;
 #pragma unroll
     for (int j = 0; j < kCPT; ++j) {
       const int idx = tid + kThr * j, c = idx >> 3, m = idx & 7;
       if ((kChunks % kThr == 0) || idx < kChunks) {
+        const u32x4 kc = chunk_f16(kr[j], kmul), vc = chunk_f16(vr[j], 1.f);  // (an 8-bit chunk becomes fp16 here)
         // K: [c][64 keys], 64-B halves swapped on rows with c&2 (conflict-free tr reads)
-        *reinterpret_cast<lds_u32x4_t*>(kbuf + c * 128 + ((m * 16) ^ ((c & 2) << 5))) = kr[j];
+        *reinterpret_cast<lds_u32x4_t*>(kbuf + c * 128 + ((m * 16) ^ ((c & 2) << 5))) = kc;
         // V: [key/4][v][4] slabs -> the PV operand is a plain conflict-free ds_read_b64
-        *reinterpret_cast<lds_u32x2_t*>(vbuf + ((2 * m) * (D + kVPad) + c) * 8) = vr[j].xy;
-        *reinterpret_cast<lds_u32x2_t*>(vbuf + ((2 * m + 1) * (D + kVPad) + c) * 8) = vr[j].zw;
+        *reinterpret_cast<lds_u32x2_t*>(vbuf + ((2 * m) * (D + kVPad) + c) * 8) = vc.xy;
+        *reinterpret_cast<lds_u32x2_t*>(vbuf + ((2 * m + 1) * (D + kVPad) + c) * 8) = vc.zw;
       }
     }
   };
@@ -529,10 +577,11 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
 
 // host: whether these arguments take the FAST staging at channel tile D, where K / V channel rows are `row_keys`
 // keys apart: every row then starts 16-byte aligned
+// (8 keys' bytes: `chunk_bytes` = 16 of fp16, 8 of an 8-bit cache)
 template <int D>
-bool fast_staging(const FwdArgs& a, int row_keys) {
-  return a.d == D && a.v_d == D && (row_keys % 8 == 0) && (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) &&
-         (reinterpret_cast<uintptr_t>(a.V) % 16 == 0);
+bool fast_staging(const FwdArgs& a, int row_keys, int chunk_bytes = 16) {
+  return a.d == D && a.v_d == D && (row_keys % 8 == 0) && (reinterpret_cast<uintptr_t>(a.K) % chunk_bytes == 0) &&
+         (reinterpret_cast<uintptr_t>(a.V) % chunk_bytes == 0);
 }
 
 // host: the <POL, FAST> instantiation these arguments take at channel tile D.  `launch(pol, fast)`

@@ -80,7 +80,8 @@ __device__ __forceinline__ int chunk_tiles(const SplitArgs& sa, int kt0, int end
 // were before the kernels shared this body (profiles/fewq_skeleton_asm.txt).
 template <int D, int POL, bool FAST, class Map>
 __device__ __forceinline__ void fewq_partial(const SplitArgs& sa, lds_char_t* smem, Map map, int64_t slice, int ch,
-                                             int kt0, int ntiles, WaveRegs<D, kFewqNW>& rg, WaveState<D>& ws) {
+                                             int kt0, int ntiles, WaveRegs<D, kFewqNW, typename KvOf<Map>::Reg>& rg,
+                                             WaveState<D>& ws) {
   const FwdArgs& a = sa.f;
   const int nq = a.rule.q.n;
   fwd_f16_core<D, kFewqNW, POL, FAST, kFewqF, Map>(a, smem, slice, 0, kt0, ntiles, rg, ws, map, slice);
@@ -95,7 +96,9 @@ __device__ __forceinline__ void fewq_partial(const SplitArgs& sa, lds_char_t* sm
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int v = 32 * u + (i & 3) + 8 * (i >> 2) + 4 * ws.h;
-      if (FAST || v < r.vd) rec[r.chan(v, row)] = ws.acc_o[u][i];
+      float o = ws.acc_o[u][i];
+      if constexpr (KvOf<Map>::k8) o *= map.vmul;  // an 8-bit cache's v_scale: the merge stays the fp16 forwards'
+      if (FAST || v < r.vd) rec[r.chan(v, row)] = o;
     }
   if (ws.h == 0) {
     rec[r.stat(FewqRecord::kMRun, row)] = ws.m_set ? ws.m_run : FewqRecord::kEmpty;
@@ -165,6 +168,90 @@ __device__ __forceinline__ void merge_folded(const GqaArgs& ga, Chunks&& chunks)
   merge_row(ga.s, folded_rows(ga).rec_stride(ga.s.f.rule.q.n), bkv, j * ga.pitch + q, v, chunks(bkv), bkv * ga.g + j, q);
 }
 
+// RaggedRows plus the block table (fa_fwd_f16_core.h: the row maps; the layout: fa_fwd_f16_paged.hip).  K and V
+// handed to tile() are the pools.
+// The core asks for its tiles in ascending order, one per key-loop step, and the entry is a dependent load in
+// front of the tile's K / V loads; asked for on the spot it stalls the wave for a memory round trip per tile
+// (2 to 12 % over the ragged forward).  So tile() loads the entry of the NEXT tile's page, a whole
+// tile ahead of its use, and takes its own from `pre_e`, where the call before left it; the kernel loads the first
+// tile's.  This rests on the core's order of asking: kt0, kt0 + 64, kt0 + 128, ... without a gap (a different
+// order would read a neighbouring page of the same sequence: wrong bits, which every bitwise test shows, never an
+// access outside the pools).  The page looked ahead to is capped at last_live, the last page with a live key, so
+// no entry of a page without one is ever loaded.
+struct PagedRows : RaggedRows {
+  static constexpr bool kPaged = true;
+  const int32_t* row;   // this sequence's table row
+  int32_t last_live;    // (len - 1) / page, len >= 1: the last page that holds a live key (< max_pages)
+  int32_t page, last_page;
+  int32_t heads, hk;    // Hk; this slice's head
+  int32_t kd, vd;       // channels of a K / V page
+  int32_t pre_e;        // the raw entry of the page of the tile that is asked for next
+  // the pools are not sliced per K/V slice: the table says where a slice's keys are
+  __device__ __forceinline__ int64_t kv_slice(int64_t, int64_t) const { return 0; }
+  // (T: the pools' element, __half or the byte of an 8-bit cache; the offsets are in elements)
+  template <class T>
+  __device__ __forceinline__ void tile(const T* K, const T* V, int k0, const T** Kt, const T** Vt, int* ts) {
+    const int p = min((int)((uint32_t)k0 / (uint32_t)page), last_live);
+    const int entry = __builtin_amdgcn_readfirstlane(min(max(pre_e, 0), last_page));
+    pre_e = row[min((int)((uint32_t)(k0 + kBN) / (uint32_t)page), last_live)];
+    const int64_t blk = ((int64_t)entry * heads + hk) * page;  // in rows of `page` keys per channel
+    const int off = k0 - p * page;
+    *Kt = K + blk * kd + off;
+    *Vt = V + blk * vd + off;
+    *ts = page;
+  }
+};
+
+// the map of K/V slice bkv of this launch, of `len` >= 1 live keys, for the chunk at kt0 < len at channel tile D
+template <int D, bool FAST>
+__device__ __forceinline__ PagedRows paged_rows(const PagedArgs& pa, uint32_t bkv, int len, int kt0) {
+  const RaggedArgs& ra = pa.r;
+  const FwdArgs& a = ra.g.s.f;
+  // ---- the slice's sequence and head, as slice_len forms its k_lens index (kv_per_len = Hk)
+  const uint32_t idx = (uint32_t)ra.rem0 + bkv, seq = idx / (uint32_t)ra.kv_per_len;
+  const int hk = (int)(idx - seq * (uint32_t)ra.kv_per_len);
+  const int32_t* row = pa.block_table + (ra.len0 + (int64_t)seq) * pa.max_pages;
+  return {{folded_rows(ra.g), len, a.rule.q.n}, row, (int)((uint32_t)(len - 1) / (uint32_t)pa.page),
+          pa.page, pa.last_page, ra.kv_per_len, hk, FAST ? D : a.d, FAST ? D : a.v_d,
+          row[(uint32_t)kt0 / (uint32_t)pa.page]};  // (kt0 < len: a page with a live key)
+}
+
+// ---- an 8-bit K/V cache (fa_fwd_f16_core.h: KvOf; fa_fwd_f16_ragged_fp8.hip, fa_fwd_f16_paged_fp8.hip)
+
+// The scales of head hk as the core takes them.  k_scale = 2^e * r with e = round(log2 k_scale) clamped to
+// [-8, 7]: kmul = 2^e multiplies K exactly in the conversion to fp16, and qmul = r, in [2^-0.5, 2^0.5) inside the
+// clamp, multiplies the Q pre-scale in fp32 before Q is rounded to fp16; all of k_scale there would push Q' towards
+// fp16 subnormals for small scales.  vmul = v_scale.  A null array means 1.0: kmul = qmul = vmul = 1, the fp16
+// forward's bits.  A scale that is not finite and positive becomes a NaN factor, so the output is NaN rather than
+// plausible.  All of this is integer work on the scale's bits (-fno-honor-nans cannot touch it) and wave-uniform.
+struct Kv8Mul {
+  float kmul, qmul, vmul;
+};
+__device__ __forceinline__ Kv8Mul kv8_mul(const float* k_scale, const float* v_scale, int hk) {
+  constexpr uint32_t kOne = 0x3f800000u, kNaN = 0x7fc00000u, kMaxFinite = 0x7f7fffffu;
+  const uint32_t kb = k_scale ? __float_as_uint(k_scale[hk]) : kOne;
+  const uint32_t vb = v_scale ? __float_as_uint(v_scale[hk]) : kOne;
+  // the exponent field, one more where the mantissa is at or above sqrt(2) (0x3fb504f3): round(log2)
+  int e = (int)(kb >> 23) - 127 + ((kb & 0x7fffffu) >= 0x3504f3u ? 1 : 0);
+  e = min(max(e, -8), 7);
+  const float r = __uint_as_float(kb) * __uint_as_float((uint32_t)(127 - e) << 23);  // exact: a power of two
+  Kv8Mul s;
+  s.kmul = __uint_as_float((uint32_t)(127 + e) << 23);
+  s.qmul = __uint_as_float(kb - 1u < kMaxFinite ? __float_as_uint(r) : kNaN);
+  s.vmul = __uint_as_float(vb - 1u < kMaxFinite ? vb : kNaN);
+  return s;
+}
+
+// RaggedRows / PagedRows over an 8-bit cache
+struct RaggedRows8 : RaggedRows {
+  static constexpr bool kKv8 = true;
+  float kmul, qmul, vmul;
+};
+struct PagedRows8 : PagedRows {
+  static constexpr bool kKv8 = true;
+  float kmul, qmul, vmul;
+};
+
 // host: the channel tile of these arguments; `f(d)` receives it as IC<D>
 template <class F>
 hipError_t with_fewq_d(const FwdArgs& a, F&& f) {
@@ -181,13 +268,13 @@ hipError_t with_fewq_rule(const FwdArgs& a, Launch&& launch) {
 }
 
 // host: the same of a forward with key lengths.  `row_keys`: the keys between two channel rows of K / V (the
-// capacity, or the page).  One query under the tail rule sees [0, len): the full form, so that its bits are the
-// full form's.
+// capacity, or the page), `chunk_bytes` those of 8 keys.  One query under the tail rule sees [0, len): the full
+// form, so that its bits are the full form's.
 template <class Launch>
-hipError_t with_fewq_tail(const RaggedArgs& ra, int row_keys, Launch&& launch) {
+hipError_t with_fewq_tail(const RaggedArgs& ra, int row_keys, Launch&& launch, int chunk_bytes = 16) {
   const FwdArgs& a = ra.g.s.f;
   return with_fewq_d(a, [&](auto d) {
-    const bool fast = fast_staging<decltype(d)::value>(a, row_keys);
+    const bool fast = fast_staging<decltype(d)::value>(a, row_keys, chunk_bytes);
     const bool tail = ra.tail_causal != 0 && a.rule.q.n > 1;
     return tail ? (fast ? launch(d, IC<1>{}, IC<1>{}) : launch(d, IC<1>{}, IC<0>{}))
                 : (fast ? launch(d, IC<0>{}, IC<1>{}) : launch(d, IC<0>{}, IC<0>{}));

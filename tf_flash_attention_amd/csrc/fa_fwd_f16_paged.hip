@@ -25,60 +25,18 @@ namespace {
 
 using namespace f16core;
 
-// RaggedRows plus the block table (fa_fwd_f16_core.h: the row maps; fa_fwd_f16_fewq.h).  K and V handed to tile() are the pools.
-// The core asks for its tiles in ascending order, one per key-loop step, and the entry is a dependent load in
-// front of the tile's K / V loads; asked for on the spot it stalls the wave for a memory round trip per tile
-// (2 to 12 % over the ragged forward).  So tile() loads the entry of the NEXT tile's page, a whole
-// tile ahead of its use, and takes its own from `pre_e`, where the call before left it; the kernel loads the first
-// tile's.  This rests on the core's order of asking: kt0, kt0 + 64, kt0 + 128, ... without a gap (a different
-// order would read a neighbouring page of the same sequence: wrong bits, which every bitwise test shows, never an
-// access outside the pools).  The page looked ahead to is capped at last_live, the last page with a live key, so
-// no entry of a page without one is ever loaded.
-struct PagedRows : RaggedRows {
-  static constexpr bool kPaged = true;
-  const int32_t* row;   // this sequence's table row
-  int32_t last_live;    // (len - 1) / page, len >= 1: the last page that holds a live key (< max_pages)
-  int32_t page, last_page;
-  int32_t heads, hk;    // Hk; this slice's head
-  int32_t kd, vd;       // channels of a K / V page
-  int32_t pre_e;        // the raw entry of the page of the tile that is asked for next
-  // the pools are not sliced per K/V slice: the table says where a slice's keys are
-  __device__ __forceinline__ int64_t kv_slice(int64_t, int64_t) const { return 0; }
-  __device__ __forceinline__ void tile(const __half* K, const __half* V, int k0, const __half** Kt,
-                                       const __half** Vt, int* ts) {
-    const int p = min((int)((uint32_t)k0 / (uint32_t)page), last_live);
-    const int entry = __builtin_amdgcn_readfirstlane(min(max(pre_e, 0), last_page));
-    pre_e = row[min((int)((uint32_t)(k0 + kBN) / (uint32_t)page), last_live)];
-    const int64_t blk = ((int64_t)entry * heads + hk) * page;  // in rows of `page` keys per channel
-    const int off = k0 - p * page;
-    *Kt = K + blk * kd + off;
-    *Vt = V + blk * vd + off;
-    *ts = page;
-  }
-};
-
 template <int D, int POL, bool FAST>
 __global__ __launch_bounds__(kFewqNW * 64, waves_per_eu(D, kFewqF)) void paged_partial_kernel(PagedArgs pa) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const RaggedArgs& ra = pa.r;
-  const GqaArgs& ga = ra.g;
-  const SplitArgs& sa = ga.s;
-  const FwdArgs& a = sa.f;
+  const SplitArgs& sa = ra.g.s;
   uint32_t bkv;
   int ch, kt0;
   fewq_block(sa, 0, &bkv, &ch, &kt0);
   const int len = __builtin_amdgcn_readfirstlane(slice_len(ra, bkv));
   if (kt0 >= len) return;  // a dead chunk: the merge does not read its record
   const int ntiles = chunk_tiles(sa, kt0, len);
-
-  // ---- the slice's sequence and head, as slice_len forms its k_lens index (kv_per_len = Hk)
-  const uint32_t idx = (uint32_t)ra.rem0 + bkv, seq = idx / (uint32_t)ra.kv_per_len;
-  const int hk = (int)(idx - seq * (uint32_t)ra.kv_per_len);
-  const int32_t* row = pa.block_table + (ra.len0 + (int64_t)seq) * pa.max_pages;
-
-  const PagedRows map = {{folded_rows(ga), len, a.rule.q.n}, row, (int)((uint32_t)(len - 1) / (uint32_t)pa.page),
-                         pa.page, pa.last_page, ra.kv_per_len, hk, FAST ? D : a.d, FAST ? D : a.v_d,
-                         row[(uint32_t)kt0 / (uint32_t)pa.page]};  // (kt0 < len: a page with a live key)
+  const PagedRows map = paged_rows<D, FAST>(pa, bkv, len, kt0);
   WaveRegs<D, kFewqNW> rg;
   WaveState<D> ws;
   fewq_partial<D, POL, FAST>(sa, (lds_char_t*)smem_raw, map, bkv, ch, kt0, ntiles, rg, ws);

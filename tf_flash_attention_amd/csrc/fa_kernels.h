@@ -89,6 +89,20 @@ struct PagedArgs {
   int32_t last_page;           // num_pages - 1: every loaded entry is clamped to [0, last_page]
 };
 
+// the ragged and the paged forward over an FP8 K/V cache (fa_fwd_f16_ragged_fp8.hip, fa_fwd_f16_paged_fp8.hip):
+// K / V (or the pools) are OCP e4m3fn bytes in the same layouts, and the scales are device arrays of kv_per_len
+// floats, one per K/V head of a sequence, that only the kernels read (null: 1.0)
+struct RaggedFp8Args {
+  RaggedArgs r;
+  const float* k_scale;  // true key = k_scale[head] * K8
+  const float* v_scale;  // true value = v_scale[head] * V8
+};
+struct PagedFp8Args {
+  PagedArgs p;
+  const float* k_scale;
+  const float* v_scale;
+};
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;
@@ -189,6 +203,10 @@ hipError_t launch_fwd_f16_ragged_merge(const RaggedArgs& ra, hipStream_t s);  //
 // the ragged forward over a page pool and a device block table: the same chunks, records and merge, with each
 // key tile's address looked up in the table — fa_fwd_f16_paged.hip
 hipError_t launch_fwd_f16_paged(const PagedArgs& pa, hipStream_t s);
+// the two over an FP8 (e4m3fn) cache with per-head scales: the same kernels with an 8-bit staging, the same merge —
+// fa_fwd_f16_ragged_fp8.hip, fa_fwd_f16_paged_fp8.hip
+hipError_t launch_fwd_f16_ragged_fp8(const RaggedFp8Args& fa8, hipStream_t s);
+hipError_t launch_fwd_f16_paged_fp8(const PagedFp8Args& pa8, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

@@ -105,6 +105,14 @@ __device__ __forceinline__ u32x4 load_chunk8(const __half* row, int e, int n, bo
                hh[6] | (uint32_t(hh[7]) << 16)};
 }
 
+// 8 consecutive bytes starting at element e of a row of length n (zeros past n), any alignment
+__device__ __forceinline__ u32x2 load_chunk8(const uint8_t* row, int e, int n, bool) {
+  uint32_t bb[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) bb[j] = (e + j < n) ? (uint32_t)row[e + j] : 0u;
+  return u32x2{bb[0] | (bb[1] << 8) | (bb[2] << 16) | (bb[3] << 24), bb[4] | (bb[5] << 8) | (bb[6] << 16) | (bb[7] << 24)};
+}
+
 __device__ __forceinline__ half8 scale8(half8 x, float s) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) x[j] = (_Float16)((float)x[j] * s);

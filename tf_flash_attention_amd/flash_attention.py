@@ -64,7 +64,7 @@ __all__ = [
     "InvalidArgumentError", "InternalError", "estimate_forward_flops",
     "Part", "combined_1d", "combined_2d", "merge_partials",
     "grouped_1d", "grouped_2d", "attention_forward_grouped",
-    "ragged_1d", "paged_1d",
+    "ragged_1d", "paged_1d", "quantize_kv_fp8",
 ]
 
 
@@ -651,7 +651,68 @@ _RAGGED_ENVELOPE = ("float16, 1d sequences, at most 128 channels, Nq >= 1, capac
                     "g * next_pow2(Nq) <= 128 with g = Hq / Hk")
 
 
-def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False):
+# An FP8 K/V cache (include/fa_api.h, "over an FP8 K/V cache"): OCP e4m3fn bytes, as
+# torch.float8_e4m3fn or as the same bytes in a uint8 tensor
+_FP8_CACHE_DTYPES = tuple(dt for dt in (getattr(torch, "float8_e4m3fn", None), torch.uint8) if dt is not None)
+FP8_E4M3_MAX = 448.0
+
+
+def quantize_kv_fp8(x, head_axis, scale=None):
+    """Quantizes a K or V tensor to ``torch.float8_e4m3fn`` with one scale per K/V head: returns ``(x8, scale)``
+    with ``x ~= scale[h] * x8`` along ``head_axis``.  Without ``scale`` it is the head's ``amax / 448`` over all
+    other axes (1.0 for a head of zeros); a given ``scale`` is a float32 tensor of shape ``(Hk,)``.  ``x / scale`` is
+    clamped to +-448 before the cast, because the cast itself turns what lies beyond the format's range into NaN.
+    Plain torch, on the device of ``x``: appends are a few tokens per step, so this is not a kernel."""
+    if getattr(torch, "float8_e4m3fn", None) is None:
+        raise NotImplementedError("this torch has no float8_e4m3fn")
+    head_axis = head_axis % x.dim()
+    xf = x.to(torch.float32)
+    if scale is None:
+        amax = xf.abs().amax(dim=[a for a in range(x.dim()) if a != head_axis])
+        scale = torch.where(amax > 0, amax / FP8_E4M3_MAX, torch.ones_like(amax))
+    elif not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32:
+        raise TypeError(f"scale must be a float32 tensor, got {getattr(scale, 'dtype', type(scale).__name__)}")
+    elif tuple(scale.shape) != (x.shape[head_axis],):
+        raise InvalidArgumentError("The shape of scale should be (Hk,) = " + _shape_str((x.shape[head_axis],))
+                                   + ", but scale_shape = " + _shape_str(scale.shape) + " was received")
+    view = [1] * x.dim()
+    view[head_axis] = -1
+    x8 = (xf / scale.to(xf.device).view(view)).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+    return x8, scale
+
+
+def _kv_cache_scales(what, Q, K, V, hk, k_scale, v_scale):
+    """Whether K and V are an FP8 cache, after the checks of their dtypes and of the scales (fp32 device tensors of
+    shape ``(Hk,)``, or None for 1.0)."""
+    fp8 = K.dtype in _FP8_CACHE_DTYPES
+    if fp8:
+        if V.dtype not in _FP8_CACHE_DTYPES:
+            raise TypeError(f"{what} must both be an FP8 cache (float8_e4m3fn or uint8) or both share the dtype of Q")
+    elif K.dtype != Q.dtype or V.dtype != Q.dtype:
+        raise TypeError(f"Q, {what} must share one dtype")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is None:
+            continue
+        if not fp8:
+            raise InvalidArgumentError(f"{name} was given, but {what} are not an FP8 cache (float8_e4m3fn or uint8): "
+                                       "a float16 cache takes no scale")
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if tuple(t.shape) != (hk,):
+            raise InvalidArgumentError(f"The shape of {name} should be (Hk,) = " + _shape_str((hk,)) + f", but {name}_shape = "
+                                       + _shape_str(t.shape) + " was received")
+        if t.device != Q.device:
+            raise InvalidArgumentError(f"{name} must be on the device of Q")
+        if not t.is_contiguous():  # (the kernels read the caller's own array on every replay, not a copy)
+            raise InvalidArgumentError(f"{name} must be contiguous")
+    return fp8
+
+
+def _scale_ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=None, v_scale=None):
     """Attention of a few queries over a padded K/V cache: Q ``batch + (Hq, C, Nq)``, K ``batch + (Hk, C, cap)``,
     V ``batch + (Hk, Cv, cap)`` with Hq = g * Hk read from the shapes (query head h attends K/V head h // g), and
     ``k_lens`` an int32 tensor of shape ``batch`` on the same device (0-d without a leading batch axis): sequence
@@ -662,11 +723,16 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False):
     The lengths are read by the kernels, never on the host: no synchronisation, and a captured graph may be
     replayed after ``k_lens`` was overwritten in place.  Inference only (no gradient); float16 only; outside the
     fused envelope the call raises NotImplementedError (a fallback would have to read the lengths on the host).
+
+    An FP8 cache: K and V of dtype ``torch.float8_e4m3fn`` (or the same bytes as ``torch.uint8``) with Q float16.
+    ``k_scale`` and ``v_scale`` are float32 tensors of shape ``(Hk,)`` on the device of Q, or None for 1.0: the true
+    key of head h is ``k_scale[h] * K[..., h, :, :]``, the true value ``v_scale[h] * V[..., h, :, :]``
+    (``quantize_kv_fp8`` makes both).  The kernels read the scales, never the host.  A float16 cache takes no scale.
     Returns ``O`` or ``(O, l, m)``."""
     Qb, Qs, Q_ch, Kb, Ks, V_ch, g = verify_grouped_shapes(1, Q.shape, K.shape, V.shape)
     dt = _dtype_id(Q, True)
-    if K.dtype != Q.dtype or V.dtype != Q.dtype:
-        raise TypeError("Q, K and V must share one dtype")
+    kv_per_len = int(Kb[-1]) if Kb else 1
+    fp8 = _kv_cache_scales("K and V", Q, K, V, kv_per_len, k_scale, v_scale)
     if not isinstance(k_lens, torch.Tensor) or k_lens.dtype != torch.int32:
         raise TypeError(f"k_lens must be an int32 tensor, got {getattr(k_lens, 'dtype', type(k_lens).__name__)}")
     batch = Qb[:-1]
@@ -695,12 +761,17 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False):
     l = torch.empty(Qb + Qs, dtype=torch.float32, device=Q.device)
     m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
     ws_bytes = int(L.fa_forward_ragged_workspace_bytes(prob, g))
-    kv_per_len = int(Kb[-1]) if Kb else 1
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        st = L.fa_forward_ragged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
-                                 k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)), O.data_ptr(), l.data_ptr(),
-                                 m.data_ptr(), ws.data_ptr(), ws_bytes)
+        if fp8:
+            st = L.fa_forward_ragged_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                         _scale_ptr(k_scale), _scale_ptr(v_scale), k_lens.data_ptr(), kv_per_len,
+                                         int(bool(tail_causal)), O.data_ptr(), l.data_ptr(), m.data_ptr(),
+                                         ws.data_ptr(), ws_bytes)
+        else:
+            st = L.fa_forward_ragged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                     k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)), O.data_ptr(), l.data_ptr(),
+                                     m.data_ptr(), ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
@@ -713,7 +784,8 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False):
 _PAGE_CONDITION = "the page size (the last axis of K_pool and V_pool) must be a multiple of 64 keys"
 
 
-def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False):
+def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False, k_scale=None,
+             v_scale=None):
     """``ragged_1d`` over a paged K/V cache: Q ``batch + (Hq, C, Nq)``, ``K_pool`` ``[num_pages, Hk, C, page]``,
     ``V_pool`` ``[num_pages, Hk, Cv, page]`` with Hq = g * Hk read from the shapes, ``block_table`` an int32 tensor
     ``batch + (max_pages,)`` and ``k_lens`` an int32 tensor of shape ``batch``, both on the device of Q.  A page
@@ -728,6 +800,14 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
     ``pos`` (a device tensor) needs no host read either, it is an ``index_put`` with device indices::
 
         K_pool[block_table[s, pos // page], :, :, pos % page] = new
+
+    An FP8 cache: pools of dtype ``torch.float8_e4m3fn`` (or the same bytes as ``torch.uint8``) with Q float16, and
+    ``k_scale`` / ``v_scale`` float32 tensors of shape ``(Hk,)`` on the device of Q, or None for 1.0, as in
+    ``ragged_1d``; they too may be overwritten in place between replays.  The append quantizes the token with the
+    pool's scales, still without a host read::
+
+        new8, _ = quantize_kv_fp8(new, head_axis=0, scale=k_scale)
+        K_pool[block_table[s, pos // page], :, :, pos % page] = new8
 
     Inference only (no gradient); float16 only; the page size must be a multiple of 64; outside the envelope the
     call raises NotImplementedError (there is no gather fallback).  Returns ``O`` or ``(O, l, m)``."""
@@ -754,8 +834,7 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
                                    "hold a page, but Q_shape = " + _shape_str(Q.shape) + ", K_pool_shape = "
                                    + _shape_str(K_pool.shape) + " were received")
     dt = _dtype_id(Q, True)
-    if K_pool.dtype != Q.dtype or V_pool.dtype != Q.dtype:
-        raise TypeError("Q, K_pool and V_pool must share one dtype")
+    fp8 = _kv_cache_scales("K_pool and V_pool", Q, K_pool, V_pool, hk, k_scale, v_scale)
     for name, t in (("block_table", block_table), ("k_lens", k_lens)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
             raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
@@ -797,10 +876,17 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
     ws_bytes = int(L.fa_forward_paged_workspace_bytes(prob, g, page))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        st = L.fa_forward_paged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(), V_pool.data_ptr(),
-                                block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(), hk,
-                                int(bool(tail_causal)), O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(),
-                                ws_bytes)
+        if fp8:
+            st = L.fa_forward_paged_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
+                                        V_pool.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
+                                        block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(), hk,
+                                        int(bool(tail_causal)), O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(),
+                                        ws_bytes)
+        else:
+            st = L.fa_forward_paged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
+                                    V_pool.data_ptr(), block_table.data_ptr(), max_pages, page, num_pages,
+                                    k_lens.data_ptr(), hk, int(bool(tail_causal)), O.data_ptr(), l.data_ptr(),
+                                    m.data_ptr(), ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
