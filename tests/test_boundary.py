@@ -159,7 +159,7 @@ def test_product_library_reads_no_environment():
     (-DFA_DIAG); the product library carries no variant selector and imports no getenv."""
     path = _lib.LIB_PATH
     data = open(path, "rb").read()
-    for key in (b"FA_FWD_VARIANT", b"FA_BWD_VARIANT", b"FA_FWD_ABL"):
+    for key in (b"FA_FWD_VARIANT", b"FA_BWD_VARIANT", b"FA_FWD_ABL", b"FA_SLAB_MAX", b"fa_diag_slab_count"):
         assert key not in data
     import subprocess
     nm = subprocess.run(["nm", "-D", "--undefined-only", path], capture_output=True, text=True)

@@ -142,6 +142,25 @@ def test_merge_kernel_sweep(dtype, n):
                 check_merge(dtype, Os, ls, ms, call_merge(dtype, Os, ls, ms), f"n={n} nq={nq} v_d={v_d} b={b}")
 
 
+MERGE_SLAB = 65535   # fa_merge_partials launches at most this many slices at once: the grid's y extent
+
+
+@pytest.mark.parametrize("nq", [7, 8], ids=["scalar", "vector"])
+@pytest.mark.parametrize("b", [MERGE_SLAB, MERGE_SLAB + 1, 2 * MERGE_SLAB + 1], ids=["one_slab", "plus_one", "three_slabs"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=_id)
+def test_merge_kernel_large_batch(dtype, b, nq):
+    """The slab loop of fa_merge_partials at its real limit: one slab exactly, one slab and one slice, three slabs,
+    every slice against the float64 reference.  nq = 7 takes the scalar path; with nq = 8 every slab's offset is
+    a multiple of 16 bytes in every dtype, so the later slabs stay on the vector path.  Rows that are empty in
+    every part lie in every slab."""
+    Os, ls, ms = synthetic_partials(dtype, 3, b, 4, nq, seed=b % 1000 + nq)
+    any_live = np.any([x != 0 for x in ls], axis=0)
+    for b0 in range(0, b, MERGE_SLAB):
+        slab = any_live[b0:b0 + MERGE_SLAB]
+        assert (~slab).any() and slab.any(), b0
+    check_merge(dtype, Os, ls, ms, call_merge(dtype, Os, ls, ms), f"b={b} nq={nq}")
+
+
 @pytest.mark.parametrize("dtype", DTYPES, ids=_id)
 def test_merge_kernel_misaligned(dtype):
     """Every tensor, inputs and outputs, one element off 16-byte alignment (nq a multiple of the vector width)."""
@@ -274,21 +293,35 @@ CASES = {
     # against 2100 keys take the split-key forward and the backward's key-chunk dQ plan
     "split_q_f16": (np.float16, 1, (2300,), 64, 64, [Spec("local", (2300,), window_size=33), Spec("full", (16,))]),
     "split_k_f16": (np.float16, 1, (33,), 64, 64, [Spec("full", (2100,)), Spec("local", (33,), window_size=5)]),
+    # two key shards over 65538 slices: the merge runs a second slab (MERGE_SLAB slices and 3 more)
+    "many_slices_f16": (np.float16, 1, (8,), 8, 8, [Spec("full", (8,)), Spec("full", (8,))]),
+    "many_slices_f32": (np.float32, 1, (8,), 8, 8, [Spec("full", (8,)), Spec("full", (8,))]),
 }
 BATCH = (1, 2)
+# cases with a batch of their own, checked on a fixed sample of its slices: name -> (batch, slices); here the first
+# and the last slices of both slabs of the merge, and a few more
+SAMPLED = {name: ((65538,), (0, 1, 2, 32767, 32768, 40000, 65533, 65534, 65535, 65536, 65537))
+           for name in ("many_slices_f16", "many_slices_f32")}
 
 
 @functools.lru_cache(maxsize=None)
 def case_data(name):
-    """Inputs (U(-2, 2), as run_case) and the dense float64 reference of a case, computed once and shared."""
+    """Inputs (U(-2, 2), as run_case) and the dense float64 reference of a case, computed once and shared.  A
+    SAMPLED case keeps its whole inputs under "device" (what runs) and "slices"; everything else, inputs and
+    reference, is of those slices only, as a case of that many slices."""
     dtype, seq_dims, qs, d, v_d, specs = CASES[name]
     rng = np.random.default_rng(sorted(CASES).index(name))
-    b = int(np.prod(BATCH))
+    batch, slices = SAMPLED.get(name, (BATCH, None))
     nq = int(np.prod(qs))
-    Q = rng.uniform(-2, 2, BATCH + (d,) + qs).astype(dtype)
-    Ks = [rng.uniform(-2, 2, BATCH + (d,) + s.ks).astype(dtype) for s in specs]
-    Vs = [rng.uniform(-2, 2, BATCH + (v_d,) + s.ks).astype(dtype) for s in specs]
-    dO = rng.uniform(-2, 2, BATCH + (v_d,) + qs).astype(dtype)
+    Q = rng.uniform(-2, 2, batch + (d,) + qs).astype(dtype)
+    Ks = [rng.uniform(-2, 2, batch + (d,) + s.ks).astype(dtype) for s in specs]
+    Vs = [rng.uniform(-2, 2, batch + (v_d,) + s.ks).astype(dtype) for s in specs]
+    dO = rng.uniform(-2, 2, batch + (v_d,) + qs).astype(dtype)
+    device = dict(Q=Q, Ks=Ks, Vs=Vs, dO=dO)
+    if slices is not None:
+        pick = lambda x: x[list(slices)]  # noqa: E731  (one batch axis)
+        Q, Ks, Vs, dO = pick(Q), [pick(x) for x in Ks], [pick(x) for x in Vs], pick(dO)
+    b = int(np.prod(Q.shape[:len(batch)]))
     masks = [O.problem_mask(s.problem(seq_dims), qs, s.ks) for s in specs]
     mask = np.concatenate(masks, axis=1)
     nks = [int(np.prod(s.ks)) for s in specs]
@@ -327,7 +360,7 @@ def case_data(name):
     return dict(Q=Q, Ks=Ks, Vs=Vs, dO=dO, masks=masks, mask=mask, ha=ha, O=o_ref, L=L, M=M, dQ=dq,
                 dKs=[dk[:, :, edges[j]:edges[j + 1]] for j in range(len(specs))],
                 dVs=[dv[:, :, edges[j]:edges[j + 1]] for j in range(len(specs))], dq_part_max=dq_part_max,
-                kcat=k, vmax=float(np.abs(v).max()), b=b, nq=nq)
+                kcat=k, vmax=float(np.abs(v).max()), b=b, nq=nq, device=device, slices=slices)
 
 
 def o_bound(name):
@@ -381,18 +414,25 @@ def run_combined(name):
     """The case through combined_1d / combined_2d, forward and backward; numpy results."""
     dtype, seq_dims, qs, d, v_d, specs = CASES[name]
     c = case_data(name)
-    tq = _to_dev(c["Q"]).requires_grad_(True)
-    tks = [_to_dev(x).requires_grad_(True) for x in c["Ks"]]
-    tvs = [_to_dev(x).requires_grad_(True) for x in c["Vs"]]
+    dev = c["device"]
+    tq = _to_dev(dev["Q"]).requires_grad_(True)
+    tks = [_to_dev(x).requires_grad_(True) for x in dev["Ks"]]
+    tvs = [_to_dev(x).requires_grad_(True) for x in dev["Vs"]]
     parts = [fa.Part(s.policy, tk, tv, s.sync_mode, s.ws, s.ls, s.causal) for s, tk, tv in zip(specs, tks, tvs)]
     o, l, m = (fa.combined_1d if seq_dims == 1 else fa.combined_2d)(tq, parts, returning_l_m=True)
     assert not l.requires_grad and not m.requires_grad
-    o.backward(_to_dev(c["dO"]))
+    o.backward(_to_dev(dev["dO"]))
     torch.cuda.synchronize()
-    b, nq = c["b"], c["nq"]
-    flat = lambda t, ch: t.detach().cpu().numpy().reshape(b, ch, -1)  # noqa: E731
-    return dict(O=flat(o, v_d), l=l.cpu().numpy(), m=m.cpu().numpy(), dQ=flat(tq.grad, d),
+    pick = sampler(name)
+    flat = lambda t, ch: pick(t.detach().cpu().numpy()).reshape(c["b"], ch, -1)  # noqa: E731
+    return dict(O=flat(o, v_d), l=pick(l.cpu().numpy()), m=pick(m.cpu().numpy()), dQ=flat(tq.grad, d),
                 dKs=[flat(t.grad, d) for t in tks], dVs=[flat(t.grad, v_d) for t in tvs])
+
+
+def sampler(name):
+    """What takes a result of the case's whole batch to the slices that case_data holds."""
+    slices = case_data(name)["slices"]
+    return (lambda x: x) if slices is None else (lambda x: x[list(slices)])
 
 
 def ratio(got, ref, bound):
@@ -418,21 +458,26 @@ def check_combined(name, got):
         assert (got["O"][:, :, ~ha] == 0).all()
 
 
-@pytest.mark.parametrize("name", [n for n in sorted(CASES) if not n.startswith(("key_shards", "empty_rows", "split"))])
+@pytest.mark.parametrize("name", [n for n in sorted(CASES)
+                                  if not n.startswith(("key_shards", "empty_rows", "split", "many_slices"))])
 def test_combined(name):
     check_combined(name, run_combined(name))
 
 
-@pytest.mark.parametrize("name", ["key_shards_f16", "key_shards_f32"])
+@pytest.mark.parametrize("name", ["key_shards_f16", "key_shards_f32", "many_slices_f16", "many_slices_f32"])
 def test_combined_key_shards(name):
-    """Three key shards under the full policy against the whole problem, and against full_1d on the unsplit K."""
+    """Three key shards under the full policy against the whole problem, and against full_1d on the unsplit K.
+    many_slices: two shards of 8 keys over 65538 slices, forward and backward, so that the merge and every forward
+    and backward launcher under combined_1d see a second slab or slice indices past 16 bits; checked on the
+    sampled slices."""
     got = run_combined(name)
     check_combined(name, got)
     c = case_data(name)
+    dev = c["device"]
     cat = lambda xs: _to_dev(np.concatenate(xs, axis=-1))  # noqa: E731
-    whole = fa.full_1d(_to_dev(c["Q"]), cat(c["Ks"]), cat(c["Vs"]))
+    whole = fa.full_1d(_to_dev(dev["Q"]), cat(dev["Ks"]), cat(dev["Vs"]))
     torch.cuda.synchronize()
-    whole = whole.cpu().numpy().reshape(got["O"].shape)
+    whole = sampler(name)(whole.cpu().numpy()).reshape(got["O"].shape)
     assert ratio(whole, c["O"], o_bound(name)) <= 1.0   # (full_1d itself, for scale)
     assert ratio(got["O"], whole.astype(np.float64), o_bound(name)) <= 1.0
 

@@ -616,6 +616,37 @@ def test_config5_full2d_f32_sampled():
     run_case(np.float32, "full", 2, "scale_front", (1, 2), 64, 64, (64, 64), (128, 128), seed=5, slices=[1])
 
 
+# ------------------------------------------------------------ slice indices past 16 bits
+# 65538 slices of a tiny problem (at most 2^26 elements a tensor), forward and backward, the oracle on the slices
+# around 2^15 and 2^16: one launcher of each family has then seen a slice index that does not fit 16 bits (a grid
+# axis other than x holds 65535 blocks at most).  The shapes follow the *_supported predicates of csrc/.
+MANY_SLICES = [0, 1, 32767, 32768, 65535, 65536, 65537]
+MANY_SLICE_CASES = {
+    # fa_generic.hip, both directions: the only path past 256 channels (an odd count)
+    "generic_simt": (np.float16, "full", 257, 257, (2,), (3,), 1),
+    # fa_fwd_f16.hip launch_t<32, 4, 8> (max(d, v_d) <= 32 is never the fast forward) and the two-pass backward of
+    # fa_bwd_f16_fast.hip, which takes every fp16 shape up to 256 channels
+    "f16_general": (np.float16, "causal", 16, 16, (24,), (40,), 1),
+    # fa_fwd_f16_fast.hip launch_fast_t<64, 8, ...> at the smallest shape fwd_f16_fast_supported takes (more than 32
+    # channels, nk % 8 == 0, an interval rule; causal, so not the full policy's ping-pong kernel) + the same backward
+    "f16_fast": (np.float16, "causal", 40, 40, (16,), (8,), 1),
+    # fa_fwd_f32.hip / fa_bwd_f32.hip launch_t<32>
+    "f32_mfma": (np.float32, "full", 8, 8, (10,), (17,), 1),
+    # fa_f64.hip launch_fwd_t<32> / launch_bwd_t<32>
+    "f64_mfma": (np.float64, "full", 8, 8, (10,), (17,), 1),
+    # fa_fwd_f16_band.hip (1d local, ls = 0, d in (32, 64], v_d = 64, nq % 8 == nk % 8 == 0): about 256 persistent
+    # workgroups walk the 65538 one-block slices
+    "local_band": (np.float16, "local", 64, 64, (8,), (8,), 2),
+}
+
+
+@pytest.mark.parametrize("name", sorted(MANY_SLICE_CASES))
+def test_many_slices(name):
+    dtype, policy, d, vd, qs, ks, ws = MANY_SLICE_CASES[name]
+    run_case(dtype, policy, 1, "none_front", (65538,), d, vd, qs, ks, ws=ws, slices=MANY_SLICES,
+             seed=sorted(MANY_SLICE_CASES).index(name))
+
+
 # ------------------------------ fp16 kernel structures forced onto other shapes (selected by env)
 # FA_FWD_VARIANT / FA_BWD_VARIANT (diagnostic library only) force a structure onto shapes the
 # dispatcher sends elsewhere, so each shipped kernel is parity-checked on every rule it accepts

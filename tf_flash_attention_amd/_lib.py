@@ -187,6 +187,14 @@ def _declare(lib):
     lib.fa_rule_probe.restype = ctypes.c_int
     lib.fa_build_info.argtypes = []
     lib.fa_build_info.restype = ctypes.c_char_p
+    # the diagnostic library only (libfa_hip_diag.so): calls that reached a launch (0 forward, 1 backward), and
+    # the slab launches of the batch-slab loops, which FA_SLAB_MAX shortens there (tests/test_gpu_slabs.py)
+    if hasattr(lib, "fa_diag_call_count"):
+        lib.fa_diag_call_count.argtypes = [ctypes.c_int]
+        lib.fa_diag_call_count.restype = ctypes.c_longlong
+    if hasattr(lib, "fa_diag_slab_count"):
+        lib.fa_diag_slab_count.argtypes = []
+        lib.fa_diag_slab_count.restype = ctypes.c_longlong
     return lib
 
 

@@ -423,6 +423,27 @@ int check_kv_per_len(int64_t bkv, int32_t kv_per_len) {
   return FA_OK;
 }
 
+#ifdef FA_DIAG
+// Diagnostic library only: FA_SLAB_MAX, read on every call like the variant selectors, lowers the slab limit of
+// the four slab loops below (fewq_slabs, bwd_slabs, fa_merge_partials, fa_accumulate_parts) so that a test can
+// drive them through several iterations at small batches; the real limits (about 2^31 blocks, 65535 slices)
+// are out of a test's reach or costly.  A value that is not positive, or not below the real limit, changes
+// nothing.  `unit`: what one count of the variable stands for (slices; for fa_accumulate_parts 8 * kThreads
+// elements of fa_merge.hip, so a slab boundary keeps the 16-byte alignment that the real limit guarantees).
+// g_diag_slabs counts the slab launches (loop iterations), so the test can prove that the loop iterated.
+std::atomic<long long> g_diag_slabs;
+int64_t diag_slab_limit(int64_t limit, int64_t unit = 1) {
+  const int64_t cap = (int64_t)fa::diag_variant("FA_SLAB_MAX") * unit;
+  return cap > 0 && cap < limit ? cap : limit;
+}
+constexpr int64_t kAccumulateSlabUnit = 8 * 256;
+#define FA_SLAB_LIMIT(...) diag_slab_limit(__VA_ARGS__)
+#define FA_DIAG_SLAB() g_diag_slabs.fetch_add(1)
+#else
+#define FA_SLAB_LIMIT(limit, ...) (limit)
+#define FA_DIAG_SLAB() ((void)0)
+#endif
+
 // A few-query forward call's pointers.  K and V null: not sliced per launch (the paged pools, set by the caller).
 // kv_bytes: the size of a K / V element, 2 (fp16) or 1 (an FP8 cache).
 struct FewqPtrs {
@@ -439,7 +460,7 @@ template <class Launch>
 int fewq_slabs(const fa_problem* p, const FewqPtrs& t, int32_t g, int64_t rows, fa::SplitArgs* sa, Launch&& launch) {
   fa::FwdArgs& a = sa->f;
   const int64_t nq = a.rule.q.n, nk = a.rule.k.n, bkv = p->b / g;
-  const int64_t bmax = fa::fwd_f16_fewq_max_batch(sa->nchunks, p->v_d, g * nq);
+  const int64_t bmax = FA_SLAB_LIMIT(fa::fwd_f16_fewq_max_batch(sa->nchunks, p->v_d, g * nq));
   for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {
     a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
     a.Q = static_cast<const uint16_t*>(t.Q) + b0 * g * p->d * nq;
@@ -449,6 +470,7 @@ int fewq_slabs(const fa_problem* p, const FewqPtrs& t, int32_t g, int64_t rows, 
     a.l = static_cast<float*>(t.l) + b0 * g * nq;
     a.m = static_cast<uint16_t*>(t.m) + b0 * g * nq;
     sa->ws = static_cast<float*>(t.workspace) + b0 * sa->nchunks * fa::fewq_record_floats(p->v_d, rows);
+    FA_DIAG_SLAB();
     const hipError_t e = launch(b0);
     if (e != hipSuccess)
       return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
@@ -489,6 +511,7 @@ int bwd_slabs(const fa_problem* p, const fa::BwdArgs& whole, int64_t bmax, fa::B
     // (ws_dQ stays: the two-pass kernels keep no dQ accumulator)
     a->ws_D = static_cast<float*>(whole.ws_D) + b0 * nq;
     a->ws_lse = static_cast<float*>(whole.ws_lse) + b0 * nq;
+    FA_DIAG_SLAB();
     const hipError_t e = launch(b0);
     if (e != hipSuccess)
       return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
@@ -545,6 +568,8 @@ int fa_validate(const fa_problem* p) {
 static std::atomic<long long> g_diag_calls[2];
 long long fa_diag_call_count(int which) { return (which == 0 || which == 1) ? g_diag_calls[which].load() : -1; }
 #define FA_DIAG_COUNT(w) g_diag_calls[w].fetch_add(1)
+// slab launches of the four slab loops (fewq_slabs, bwd_slabs, the merge and the accumulate loop)
+long long fa_diag_slab_count(void) { return g_diag_slabs.load(); }
 #else
 #define FA_DIAG_COUNT(w) ((void)0)
 #endif
@@ -863,7 +888,7 @@ int backward_split_q(void* stream, const fa_problem* p, const QSplitPlan& qp, co
   sa.nchunks = qp.nchunks; sa.chunk = qp.chunk; sa.q_first = qp.q_first; sa.q_end = qp.qe;
   float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + w.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return bwd_slabs(p, whole, fa::bwd_f16_qsplit_max_batch(sa), &sa.b, [&](int64_t b0) {
+  return bwd_slabs(p, whole, FA_SLAB_LIMIT(fa::bwd_f16_qsplit_max_batch(sa)), &sa.b, [&](int64_t b0) {
     sa.ws_part = part + b0 * qp.nchunks * (p->d + p->v_d) * whole.rule.k.n;
     return fa::launch_bwd_f16_qsplit(sa, s);
   });
@@ -893,7 +918,7 @@ int fa_backward_split(void* stream, const fa_problem* p, const void* Q, const vo
   sa.nchunks = sp.nchunks; sa.chunk = sp.chunk; sa.k_first = sp.k_first; sa.k_end = sp.ke;
   float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + w.total);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return bwd_slabs(p, whole, fa::bwd_f16_split_max_batch(sa), &sa.b, [&](int64_t b0) {
+  return bwd_slabs(p, whole, FA_SLAB_LIMIT(fa::bwd_f16_split_max_batch(sa)), &sa.b, [&](int64_t b0) {
     sa.ws_part = part + b0 * sp.nchunks * p->d * whole.rule.q.n;
     return fa::launch_bwd_f16_split(sa, s);
   });
@@ -923,7 +948,7 @@ int fa_merge_partials(void* stream, int32_t dtype, int64_t b, int64_t nq, int32_
         return set_error(FA_ERR_INVALID_ARGUMENT, "an output aliases an input of part " + std::to_string(i));
     a.O_parts[i] = O_parts[i]; a.l_parts[i] = l_parts[i]; a.m_parts[i] = m_parts[i];
   }
-  const int64_t bmax = fa::merge_max_batch(dtype, nq, v_d);
+  const int64_t bmax = FA_SLAB_LIMIT(fa::merge_max_batch(dtype, nq, v_d));
   if (bmax < 1) return set_error(FA_ERR_UNSUPPORTED, "one slice exceeds the merge kernel's grid");
   const size_t es = elem_size(dtype), ls = dtype == FA_F16 ? sizeof(float) : es;
   a.nq = nq; a.v_d = v_d;
@@ -941,6 +966,7 @@ int fa_merge_partials(void* stream, int32_t dtype, int64_t b, int64_t nq, int32_
     a.O = static_cast<char*>(O) + o_off;
     a.l = static_cast<char*>(l) + l_off;
     a.m = static_cast<char*>(m) + m_off;
+    FA_DIAG_SLAB();
     const hipError_t e = fa::launch_merge(dtype, n_parts, a, s);
     if (e != hipSuccess)
       return set_error((int)e, std::string("Failed to launch the merge kernel: ") + hipGetErrorString(e));
@@ -965,12 +991,13 @@ int fa_accumulate_parts(void* stream, int32_t dtype, int64_t count, int32_t n_pa
   fa::AccumulateArgs a;
   memset(&a, 0, sizeof(a));
   const size_t es = elem_size(dtype);
-  const int64_t cmax = fa::accumulate_max_count();
+  const int64_t cmax = FA_SLAB_LIMIT(fa::accumulate_max_count(), kAccumulateSlabUnit);
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int64_t c0 = 0; c0 < count; c0 += cmax) {
     a.count = count - c0 < cmax ? count - c0 : cmax;
     for (int i = 0; i < n_parts; ++i) a.parts[i] = static_cast<const char*>(parts[i]) + es * (size_t)c0;
     a.out = static_cast<char*>(out) + es * (size_t)c0;
+    FA_DIAG_SLAB();
     const hipError_t e = fa::launch_accumulate(dtype, n_parts, a, s);
     if (e != hipSuccess)
       return set_error((int)e, std::string("Failed to launch the accumulate kernel: ") + hipGetErrorString(e));
