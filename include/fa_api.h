@@ -261,6 +261,73 @@ int fa_forward_paged_fp8(void* stream, const fa_problem* p, int32_t kv_group,
                          void* O, void* l, void* m,
                          void* workspace, size_t workspace_bytes);
 
+/* Sliding-window decode: the four forwards above with a window of W = `window` >= 1 keys.  The tail rule's
+ * positions are implied (there is no tail_causal argument): with L the clamped length of a slice, query i sits at
+ * position pos_i = L - nq + i and sees the keys j with max(0, pos_i - W + 1) <= j <= pos_i: W keys, its own
+ * position included (local_1d's |qo - ko| <= W - 1 with is_causal).  A query with pos_i < 0 gets the empty row
+ * (O = 0, l = 0, every byte of m 0xFA).  The block as a whole sees [lo, L), lo = max(0, L - nq - W + 1): at most
+ * span_w = min(nk, W + nq - 1) keys.
+ *
+ * Everything else is the un-windowed twin's contract: envelope, argument errors, b == 0, FA_ERR_UNSUPPORTED and
+ * FA_ERR_WORKSPACE_TOO_SMALL with nothing written, no host synchronisation, no host read of k_lens, block_table
+ * or the scales.  In addition window < 1 returns FA_ERR_INVALID_ARGUMENT with text in fa_last_error().
+ *
+ * window >= nk can never cut anything (L <= nk), and the host knows it: the call IS the un-windowed twin with
+ *   tail_causal = 1, with its plan, workspace bytes and kernels, bit for bit.
+ * window < nk: the plan follows the window, not the capacity.  chunk = fa_forward_grouped_plan's formula with
+ *   span_w in place of the capacity span, max(min_chunk, ceil(ceil(span_w / 64) / 64) * 64); the chunk boundaries
+ *   stay at absolute multiples of chunk from key 0; per K/V slice
+ *     n_launch = min(ceil(nk / chunk), floor((span_w + chunk - 2) / chunk) + 1)
+ *   workgroups are launched, the most chunks an interval of span_w keys can touch.  Workgroup (slice, c) works
+ *   absolute chunk floor(lo / chunk) + c with the lo of the length it loads, over the tiles from
+ *   max(chunk start, floor(lo / 64) * 64) to min(chunk end, L), and returns at once where that is empty.  The
+ *   workspace is b / kv_group * n_launch records of the twins' layout.
+ * The plan functions (host-only; pure functions of the problem WITHOUT b, the lengths or the table) write
+ *   out[0] n_launch (0 outside the envelope)     out[4] pitch P
+ *   out[1] keys per chunk                        out[5] folded rows kv_group * P
+ *   out[2] span_w                                out[6] 1 if delegated to the tail form (window >= nk): out[0],
+ *   out[3] ceil(nk / chunk)                             out[1] are then the twin's plan, out[3] = out[0]
+ *                                                out[7] reserved, 0
+ * The FP8 forms use the fp16 plan and workspace functions, as their twins do.
+ *
+ * Never read: key tiles wholly below floor(lo / 64) * 64 and keys at or past L; in the paged forms the table
+ *   entries of pages wholly below that key and of pages past the last live page: the serving stack may free
+ *   and reuse those pages and leave anything in their entries.  Loaded entries and lengths are clamped as in the
+ *   twins.
+ * Finite keys: the keys of the first staged tile that lie below lo (at most 63, the sequence's own earlier keys
+ *   on a page it still owns) are loaded and masked, not zeroed.  They must be finite: a NaN or Inf in V there
+ *   would survive a probability of 0.
+ * A slice's bits do not depend on b or on the other slices' lengths; the paged bits are the ragged ones on the
+ *   gathered cache; the FP8 bits with null or unit scales are the fp16 ones on the converted cache. */
+int fa_forward_ragged_window_plan(const fa_problem* p, int32_t kv_group, int32_t window, int32_t out[8]);
+int fa_forward_paged_window_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window, int32_t out[8]);
+size_t fa_forward_ragged_window_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t window);
+size_t fa_forward_paged_window_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window);
+int fa_forward_ragged_window(void* stream, const fa_problem* p, int32_t kv_group,
+                             const void* Q, const void* K, const void* V,
+                             const int32_t* k_lens, int32_t kv_per_len, int32_t window,
+                             void* O, void* l, void* m,
+                             void* workspace, size_t workspace_bytes);
+int fa_forward_paged_window(void* stream, const fa_problem* p, int32_t kv_group,
+                            const void* Q, const void* K_pool, const void* V_pool,
+                            const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                            const int32_t* k_lens, int32_t kv_per_len, int32_t window,
+                            void* O, void* l, void* m,
+                            void* workspace, size_t workspace_bytes);
+int fa_forward_ragged_window_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                                 const void* Q, const void* K8, const void* V8,
+                                 const float* k_scale, const float* v_scale,
+                                 const int32_t* k_lens, int32_t kv_per_len, int32_t window,
+                                 void* O, void* l, void* m,
+                                 void* workspace, size_t workspace_bytes);
+int fa_forward_paged_window_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                                const void* Q, const void* K_pool8, const void* V_pool8,
+                                const float* k_scale, const float* v_scale,
+                                const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                                const int32_t* k_lens, int32_t kv_per_len, int32_t window,
+                                void* O, void* l, void* m,
+                                void* workspace, size_t workspace_bytes);
+
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);

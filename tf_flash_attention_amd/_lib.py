@@ -44,6 +44,14 @@ EXPORTED_SYMBOLS = (
     "fa_forward_paged",
     "fa_forward_ragged_fp8",
     "fa_forward_paged_fp8",
+    "fa_forward_ragged_window_plan",
+    "fa_forward_paged_window_plan",
+    "fa_forward_ragged_window_workspace_bytes",
+    "fa_forward_paged_window_workspace_bytes",
+    "fa_forward_ragged_window",
+    "fa_forward_paged_window",
+    "fa_forward_ragged_window_fp8",
+    "fa_forward_paged_window_fp8",
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_backward_split_plan",
@@ -172,6 +180,26 @@ def _declare(lib):
                                              ctypes.c_int32, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32,
                                              vp, vp, vp, vp, ctypes.c_size_t]
         lib.fa_forward_paged_fp8.restype = ctypes.c_int
+    # (absent from a library built before sliding-window decode, as above): the twins' argument lists with
+    # `window` where tail_causal stands, and `window` after the plan functions' own arguments
+    if hasattr(lib, "fa_forward_ragged_window"):
+        i32 = ctypes.c_int32
+        lib.fa_forward_ragged_window_plan.argtypes = [P, i32, i32, ctypes.POINTER(i32)]
+        lib.fa_forward_ragged_window_plan.restype = ctypes.c_int
+        lib.fa_forward_paged_window_plan.argtypes = [P, i32, i32, i32, ctypes.POINTER(i32)]
+        lib.fa_forward_paged_window_plan.restype = ctypes.c_int
+        lib.fa_forward_ragged_window_workspace_bytes.argtypes = [P, i32, i32]
+        lib.fa_forward_ragged_window_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_forward_paged_window_workspace_bytes.argtypes = [P, i32, i32, i32]
+        lib.fa_forward_paged_window_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_forward_ragged_window.argtypes = list(lib.fa_forward_ragged.argtypes)
+        lib.fa_forward_ragged_window.restype = ctypes.c_int
+        lib.fa_forward_paged_window.argtypes = list(lib.fa_forward_paged.argtypes)
+        lib.fa_forward_paged_window.restype = ctypes.c_int
+        lib.fa_forward_ragged_window_fp8.argtypes = list(lib.fa_forward_ragged_fp8.argtypes)
+        lib.fa_forward_ragged_window_fp8.restype = ctypes.c_int
+        lib.fa_forward_paged_window_fp8.argtypes = list(lib.fa_forward_paged_fp8.argtypes)
+        lib.fa_forward_paged_window_fp8.restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

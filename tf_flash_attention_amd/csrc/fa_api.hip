@@ -302,6 +302,48 @@ int check_paged(const fa_problem* p, int32_t kv_group, int32_t page) {
   return FA_OK;
 }
 
+// Sliding-window forms of the ragged and the paged forward: `base` is the un-windowed twin's
+// plan.  A window that reaches the capacity cuts nothing, and the call is the twin's tail form with its plan
+// (delegated).  Below it the block sees at most span_w = min(nk, W + nq - 1) keys somewhere in the capacity (where,
+// the device knows): grouped_plan's chunk formula over span_w, chunk boundaries at absolute multiples of the chunk,
+// and as many launched chunks as an interval of span_w keys can touch.  A pure function of the problem without b.
+struct WindowPlan {
+  GroupedPlan g;  // g.nchunks: the launched chunks per K/V slice
+  int32_t span_w, cap_chunks, delegated;
+};
+
+WindowPlan window_plan(const fa_problem* p, const GroupedPlan& base, int32_t window) {
+  WindowPlan w = {base, 0, base.nchunks, 0};
+  if (base.nchunks == 0) return w;  // outside the envelope (inside it: 1d, nq >= 1, nk >= 1)
+  const int64_t nq = p->q_seq[0], nk = p->k_seq[0];
+  w.span_w = (int32_t)(nk < window + nq - 1 ? nk : window + nq - 1);
+  w.delegated = window >= nk;
+  if (w.delegated) return w;
+  const int32_t min_chunk = base.rows <= 64 ? 512 : 1024;
+  const int32_t capped = ((w.span_w + kSplitMaxChunks - 1) / kSplitMaxChunks + kSplitTile - 1) / kSplitTile * kSplitTile;
+  w.g.chunk = capped > min_chunk ? capped : min_chunk;
+  w.cap_chunks = (int32_t)((nk + w.g.chunk - 1) / w.g.chunk);
+  const int32_t touched = (w.span_w + w.g.chunk - 2) / w.g.chunk + 1;
+  w.g.nchunks = touched < w.cap_chunks ? touched : w.cap_chunks;
+  return w;
+}
+
+int check_window(int32_t window) {
+  if (window < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "windowed forward: window = " + std::to_string(window) + " must be >= 1");
+  return FA_OK;
+}
+
+void write_window_plan(int32_t out[8], const WindowPlan& w) {
+  out[0] = w.g.nchunks;
+  out[1] = w.g.chunk;
+  out[2] = w.span_w;
+  out[3] = w.cap_chunks;
+  out[4] = w.g.pitch;
+  out[5] = w.g.rows;
+  out[6] = w.delegated;
+  out[7] = 0;
+}
+
 // Split-key routing of the fp16 backward's dQ pass: the forward's plan, where the
 // dQ kernel's 32-bit buffer offsets reach a slice's K / V channel rows (the b-free part of
 // bwd_f16_fast_supported).  Also a pure function of the problem WITHOUT b, and a subset of the
@@ -685,15 +727,21 @@ struct Kv8 {
   const float *k_scale, *v_scale;
 };
 
-// fa_forward_ragged, and fa_forward_ragged_fp8 with kv8: the same checks, plan, workspace and launches
+// fa_forward_ragged, and fa_forward_ragged_fp8 with kv8: the same checks, plan, workspace and launches.  With
+// `window` the sliding-window forms: the tail form itself where the window reaches the capacity, else the
+// window's plan and kernels.
 static int forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
                           const Kv8* kv8, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l,
-                          void* m, void* workspace, size_t workspace_bytes) {
+                          void* m, void* workspace, size_t workspace_bytes, const int32_t* window = nullptr) {
   const int st = check_ragged(p, kv_group);
   if (st != FA_OK) return st;
   const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
   if (kst != FA_OK) return kst;
-  const GroupedPlan gp = ragged_plan(p, kv_group);
+  const int wst = window ? check_window(*window) : FA_OK;
+  if (wst != FA_OK) return wst;
+  const WindowPlan wp = window_plan(p, ragged_plan(p, kv_group), window ? *window : 0x7fffffff);
+  const GroupedPlan& gp = wp.g;
+  const bool win = window && !wp.delegated;
   if (gp.nchunks == 0)
     return set_error(FA_ERR_UNSUPPORTED,
                      "ragged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
@@ -711,6 +759,8 @@ static int forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, c
   hipStream_t s = static_cast<hipStream_t>(stream);
   return fewq_slabs(p, {Q, K, V, O, l, m, workspace, kv8 ? 1 : 2}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
+    if (win)
+      return kv8 ? fa::launch_fwd_f16_window_ragged_fp8({fa8, *window}, s) : fa::launch_fwd_f16_window_ragged({ra, *window}, s);
     return kv8 ? fa::launch_fwd_f16_ragged_fp8(fa8, s) : fa::launch_fwd_f16_ragged(ra, s);
   });
 }
@@ -749,17 +799,21 @@ size_t fa_forward_paged_workspace_bytes(const fa_problem* p, int32_t kv_group, i
 static int forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
                          const void* V_pool, const Kv8* kv8, const int32_t* block_table, int32_t max_pages, int32_t page,
                          int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
-                         void* l, void* m, void* workspace, size_t workspace_bytes) {
+                         void* l, void* m, void* workspace, size_t workspace_bytes, const int32_t* window = nullptr) {
   const int st = check_paged(p, kv_group, page);
   if (st != FA_OK) return st;
   const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
   if (kst != FA_OK) return kst;
+  const int wst = window ? check_window(*window) : FA_OK;
+  if (wst != FA_OK) return wst;
   if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages must be >= 1");
   if ((int64_t)max_pages * page != p->k_seq[0])
     return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages * page = " + std::to_string((int64_t)max_pages * page) +
                                                   " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
   if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: num_pages must be >= 1");
-  const GroupedPlan gp = paged_plan(p, kv_group, page);
+  const WindowPlan wp = window_plan(p, paged_plan(p, kv_group, page), window ? *window : 0x7fffffff);
+  const GroupedPlan& gp = wp.g;
+  const bool win = window && !wp.delegated;
   if (gp.nchunks == 0)
     return set_error(FA_ERR_UNSUPPORTED,
                      "paged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
@@ -783,6 +837,8 @@ static int forward_paged(void* stream, const fa_problem* p, int32_t kv_group, co
   hipStream_t s = static_cast<hipStream_t>(stream);
   return fewq_slabs(p, {Q, nullptr, nullptr, O, l, m, workspace}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
+    if (win)
+      return kv8 ? fa::launch_fwd_f16_window_paged_fp8({pa8, *window}, s) : fa::launch_fwd_f16_window_paged({pa, *window}, s);
     return kv8 ? fa::launch_fwd_f16_paged_fp8(pa8, s) : fa::launch_fwd_f16_paged(pa, s);
   });
 }
@@ -802,6 +858,74 @@ int fa_forward_paged_fp8(void* stream, const fa_problem* p, int32_t kv_group, co
   const Kv8 kv8 = {k_scale, v_scale};
   return forward_paged(stream, p, kv_group, Q, K_pool8, V_pool8, &kv8, block_table, max_pages, page, num_pages, k_lens,
                        kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
+}
+
+// ---- the sliding-window forms (include/fa_api.h): the twins' paths with the window's plan
+
+int fa_forward_ragged_window_plan(const fa_problem* p, int32_t kv_group, int32_t window, int32_t out[8]) {
+  const int st = check_ragged(p, kv_group);
+  if (st != FA_OK) return st;
+  const int wst = check_window(window);
+  if (wst != FA_OK) return wst;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  write_window_plan(out, window_plan(p, ragged_plan(p, kv_group), window));
+  return FA_OK;
+}
+
+size_t fa_forward_ragged_window_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t window) {
+  if (check_ragged(p, kv_group) != FA_OK || check_window(window) != FA_OK) return 0;
+  const WindowPlan w = window_plan(p, ragged_plan(p, kv_group), window);
+  return w.g.nchunks ? grouped_ws_bytes(p, kv_group, w.g) : 0;
+}
+
+int fa_forward_paged_window_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window, int32_t out[8]) {
+  const int st = check_paged(p, kv_group, page);
+  if (st != FA_OK) return st;
+  const int wst = check_window(window);
+  if (wst != FA_OK) return wst;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  write_window_plan(out, window_plan(p, paged_plan(p, kv_group, page), window));
+  return FA_OK;
+}
+
+size_t fa_forward_paged_window_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window) {
+  if (check_paged(p, kv_group, page) != FA_OK || check_window(window) != FA_OK) return 0;
+  const WindowPlan w = window_plan(p, paged_plan(p, kv_group, page), window);
+  return w.g.nchunks ? grouped_ws_bytes(p, kv_group, w.g) : 0;
+}
+
+int fa_forward_ragged_window(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K,
+                             const void* V, const int32_t* k_lens, int32_t kv_per_len, int32_t window, void* O, void* l,
+                             void* m, void* workspace, size_t workspace_bytes) {
+  return forward_ragged(stream, p, kv_group, Q, K, V, nullptr, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes,
+                        &window);
+}
+
+int fa_forward_ragged_window_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K8,
+                                 const void* V8, const float* k_scale, const float* v_scale, const int32_t* k_lens,
+                                 int32_t kv_per_len, int32_t window, void* O, void* l, void* m, void* workspace,
+                                 size_t workspace_bytes) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_ragged(stream, p, kv_group, Q, K8, V8, &kv8, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes,
+                        &window);
+}
+
+int fa_forward_paged_window(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
+                            const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page,
+                            int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t window, void* O, void* l,
+                            void* m, void* workspace, size_t workspace_bytes) {
+  return forward_paged(stream, p, kv_group, Q, K_pool, V_pool, nullptr, block_table, max_pages, page, num_pages, k_lens,
+                       kv_per_len, 1, O, l, m, workspace, workspace_bytes, &window);
+}
+
+int fa_forward_paged_window_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool8,
+                                const void* V_pool8, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                                int32_t max_pages, int32_t page, int64_t num_pages, const int32_t* k_lens,
+                                int32_t kv_per_len, int32_t window, void* O, void* l, void* m, void* workspace,
+                                size_t workspace_bytes) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_paged(stream, p, kv_group, Q, K_pool8, V_pool8, &kv8, block_table, max_pages, page, num_pages, k_lens,
+                       kv_per_len, 1, O, l, m, workspace, workspace_bytes, &window);
 }
 
 size_t fa_backward_workspace_bytes(const fa_problem* p) {
@@ -1080,7 +1204,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
 }
 
 }  // extern "C"

@@ -103,6 +103,16 @@ struct PagedFp8Args {
   const float* v_scale;
 };
 
+// the sliding-window forms of the four forwards above (fa_fwd_f16_window.h): `a` with the window's plan in place
+// of the capacity's.  a's SplitArgs holds nchunks = the launched chunks per K/V slice (relative to the chunk that
+// holds the window's first key, a device value) and the records [b_kv][nchunks]; its tail_causal is not read:
+// the tail rule's positions are implied.
+template <class Args>
+struct WindowOf {
+  Args a;
+  int32_t window;  // W: query i sees the keys [max(0, pos_i - W + 1), pos_i], pos_i = len - nq + i; 1 <= W < nk
+};
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;
@@ -207,6 +217,13 @@ hipError_t launch_fwd_f16_paged(const PagedArgs& pa, hipStream_t s);
 // fa_fwd_f16_ragged_fp8.hip, fa_fwd_f16_paged_fp8.hip
 hipError_t launch_fwd_f16_ragged_fp8(const RaggedFp8Args& fa8, hipStream_t s);
 hipError_t launch_fwd_f16_paged_fp8(const PagedFp8Args& pa8, hipStream_t s);
+// the same four with a sliding window: work for the window's chunks only — fa_fwd_f16_window_ragged.hip,
+// _window_paged.hip, _window_ragged_fp8.hip, _window_paged_fp8.hip (shared: fa_fwd_f16_window.h)
+hipError_t launch_fwd_f16_window_ragged(const WindowOf<RaggedArgs>& wa, hipStream_t s);
+hipError_t launch_fwd_f16_window_merge(const WindowOf<RaggedArgs>& wa, hipStream_t s);  // the merge of all four
+hipError_t launch_fwd_f16_window_paged(const WindowOf<PagedArgs>& wa, hipStream_t s);
+hipError_t launch_fwd_f16_window_ragged_fp8(const WindowOf<RaggedFp8Args>& wa, hipStream_t s);
+hipError_t launch_fwd_f16_window_paged_fp8(const WindowOf<PagedFp8Args>& wa, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

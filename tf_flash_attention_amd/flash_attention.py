@@ -712,7 +712,22 @@ def _scale_ptr(t):
     return t.data_ptr() if t is not None else None
 
 
-def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=None, v_scale=None):
+def _decode_window(what, window_size, tail_causal, nq):
+    """The window of a windowed ``ragged_1d`` / ``paged_1d`` call as an int, or None without one."""
+    if window_size is None:
+        return None
+    if isinstance(window_size, bool) or not isinstance(window_size, int):
+        raise TypeError(f"window_size must be an int or None, got {type(window_size).__name__}")
+    if window_size < 1:
+        raise InvalidArgumentError(f"{what}: window_size must be >= 1, but window_size = {window_size} was received")
+    if nq > 1 and not tail_causal:
+        raise InvalidArgumentError(f"{what}: a window places the Nq = {nq} queries at the last Nq positions of the "
+                                   "sequence, which is the tail rule, so window_size with Nq > 1 requires "
+                                   "tail_causal=True")
+    return min(window_size, 2 ** 31 - 1)  # (any window at or above the capacity is the tail rule)
+
+
+def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=None, v_scale=None, window_size=None):
     """Attention of a few queries over a padded K/V cache: Q ``batch + (Hq, C, Nq)``, K ``batch + (Hk, C, cap)``,
     V ``batch + (Hk, Cv, cap)`` with Hq = g * Hk read from the shapes (query head h attends K/V head h // g), and
     ``k_lens`` an int32 tensor of shape ``batch`` on the same device (0-d without a leading batch axis): sequence
@@ -728,6 +743,14 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=N
     ``k_scale`` and ``v_scale`` are float32 tensors of shape ``(Hk,)`` on the device of Q, or None for 1.0: the true
     key of head h is ``k_scale[h] * K[..., h, :, :]``, the true value ``v_scale[h] * V[..., h, :, :]``
     (``quantize_kv_fp8`` makes both).  The kernels read the scales, never the host.  A float16 cache takes no scale.
+
+    A sliding window: ``window_size`` = W >= 1 (None: no window).  The queries sit at the last Nq positions of the
+    sequence, so Nq > 1 requires ``tail_causal=True`` (for Nq = 1 either value is accepted): query i at position
+    ``pos = k_lens[s] - Nq + i`` sees the W keys ``max(0, pos - W + 1) <= j <= pos``, its own position included
+    (``local_1d``'s window with ``is_causal``).  The launched work, the workspace and the time follow W + Nq - 1,
+    not the capacity; ``W >= cap`` is the tail-causal call itself, bit for bit.  With
+    ``lo = max(0, k_lens[s] - Nq - W + 1)``, keys below ``lo // 64 * 64`` are never read.  The at most 63 keys
+    between that and ``lo`` are read and masked, so they must be finite (they are the sequence's own earlier keys).
     Returns ``O`` or ``(O, l, m)``."""
     Qb, Qs, Q_ch, Kb, Ks, V_ch, g = verify_grouped_shapes(1, Q.shape, K.shape, V.shape)
     dt = _dtype_id(Q, True)
@@ -745,10 +768,14 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=N
     if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, K, V)):
         raise RuntimeError("ragged_1d is inference only and has no gradient; call it under torch.no_grad() or "
                            "detach its inputs")
+    window = _decode_window("ragged_1d", window_size, tail_causal, int(Qs[0]))
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(Qb), Qs, Ks, Q_ch, V_ch)
     L = _lib.lib()
-    plan = (ctypes.c_int32 * 6)()
-    st = L.fa_forward_ragged_plan(prob, g, plan)
+    plan = (ctypes.c_int32 * 8)()
+    if window is None:
+        st = L.fa_forward_ragged_plan(prob, g, plan)
+    else:
+        st = L.fa_forward_ragged_window_plan(prob, g, window, plan)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     if plan[0] == 0:
@@ -760,10 +787,22 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=N
     O = torch.empty(Qb + (V_ch,) + Qs, dtype=Q.dtype, device=Q.device)
     l = torch.empty(Qb + Qs, dtype=torch.float32, device=Q.device)
     m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
-    ws_bytes = int(L.fa_forward_ragged_workspace_bytes(prob, g))
+    if window is None:
+        ws_bytes = int(L.fa_forward_ragged_workspace_bytes(prob, g))
+    else:
+        ws_bytes = int(L.fa_forward_ragged_window_workspace_bytes(prob, g, window))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        if fp8:
+        if window is not None and fp8:
+            st = L.fa_forward_ragged_window_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
+                                                V.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
+                                                k_lens.data_ptr(), kv_per_len, window, O.data_ptr(), l.data_ptr(),
+                                                m.data_ptr(), ws.data_ptr(), ws_bytes)
+        elif window is not None:
+            st = L.fa_forward_ragged_window(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
+                                            V.data_ptr(), k_lens.data_ptr(), kv_per_len, window, O.data_ptr(),
+                                            l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+        elif fp8:
             st = L.fa_forward_ragged_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
                                          _scale_ptr(k_scale), _scale_ptr(v_scale), k_lens.data_ptr(), kv_per_len,
                                          int(bool(tail_causal)), O.data_ptr(), l.data_ptr(), m.data_ptr(),
@@ -785,7 +824,7 @@ _PAGE_CONDITION = "the page size (the last axis of K_pool and V_pool) must be a 
 
 
 def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False, k_scale=None,
-             v_scale=None):
+             v_scale=None, window_size=None):
     """``ragged_1d`` over a paged K/V cache: Q ``batch + (Hq, C, Nq)``, ``K_pool`` ``[num_pages, Hk, C, page]``,
     ``V_pool`` ``[num_pages, Hk, Cv, page]`` with Hq = g * Hk read from the shapes, ``block_table`` an int32 tensor
     ``batch + (max_pages,)`` and ``k_lens`` an int32 tensor of shape ``batch``, both on the device of Q.  A page
@@ -808,6 +847,22 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
 
         new8, _ = quantize_kv_fp8(new, head_axis=0, scale=k_scale)
         K_pool[block_table[s, pos // page], :, :, pos % page] = new8
+
+    A sliding window: ``window_size`` = W >= 1 (None: no window), with ``ragged_1d``'s rule: Nq > 1 requires
+    ``tail_causal=True``, and query i at position ``pos = k_lens[s] - Nq + i`` sees the W keys
+    ``max(0, pos - W + 1) <= j <= pos``.  Work, workspace and time follow W + Nq - 1, not the capacity; ``W >= cap``
+    is the tail-causal call itself.  With ``lo = max(0, k_lens[s] - Nq - W + 1)``: keys below ``lo // 64 * 64`` are
+    never read, and the table entries of pages wholly below that key are never loaded, like those past the last
+    live page, so such pages may be freed and reused and their entries may hold anything.  The at most 63 keys
+    between ``lo // 64 * 64`` and ``lo`` are read and masked: they must be finite (they lie on a page the
+    sequence still owns).  Attention sinks (the first S keys stay visible) compose from two calls and
+    ``merge_partials``::
+
+        O1, l1, m1 = paged_1d(Q, K_pool, V_pool, table, k_lens, tail_causal=True, returning_l_m=True, window_size=W)
+        O2, l2, m2 = paged_1d(Q, K_pool, V_pool, table, k_lens.clamp(max=S), returning_l_m=True)
+        O, l, m = merge_partials([O1, O2], [l1, l2], [m1, m2])
+
+    (exact where the two key sets are disjoint: S <= k_lens - Nq - W + 1).
 
     Inference only (no gradient); float16 only; the page size must be a multiple of 64; outside the envelope the
     call raises NotImplementedError (there is no gather fallback).  Returns ``O`` or ``(O, l, m)``."""
@@ -857,10 +912,14 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
     cap = max_pages * page
     if cap > 2 ** 30:
         raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    window = _decode_window("paged_1d", window_size, tail_causal, nq)
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_ch)
     L = _lib.lib()
-    plan = (ctypes.c_int32 * 6)()
-    st = L.fa_forward_paged_plan(prob, g, page, plan)
+    plan = (ctypes.c_int32 * 8)()
+    if window is None:
+        st = L.fa_forward_paged_plan(prob, g, page, plan)
+    else:
+        st = L.fa_forward_paged_window_plan(prob, g, page, window, plan)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     if plan[0] == 0:
@@ -873,10 +932,24 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
     O = torch.empty(batch + (hq, v_ch, nq), dtype=Q.dtype, device=Q.device)
     l = torch.empty(batch + (hq, nq), dtype=torch.float32, device=Q.device)
     m = torch.empty(batch + (hq, nq), dtype=Q.dtype, device=Q.device)
-    ws_bytes = int(L.fa_forward_paged_workspace_bytes(prob, g, page))
+    if window is None:
+        ws_bytes = int(L.fa_forward_paged_workspace_bytes(prob, g, page))
+    else:
+        ws_bytes = int(L.fa_forward_paged_window_workspace_bytes(prob, g, page, window))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        if fp8:
+        if window is not None and fp8:
+            st = L.fa_forward_paged_window_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
+                                               V_pool.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
+                                               block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(),
+                                               hk, window, O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(),
+                                               ws_bytes)
+        elif window is not None:
+            st = L.fa_forward_paged_window(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
+                                           V_pool.data_ptr(), block_table.data_ptr(), max_pages, page, num_pages,
+                                           k_lens.data_ptr(), hk, window, O.data_ptr(), l.data_ptr(), m.data_ptr(),
+                                           ws.data_ptr(), ws_bytes)
+        elif fp8:
             st = L.fa_forward_paged_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
                                         V_pool.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
                                         block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(), hk,
