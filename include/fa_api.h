@@ -328,6 +328,72 @@ int fa_forward_paged_window_fp8(void* stream, const fa_problem* p, int32_t kv_gr
                                 void* O, void* l, void* m,
                                 void* workspace, size_t workspace_bytes);
 
+/* Query-blocked forwards (chunked prefill, long speculative drafts): fa_forward_ragged / fa_forward_paged and their
+ * _fp8 forms for ANY nq >= 1, with the same layouts, arguments and semantics.  tail_causal == 0: every query sees
+ * the keys [0, L), L the clamped length of its slice.  tail_causal != 0: the nq queries are the last nq positions,
+ * query i sees j <= L - nq + i; a query before position 0 gets the empty row (O = 0, l = 0, every byte of m 0xFA).
+ * A batch that mixes prefill with decode right-aligns each sequence's real queries in the nq slots; the padding
+ * queries in front compute earlier positions' rows, or empty rows.
+ *
+ * Envelope: the twins' without the row cap: fp16, 1d sequences, FA_FULL, max(d, v_d) <= 128, 1 <= kv_group <= 128,
+ * nq >= 1, nk >= 1, and page % 64 == 0 in the paged forms.  Outside it FA_ERR_UNSUPPORTED with nothing written.
+ * Argument errors, b == 0 and FA_ERR_WORKSPACE_TOO_SMALL with nothing written are the twins'; so are: no host
+ * synchronisation, no host read of k_lens, block_table or the scales, replayable from a captured graph.
+ *
+ * Block shape (a pure function of the problem WITHOUT b): P_b = the largest power of two with
+ * kv_group * P_b <= 128, rows = kv_group * P_b, nqb = ceil(nq / P_b) query blocks; block qb holds the queries
+ * [qb * P_b, min(nq, (qb + 1) * P_b)) of all kv_group heads.
+ * nqb == 1 (kv_group * next_pow2(nq) <= 128): the call IS the un-blocked twin, with its plan, workspace bytes and
+ *   kernels, bit for bit.
+ * nqb >= 2: one workgroup per (K/V slice, query block, key chunk) and a merge.  With
+ *     kmax = max(1, 64 / nqb), min_chunk = 512 where rows <= 64, else 1024,
+ *     chunk = max(min_chunk, ceil(ceil(nk / 64) / kmax) * 64), nchunks = ceil(nk / chunk):
+ *   the blocks already fill the GPU, so the more blocks the fewer chunks.  (64 / nqb is a starting rule; DESIGN.md
+ *   3.14 says what was and was not measured.)  Under the tail rule block qb sees the keys [0, L_b),
+ *   L_b = clamp(L - nq + min(nq, (qb + 1) * P_b), 0, L): its workgroups of chunks at or past L_b return at once, and
+ *   tiles at or past L_b are never staged.  The workspace is b / kv_group * nqb * nchunks records of
+ *   rows * (v_d + 3) floats, rounded up to 256 bytes.
+ * The plan functions (host-only; pure functions of the problem WITHOUT b, the lengths or the table) write
+ *   out[0] chunks (0 outside the envelope; then all of out[] is 0)    out[3] rows
+ *   out[1] keys per chunk                                            out[4] nqb
+ *   out[2] P_b                                                       out[5] 1 if delegated to the twin (nqb == 1):
+ *   out[6], out[7] reserved, 0                                              out[0], out[1] are then the twin's plan
+ * The FP8 forms use the fp16 plan and workspace functions, as their twins do.
+ *
+ * Never read: keys at or past L, whatever they hold; in the paged forms the table entries of pages without a key
+ *   below L.  Loaded entries and lengths are clamped as in the twins.  No unwritten workspace word reaches a result.
+ * A slice's bits do not depend on b or on the other slices' lengths; the paged bits are the ragged ones on the
+ *   gathered cache; the FP8 bits with null or unit scales are the fp16 ones on the converted cache.  The kernel
+ *   instance is chosen per call, so a block's bits do not depend on how many queries the last block holds. */
+int fa_forward_ragged_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t out[8]);
+int fa_forward_paged_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[8]);
+size_t fa_forward_ragged_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group);
+size_t fa_forward_paged_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page);
+int fa_forward_ragged_prefill(void* stream, const fa_problem* p, int32_t kv_group,
+                              const void* Q, const void* K, const void* V,
+                              const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                              void* O, void* l, void* m,
+                              void* workspace, size_t workspace_bytes);
+int fa_forward_paged_prefill(void* stream, const fa_problem* p, int32_t kv_group,
+                             const void* Q, const void* K_pool, const void* V_pool,
+                             const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                             const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                             void* O, void* l, void* m,
+                             void* workspace, size_t workspace_bytes);
+int fa_forward_ragged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                                  const void* Q, const void* K8, const void* V8,
+                                  const float* k_scale, const float* v_scale,
+                                  const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                                  void* O, void* l, void* m,
+                                  void* workspace, size_t workspace_bytes);
+int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                                 const void* Q, const void* K_pool8, const void* V_pool8,
+                                 const float* k_scale, const float* v_scale,
+                                 const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                                 const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                                 void* O, void* l, void* m,
+                                 void* workspace, size_t workspace_bytes);
+
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);

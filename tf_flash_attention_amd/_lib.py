@@ -52,6 +52,14 @@ EXPORTED_SYMBOLS = (
     "fa_forward_paged_window",
     "fa_forward_ragged_window_fp8",
     "fa_forward_paged_window_fp8",
+    "fa_forward_ragged_prefill_plan",
+    "fa_forward_paged_prefill_plan",
+    "fa_forward_ragged_prefill_workspace_bytes",
+    "fa_forward_paged_prefill_workspace_bytes",
+    "fa_forward_ragged_prefill",
+    "fa_forward_paged_prefill",
+    "fa_forward_ragged_prefill_fp8",
+    "fa_forward_paged_prefill_fp8",
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_backward_split_plan",
@@ -200,6 +208,25 @@ def _declare(lib):
         lib.fa_forward_ragged_window_fp8.restype = ctypes.c_int
         lib.fa_forward_paged_window_fp8.argtypes = list(lib.fa_forward_paged_fp8.argtypes)
         lib.fa_forward_paged_window_fp8.restype = ctypes.c_int
+    # (absent from a library built before the query-blocked forwards, as above): the twins' argument lists
+    if hasattr(lib, "fa_forward_ragged_prefill"):
+        i32 = ctypes.c_int32
+        lib.fa_forward_ragged_prefill_plan.argtypes = [P, i32, ctypes.POINTER(i32)]
+        lib.fa_forward_ragged_prefill_plan.restype = ctypes.c_int
+        lib.fa_forward_paged_prefill_plan.argtypes = [P, i32, i32, ctypes.POINTER(i32)]
+        lib.fa_forward_paged_prefill_plan.restype = ctypes.c_int
+        lib.fa_forward_ragged_prefill_workspace_bytes.argtypes = [P, i32]
+        lib.fa_forward_ragged_prefill_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_forward_paged_prefill_workspace_bytes.argtypes = [P, i32, i32]
+        lib.fa_forward_paged_prefill_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_forward_ragged_prefill.argtypes = list(lib.fa_forward_ragged.argtypes)
+        lib.fa_forward_ragged_prefill.restype = ctypes.c_int
+        lib.fa_forward_paged_prefill.argtypes = list(lib.fa_forward_paged.argtypes)
+        lib.fa_forward_paged_prefill.restype = ctypes.c_int
+        lib.fa_forward_ragged_prefill_fp8.argtypes = list(lib.fa_forward_ragged_fp8.argtypes)
+        lib.fa_forward_ragged_prefill_fp8.restype = ctypes.c_int
+        lib.fa_forward_paged_prefill_fp8.argtypes = list(lib.fa_forward_paged_fp8.argtypes)
+        lib.fa_forward_paged_prefill_fp8.restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

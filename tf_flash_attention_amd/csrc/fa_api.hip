@@ -344,6 +344,67 @@ void write_window_plan(int32_t out[8], const WindowPlan& w) {
   out[7] = 0;
 }
 
+// Query-blocked forms of the ragged and the paged forward: `twin` is the un-blocked twin's plan.
+// Inside the twin's envelope (kv_group * next_pow2(nq) <= 128: one block) the call is the twin's with its plan
+// (delegated).  Outside it the queries are cut into nqb = ceil(nq / pb) blocks of pb queries, pb the largest power
+// of two with kv_group * pb <= 128, one workgroup each per key chunk.  The chunk split exists to fill the GPU where
+// the workgroups are few, the blocks already supply them, and every (block, chunk) costs a record of
+// rows * (v_d + 3) floats: so at most kmax = max(1, 64 / nqb) chunks, of at least the twins' min_chunk keys.  A
+// pure function of the problem without b, the lengths or the table.
+struct PrefillPlan {
+  GroupedPlan g;  // delegated: the twin's; else pitch = pb, rows = kv_group * pb, the chunks below
+  int32_t pb, rows, nqb, delegated;
+};
+
+PrefillPlan prefill_plan(const fa_problem* p, int32_t kv_group, const GroupedPlan& twin, int32_t page_keys) {
+  PrefillPlan w = {};
+  if (fa_validate(p) != FA_OK || p->seq_dims != 1 || kv_group < 1 || kv_group > kGroupMaxRows) return w;
+  const int64_t nq = p->q_seq[0], nk = p->k_seq[0];
+  if (nq < 1 || nk < 1) return w;
+  int32_t pb = 1;
+  while (2 * pb * kv_group <= kGroupMaxRows) pb *= 2;
+  const int32_t nqb = (int32_t)((nq + pb - 1) / pb);
+  if (twin.nchunks != 0) {  // (then nqb == 1)
+    w = {twin, pb, kv_group * pb, nqb, 1};
+    return w;
+  }
+  if (nqb < 2 || p->dtype != FA_F16 || p->policy != FA_FULL || p->d > 128 || p->v_d > 128 || page_keys % kSplitTile != 0)
+    return w;
+#ifdef FA_DIAG
+  // a pinned forward variant keeps measuring the kernel it names
+  if (fa::diag_variant("FA_FWD_VARIANT") >= 0) return w;
+#endif
+  w = {twin, pb, kv_group * pb, nqb, 0};
+  w.g.pitch = pb;
+  w.g.rows = w.rows;
+  w.g.kb = w.g.k_first = 0;
+  w.g.ke = (int32_t)nk;
+  const int32_t kmax = kSplitMaxChunks / nqb > 1 ? kSplitMaxChunks / nqb : 1;
+  const int32_t min_chunk = w.rows <= 64 ? 512 : 1024;
+  const int64_t tiles = (nk + kSplitTile - 1) / kSplitTile;
+  const int64_t capped = (tiles + kmax - 1) / kmax * kSplitTile;
+  w.g.chunk = (int32_t)(capped > min_chunk ? capped : min_chunk);
+  w.g.nchunks = (int32_t)((nk + w.g.chunk - 1) / w.g.chunk);
+  return w;
+}
+
+size_t prefill_ws_bytes(const fa_problem* p, int32_t kv_group, const PrefillPlan& w) {
+  if (w.delegated) return grouped_ws_bytes(p, kv_group, w.g);
+  return align_up((size_t)(p->b / kv_group) * (size_t)w.nqb * (size_t)w.g.nchunks *
+                  (size_t)fa::fewq_record_floats(p->v_d, w.rows) * sizeof(float));
+}
+
+void write_prefill_plan(int32_t out[8], const PrefillPlan& w) {
+  const bool in = w.g.nchunks != 0;
+  out[0] = w.g.nchunks;
+  out[1] = in ? w.g.chunk : 0;
+  out[2] = in ? w.pb : 0;
+  out[3] = in ? w.rows : 0;
+  out[4] = in ? w.nqb : 0;
+  out[5] = in ? w.delegated : 0;
+  out[6] = out[7] = 0;
+}
+
 // Split-key routing of the fp16 backward's dQ pass: the forward's plan, where the
 // dQ kernel's 32-bit buffer offsets reach a slice's K / V channel rows (the b-free part of
 // bwd_f16_fast_supported).  Also a pure function of the problem WITHOUT b, and a subset of the
@@ -497,12 +558,15 @@ struct FewqPtrs {
 // The launches of a few-query forward over the p->b / g K/V slices, g query slices each, in slabs of at most
 // fwd_f16_fewq_max_batch slices: one launch pair covers every realistic batch; the loop only keeps the grids
 // inside 2^31 blocks.  Sets b, the slab's pointers and the workspace (records of `rows` floats a row) in *sa,
-// which lies inside the arguments that launch(b0) sends; b0 is the slab's first K/V slice.
+// which lies inside the arguments that launch(b0) sends; b0 is the slab's first K/V slice.  nqb: the query blocks
+// of a query-blocked forward, which multiply a slice's partial workgroups and records (its merge threads are
+// g * nq a channel either way).
 template <class Launch>
-int fewq_slabs(const fa_problem* p, const FewqPtrs& t, int32_t g, int64_t rows, fa::SplitArgs* sa, Launch&& launch) {
+int fewq_slabs(const fa_problem* p, const FewqPtrs& t, int32_t g, int64_t rows, fa::SplitArgs* sa, Launch&& launch,
+               int32_t nqb = 1) {
   fa::FwdArgs& a = sa->f;
   const int64_t nq = a.rule.q.n, nk = a.rule.k.n, bkv = p->b / g;
-  const int64_t bmax = FA_SLAB_LIMIT(fa::fwd_f16_fewq_max_batch(sa->nchunks, p->v_d, g * nq));
+  const int64_t bmax = FA_SLAB_LIMIT(fa::fwd_f16_fewq_max_batch(sa->nchunks * nqb, p->v_d, g * nq));
   for (int64_t b0 = 0; b0 < bkv; b0 += bmax) {
     a.b = bkv - b0 < bmax ? bkv - b0 : bmax;
     a.Q = static_cast<const uint16_t*>(t.Q) + b0 * g * p->d * nq;
@@ -511,7 +575,7 @@ int fewq_slabs(const fa_problem* p, const FewqPtrs& t, int32_t g, int64_t rows, 
     a.O = static_cast<uint16_t*>(t.O) + b0 * g * p->v_d * nq;
     a.l = static_cast<float*>(t.l) + b0 * g * nq;
     a.m = static_cast<uint16_t*>(t.m) + b0 * g * nq;
-    sa->ws = static_cast<float*>(t.workspace) + b0 * sa->nchunks * fa::fewq_record_floats(p->v_d, rows);
+    sa->ws = static_cast<float*>(t.workspace) + b0 * nqb * sa->nchunks * fa::fewq_record_floats(p->v_d, rows);
     FA_DIAG_SLAB();
     const hipError_t e = launch(b0);
     if (e != hipSuccess)
@@ -729,10 +793,12 @@ struct Kv8 {
 
 // fa_forward_ragged, and fa_forward_ragged_fp8 with kv8: the same checks, plan, workspace and launches.  With
 // `window` the sliding-window forms: the tail form itself where the window reaches the capacity, else the
-// window's plan and kernels.
+// window's plan and kernels.  With `prefill` the query-blocked forms: the twin itself where one block holds the
+// queries, else the blocked plan and kernels.
 static int forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
                           const Kv8* kv8, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l,
-                          void* m, void* workspace, size_t workspace_bytes, const int32_t* window = nullptr) {
+                          void* m, void* workspace, size_t workspace_bytes, const int32_t* window = nullptr,
+                          bool prefill = false) {
   const int st = check_ragged(p, kv_group);
   if (st != FA_OK) return st;
   const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
@@ -740,15 +806,20 @@ static int forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, c
   const int wst = window ? check_window(*window) : FA_OK;
   if (wst != FA_OK) return wst;
   const WindowPlan wp = window_plan(p, ragged_plan(p, kv_group), window ? *window : 0x7fffffff);
-  const GroupedPlan& gp = wp.g;
+  const PrefillPlan pp = prefill ? prefill_plan(p, kv_group, wp.g, 0) : PrefillPlan{};
+  const bool blocked = prefill && !pp.delegated;
+  const GroupedPlan& gp = blocked ? pp.g : wp.g;
   const bool win = window && !wp.delegated;
   if (gp.nchunks == 0)
     return set_error(FA_ERR_UNSUPPORTED,
-                     "ragged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
-                     "kv_group * pitch <= 128, nq >= 1, nk >= 1)");
-  if (!workspace || workspace_bytes < grouped_ws_bytes(p, kv_group, gp))
+                     prefill ? "ragged prefill forward: outside the envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                               "1 <= kv_group <= 128, nq >= 1, nk >= 1)"
+                             : "ragged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                               "kv_group * pitch <= 128, nq >= 1, nk >= 1)");
+  if (!workspace || workspace_bytes < (blocked ? prefill_ws_bytes(p, kv_group, pp) : grouped_ws_bytes(p, kv_group, gp)))
     return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
-                     "forward workspace is smaller than fa_forward_ragged_workspace_bytes()");
+                     prefill ? "forward workspace is smaller than fa_forward_ragged_prefill_workspace_bytes()"
+                             : "forward workspace is smaller than fa_forward_ragged_workspace_bytes()");
   FA_DIAG_COUNT(0);
   if (p->b == 0) return FA_OK;
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
@@ -761,8 +832,10 @@ static int forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, c
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
     if (win)
       return kv8 ? fa::launch_fwd_f16_window_ragged_fp8({fa8, *window}, s) : fa::launch_fwd_f16_window_ragged({ra, *window}, s);
+    if (blocked)
+      return kv8 ? fa::launch_fwd_f16_prefill_ragged_fp8({fa8, pp.nqb}, s) : fa::launch_fwd_f16_prefill_ragged({ra, pp.nqb}, s);
     return kv8 ? fa::launch_fwd_f16_ragged_fp8(fa8, s) : fa::launch_fwd_f16_ragged(ra, s);
-  });
+  }, blocked ? pp.nqb : 1);
 }
 
 int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
@@ -799,7 +872,8 @@ size_t fa_forward_paged_workspace_bytes(const fa_problem* p, int32_t kv_group, i
 static int forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
                          const void* V_pool, const Kv8* kv8, const int32_t* block_table, int32_t max_pages, int32_t page,
                          int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
-                         void* l, void* m, void* workspace, size_t workspace_bytes, const int32_t* window = nullptr) {
+                         void* l, void* m, void* workspace, size_t workspace_bytes, const int32_t* window = nullptr,
+                         bool prefill = false) {
   const int st = check_paged(p, kv_group, page);
   if (st != FA_OK) return st;
   const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
@@ -812,15 +886,20 @@ static int forward_paged(void* stream, const fa_problem* p, int32_t kv_group, co
                                                   " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
   if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: num_pages must be >= 1");
   const WindowPlan wp = window_plan(p, paged_plan(p, kv_group, page), window ? *window : 0x7fffffff);
-  const GroupedPlan& gp = wp.g;
+  const PrefillPlan pp = prefill ? prefill_plan(p, kv_group, wp.g, page) : PrefillPlan{};
+  const bool blocked = prefill && !pp.delegated;
+  const GroupedPlan& gp = blocked ? pp.g : wp.g;
   const bool win = window && !wp.delegated;
   if (gp.nchunks == 0)
     return set_error(FA_ERR_UNSUPPORTED,
-                     "paged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
-                     "kv_group * pitch <= 128, nq >= 1, nk >= 1, page % 64 == 0)");
-  if (!workspace || workspace_bytes < grouped_ws_bytes(p, kv_group, gp))
+                     prefill ? "paged prefill forward: outside the envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                               "1 <= kv_group <= 128, nq >= 1, nk >= 1, page % 64 == 0)"
+                             : "paged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                               "kv_group * pitch <= 128, nq >= 1, nk >= 1, page % 64 == 0)");
+  if (!workspace || workspace_bytes < (blocked ? prefill_ws_bytes(p, kv_group, pp) : grouped_ws_bytes(p, kv_group, gp)))
     return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
-                     "forward workspace is smaller than fa_forward_paged_workspace_bytes()");
+                     prefill ? "forward workspace is smaller than fa_forward_paged_prefill_workspace_bytes()"
+                             : "forward workspace is smaller than fa_forward_paged_workspace_bytes()");
   FA_DIAG_COUNT(0);
   if (p->b == 0) return FA_OK;
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
@@ -839,8 +918,10 @@ static int forward_paged(void* stream, const fa_problem* p, int32_t kv_group, co
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
     if (win)
       return kv8 ? fa::launch_fwd_f16_window_paged_fp8({pa8, *window}, s) : fa::launch_fwd_f16_window_paged({pa, *window}, s);
+    if (blocked)
+      return kv8 ? fa::launch_fwd_f16_prefill_paged_fp8({pa8, pp.nqb}, s) : fa::launch_fwd_f16_prefill_paged({pa, pp.nqb}, s);
     return kv8 ? fa::launch_fwd_f16_paged_fp8(pa8, s) : fa::launch_fwd_f16_paged(pa, s);
-  });
+  }, blocked ? pp.nqb : 1);
 }
 
 int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
@@ -926,6 +1007,70 @@ int fa_forward_paged_window_fp8(void* stream, const fa_problem* p, int32_t kv_gr
   const Kv8 kv8 = {k_scale, v_scale};
   return forward_paged(stream, p, kv_group, Q, K_pool8, V_pool8, &kv8, block_table, max_pages, page, num_pages, k_lens,
                        kv_per_len, 1, O, l, m, workspace, workspace_bytes, &window);
+}
+
+// ---- the query-blocked forms (include/fa_api.h): the twins' paths with the blocked plan
+
+int fa_forward_ragged_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t out[8]) {
+  const int st = check_ragged(p, kv_group);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  write_prefill_plan(out, prefill_plan(p, kv_group, ragged_plan(p, kv_group), 0));
+  return FA_OK;
+}
+
+size_t fa_forward_ragged_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group) {
+  if (check_ragged(p, kv_group) != FA_OK) return 0;
+  const PrefillPlan w = prefill_plan(p, kv_group, ragged_plan(p, kv_group), 0);
+  return w.g.nchunks ? prefill_ws_bytes(p, kv_group, w) : 0;
+}
+
+int fa_forward_paged_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[8]) {
+  const int st = check_paged(p, kv_group, page);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  write_prefill_plan(out, prefill_plan(p, kv_group, paged_plan(p, kv_group, page), page));
+  return FA_OK;
+}
+
+size_t fa_forward_paged_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page) {
+  if (check_paged(p, kv_group, page) != FA_OK) return 0;
+  const PrefillPlan w = prefill_plan(p, kv_group, paged_plan(p, kv_group, page), page);
+  return w.g.nchunks ? prefill_ws_bytes(p, kv_group, w) : 0;
+}
+
+int fa_forward_ragged_prefill(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K,
+                              const void* V, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
+                              void* l, void* m, void* workspace, size_t workspace_bytes) {
+  return forward_ragged(stream, p, kv_group, Q, K, V, nullptr, k_lens, kv_per_len, tail_causal, O, l, m, workspace,
+                        workspace_bytes, nullptr, true);
+}
+
+int fa_forward_ragged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K8,
+                                  const void* V8, const float* k_scale, const float* v_scale, const int32_t* k_lens,
+                                  int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m, void* workspace,
+                                  size_t workspace_bytes) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_ragged(stream, p, kv_group, Q, K8, V8, &kv8, k_lens, kv_per_len, tail_causal, O, l, m, workspace,
+                        workspace_bytes, nullptr, true);
+}
+
+int fa_forward_paged_prefill(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
+                             const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page,
+                             int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
+                             void* l, void* m, void* workspace, size_t workspace_bytes) {
+  return forward_paged(stream, p, kv_group, Q, K_pool, V_pool, nullptr, block_table, max_pages, page, num_pages, k_lens,
+                       kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes, nullptr, true);
+}
+
+int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool8,
+                                 const void* V_pool8, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                                 int32_t max_pages, int32_t page, int64_t num_pages, const int32_t* k_lens,
+                                 int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m, void* workspace,
+                                 size_t workspace_bytes) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_paged(stream, p, kv_group, Q, K_pool8, V_pool8, &kv8, block_table, max_pages, page, num_pages, k_lens,
+                       kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes, nullptr, true);
 }
 
 size_t fa_backward_workspace_bytes(const fa_problem* p) {
@@ -1204,7 +1349,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@
 //     through a device block table (the row maps' tile below);
 //   * ragged_fp8_partial_kernel / paged_fp8_partial_kernel (fa_fwd_f16_ragged_fp8.hip, _paged_fp8.hip): the last
 //     two over a K/V cache of e4m3fn bytes, converted to fp16 on the way into LDS (KvOf below).
+// The window_* and prefill_* partial kernels (fa_fwd_f16_window.h, fa_fwd_f16_prefill.h) are the last four again, with a
+// lower interval end, and over one block of a longer query axis (a map with kQBlock below).
 // The partial kernels share what surrounds the core, and their merge, in fa_fwd_f16_fewq.h.
 // The structure:
 //   * Sᵀ = Kᵀ·Q and Oᵀ = V·Pᵀ on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
@@ -160,12 +162,17 @@ struct WaveRegs {
 // (profiles/paged_core_asm_equal.txt).  A map with kPaged (fa_fwd_f16_paged.hip) is asked, tile(K, V, k0, ...):
 // it looks the tile's page up in a block table and answers a pointer into a page pool with the page as the
 // stride; a page is a multiple of the 64-key tile, so a tile never straddles two pages.
+// A map with kQBlock (fa_fwd_f16_prefill.h) folds one BLOCK of a longer query axis: it carries the block's first
+// query q0 and its query count nq, and the core then starts Q q0 elements in, keeps a.rule.q.n as Q's row stride
+// only, and counts the live rows and each wave's last lane by the block's nq.  For every other map the three are
+// one number, as they always were.
 // The core asks none of the next two; the few-query partial and merge kernels (fa_fwd_f16_fewq.h) do: whether
 // row rho of the block is a live query (row_live), and the floats per row of a partial record (rec_stride).
 struct IdentityRows {
   static constexpr bool kFolded = false;
   static constexpr bool kRagged = false;
   static constexpr bool kPaged = false;
+  static constexpr bool kQBlock = false;
   __device__ __forceinline__ int key_limit(int nk) const { return nk; }
   __device__ __forceinline__ void lane_interval(const Rule& r, int qi, int* klo, int* khi) const { key_interval(r, qi, klo, khi); }
   __device__ __forceinline__ int64_t q_slice(int64_t bi, int64_t) const { return bi; }
@@ -181,6 +188,7 @@ struct FoldedRows {
   static constexpr bool kFolded = true;
   static constexpr bool kRagged = false;
   static constexpr bool kPaged = false;
+  static constexpr bool kQBlock = false;
   __device__ __forceinline__ int key_limit(int nk) const { return nk; }
   __device__ __forceinline__ void lane_interval(const Rule& r, int qi, int* klo, int* khi) const { key_interval(r, qi, klo, khi); }
   int32_t g, pitch, log2_pitch;
@@ -247,14 +255,20 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   constexpr float kNegInf = -__builtin_huge_valf();
   __builtin_assume(kt0 % kBN == 0);  // lets key indices fold as they do where kt0 is formed in place
 
-  const int nq = a.rule.q.n, nk = a.rule.k.n, d = FAST ? D : a.d, vd = FAST ? D : a.v_d;
+  // nqs: the row stride of Q.  nq: the queries this workgroup's rows stand for, which every live-row test and wave
+  // bound below counts by: the same number, except under a map with kQBlock
+  const int nqs = a.rule.q.n;
+  int nq_block = nqs;
+  if constexpr (Map::kQBlock) nq_block = map.nq;
+  const int nq = nq_block, nk = a.rule.k.n, d = FAST ? D : a.d, vd = FAST ? D : a.v_d;
   const int nkl = map.key_limit(nk);  // live keys; nk stays the row stride of K and V
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, r = lane & 31;
   const int g = lane >> 4, i16 = lane & 15, tq = i16 >> 2, tp = i16 & 3;  // tr-read lane roles
 
-  const __half* Q = static_cast<const __half*>(a.Q) + map.q_slice(bi, bkv) * (int64_t)d * nq;
+  const __half* Q = static_cast<const __half*>(a.Q) + map.q_slice(bi, bkv) * (int64_t)d * nqs;
+  if constexpr (Map::kQBlock) Q += map.q0;
   const KvT* K = static_cast<const KvT*>(a.K) + map.kv_slice(bi, bkv) * (int64_t)d * nk;
   const KvT* V = static_cast<const KvT*>(a.V) + map.kv_slice(bi, bkv) * (int64_t)vd * nk;
   const bool qvec = ((nq & 7) == 0) && ((reinterpret_cast<uintptr_t>(a.Q) & 15) == 0);
@@ -328,7 +342,7 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
       for (int e = 0; e < 8; ++e) {
         const int rho = 8 * m + e, j = rho >> map.log2_pitch, i = rho & (map.pitch - 1);
         const bool live = c < d && j < map.g && i < nq;
-        hh[e] = live ? (uint32_t)__half_as_ushort(Q[((int64_t)j * d + c) * nq + i]) : 0u;
+        hh[e] = live ? (uint32_t)__half_as_ushort(Q[((int64_t)j * d + c) * nqs + i]) : 0u;
       }
       v = u32x4{hh[0] | (hh[1] << 16), hh[2] | (hh[3] << 16), hh[4] | (hh[5] << 16), hh[6] | (hh[7] << 16)};
     } else if (c < d) {

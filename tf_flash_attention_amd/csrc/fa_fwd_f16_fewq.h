@@ -81,7 +81,9 @@ __device__ __forceinline__ int chunk_tiles(const SplitArgs& sa, int kt0, int end
 template <int D, int POL, bool FAST, class Map>
 __device__ __forceinline__ void fewq_partial(const SplitArgs& sa, lds_char_t* smem, Map map, int64_t slice, int ch,
                                              int kt0, int ntiles, WaveRegs<D, kFewqNW, typename KvOf<Map>::Reg>& rg,
-                                             WaveState<D>& ws) {
+                                             WaveState<D>& ws, int64_t rec_slice = -1) {
+  // rec_slice: the slice that the record is filed under, where that is not the K/V slice (a query-blocked
+  // forward files block qb of slice s under s * nqb + qb: fa_fwd_f16_prefill.h)
   const FwdArgs& a = sa.f;
   const int nq = a.rule.q.n;
   fwd_f16_core<D, kFewqNW, POL, FAST, kFewqF, Map>(a, smem, slice, 0, kt0, ntiles, rg, ws, map, slice);
@@ -90,7 +92,7 @@ __device__ __forceinline__ void fewq_partial(const SplitArgs& sa, lds_char_t* sm
   if (!(ws.wave_active & map.row_live(row, nq))) return;  // (&: one test, not a branch per condition)
   const float l_tot = ws.l_run + xor32(ws.l_run);
   const FewqRecord r = {FAST ? D : a.v_d, map.rec_stride(nq)};
-  float* rec = sa.ws + (slice * sa.nchunks + ch) * r.floats();
+  float* rec = sa.ws + ((rec_slice < 0 ? slice : rec_slice) * sa.nchunks + ch) * r.floats();
 #pragma unroll
   for (int u = 0; u < D / 32; ++u)
 #pragma unroll

@@ -1,0 +1,39 @@
+// fa_fwd_f16_prefill_paged.hip — the paged few-query fp16 forward (fa_fwd_f16_paged.hip) over any number of
+// queries, in blocks (gfx950 MFMA; fa_fwd_f16_prefill.h says what the query-blocked forwards share).
+#include "fa_fwd_f16_prefill.h"
+
+namespace fa {
+namespace {
+
+using namespace f16core;
+
+template <int D, int POL, bool FAST>
+__global__ __launch_bounds__(kFewqNW * 64, waves_per_eu(D, kFewqF)) void prefill_paged_partial_kernel(PrefillOf<PagedArgs> pf) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const PagedArgs& pa = pf.a;
+  const RaggedArgs& ra = pa.r;
+  const SplitArgs& sa = ra.g.s;
+  uint32_t bkv;
+  int qb, q0, ch, lb, kt0, ntiles;
+  if (!prefill_block(ra, pf.nqb, POL == 1, &bkv, &qb, &q0, &ch, &lb, &kt0, &ntiles)) return;  // the merge does not read its record
+  // (the map of lb keys: the first entry loaded is the first staged tile's, the look-ahead stops at page (lb - 1) / page)
+  PagedRows rows = paged_rows<D, FAST>(pa, bkv, lb, kt0);
+  rows.nq = block_queries(ra.g, q0);
+  const BlockPagedRows map = {rows, q0};
+  WaveRegs<D, kFewqNW> rg;
+  WaveState<D> ws;
+  fewq_partial<D, POL, FAST>(sa, (lds_char_t*)smem_raw, map, bkv, ch, kt0, ntiles, rg, ws, (int64_t)bkv * pf.nqb + qb);
+}
+
+}  // namespace
+
+hipError_t launch_fwd_f16_prefill_paged(const PrefillOf<PagedArgs>& pf, hipStream_t s) {
+  const RaggedArgs& ra = pf.a.r;
+  const hipError_t e = with_fewq_tail(ra, pf.a.page, [&](auto d, auto pol, auto fast) {
+    return launch_prefill_partial(d, prefill_paged_partial_kernel<d.value, pol.value, fast.value != 0>, pf, ra.g.s, pf.nqb, s);
+  });
+  if (e != hipSuccess) return e;
+  return launch_fwd_f16_prefill_merge({ra, pf.nqb}, s);  // the merge reads neither K / V nor the table
+}
+
+}  // namespace fa

@@ -113,6 +113,15 @@ struct WindowOf {
   int32_t window;  // W: query i sees the keys [max(0, pos_i - W + 1), pos_i], pos_i = len - nq + i; 1 <= W < nk
 };
 
+// the query-blocked forms of the same four forwards (fa_fwd_f16_prefill.h): `a` for any number of queries.  a's
+// GqaArgs holds the BLOCK's pitch P (the largest power of two with g * P <= 128, not bounded below by nq), and its
+// SplitArgs the records [b_kv][nqb][nchunks] of stride g * P.
+template <class Args>
+struct PrefillOf {
+  Args a;
+  int32_t nqb;  // query blocks: ceil(nq / P), >= 2
+};
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;
@@ -224,6 +233,14 @@ hipError_t launch_fwd_f16_window_merge(const WindowOf<RaggedArgs>& wa, hipStream
 hipError_t launch_fwd_f16_window_paged(const WindowOf<PagedArgs>& wa, hipStream_t s);
 hipError_t launch_fwd_f16_window_ragged_fp8(const WindowOf<RaggedFp8Args>& wa, hipStream_t s);
 hipError_t launch_fwd_f16_window_paged_fp8(const WindowOf<PagedFp8Args>& wa, hipStream_t s);
+// the same four for any number of queries: one workgroup per (K/V slice, query block, key chunk) —
+// fa_fwd_f16_prefill_ragged.hip, _prefill_paged.hip, _prefill_ragged_fp8.hip, _prefill_paged_fp8.hip (shared:
+// fa_fwd_f16_prefill.h)
+hipError_t launch_fwd_f16_prefill_ragged(const PrefillOf<RaggedArgs>& pf, hipStream_t s);
+hipError_t launch_fwd_f16_prefill_merge(const PrefillOf<RaggedArgs>& pf, hipStream_t s);  // the merge of all four
+hipError_t launch_fwd_f16_prefill_paged(const PrefillOf<PagedArgs>& pf, hipStream_t s);
+hipError_t launch_fwd_f16_prefill_ragged_fp8(const PrefillOf<RaggedFp8Args>& pf, hipStream_t s);
+hipError_t launch_fwd_f16_prefill_paged_fp8(const PrefillOf<PagedFp8Args>& pf, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

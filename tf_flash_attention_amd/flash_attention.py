@@ -64,7 +64,7 @@ __all__ = [
     "InvalidArgumentError", "InternalError", "estimate_forward_flops",
     "Part", "combined_1d", "combined_2d", "merge_partials",
     "grouped_1d", "grouped_2d", "attention_forward_grouped",
-    "ragged_1d", "paged_1d", "quantize_kv_fp8",
+    "ragged_1d", "paged_1d", "ragged_prefill_1d", "paged_prefill_1d", "quantize_kv_fp8",
 ]
 
 
@@ -751,7 +751,33 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=N
     not the capacity; ``W >= cap`` is the tail-causal call itself, bit for bit.  With
     ``lo = max(0, k_lens[s] - Nq - W + 1)``, keys below ``lo // 64 * 64`` are never read.  The at most 63 keys
     between that and ``lo`` are read and masked, so they must be finite (they are the sequence's own earlier keys).
-    Returns ``O`` or ``(O, l, m)``."""
+    More queries than the envelope's g * next_pow2(Nq) <= 128 (chunked prefill, a long speculative draft):
+    ``ragged_prefill_1d``.  Returns ``O`` or ``(O, l, m)``."""
+    return _ragged_forward("ragged_1d", False, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, window_size)
+
+
+def ragged_prefill_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=None, v_scale=None):
+    """``ragged_1d`` for any number of queries (chunked prefill, long speculative drafts): the same tensors, layouts,
+    ``tail_causal`` rule, empty rows, FP8 cache and scales, with Nq >= 1 unbounded and 1 <= g <= 128.  The queries are
+    worked in blocks of P = the largest power of two with g * P <= 128; where one block holds them all the call is
+    ``ragged_1d`` itself, bit for bit.  There is no ``window_size``.
+
+    A batch that mixes prefill with decode right-aligns each sequence's real queries in the Nq slots (with
+    ``tail_causal`` the last slot is the sequence's last position).  The padding queries in front compute earlier
+    positions' rows, or empty rows where they lie before position 0; the caller ignores them.
+
+    ``k_lens`` and the scales are read by the kernels, never on the host.  Inference only; float16 only; outside
+    the envelope (more than 128 channels, g > 128) the call raises NotImplementedError.  Returns ``O`` or
+    ``(O, l, m)``."""
+    return _ragged_forward("ragged_prefill_1d", True, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, None)
+
+
+_PREFILL_ENVELOPE = ("float16, 1d sequences, at most 128 channels, Nq >= 1, capacity >= 1 and "
+                     "1 <= g <= 128 with g = Hq / Hk")
+
+
+def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, window_size):
+    """``ragged_1d`` (``prefill`` False) and ``ragged_prefill_1d``: one validation, the entry points differ."""
     Qb, Qs, Q_ch, Kb, Ks, V_ch, g = verify_grouped_shapes(1, Q.shape, K.shape, V.shape)
     dt = _dtype_id(Q, True)
     kv_per_len = int(Kb[-1]) if Kb else 1
@@ -766,20 +792,23 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=N
     if k_lens.device != Q.device:
         raise InvalidArgumentError("k_lens must be on the device of Q, K and V")
     if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, K, V)):
-        raise RuntimeError("ragged_1d is inference only and has no gradient; call it under torch.no_grad() or "
+        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
                            "detach its inputs")
-    window = _decode_window("ragged_1d", window_size, tail_causal, int(Qs[0]))
+    window = _decode_window(what, window_size, tail_causal, int(Qs[0]))
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(Qb), Qs, Ks, Q_ch, V_ch)
     L = _lib.lib()
     plan = (ctypes.c_int32 * 8)()
-    if window is None:
+    if prefill:
+        st = L.fa_forward_ragged_prefill_plan(prob, g, plan)
+    elif window is None:
         st = L.fa_forward_ragged_plan(prob, g, plan)
     else:
         st = L.fa_forward_ragged_window_plan(prob, g, window, plan)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     if plan[0] == 0:
-        raise NotImplementedError("ragged_1d: outside the fused envelope (" + _RAGGED_ENVELOPE + "), got Q_shape = "
+        raise NotImplementedError(what + ": outside the fused envelope ("
+                                  + (_PREFILL_ENVELOPE if prefill else _RAGGED_ENVELOPE) + "), got Q_shape = "
                                   + _shape_str(Q.shape) + ", K_shape = " + _shape_str(K.shape) + ", V_shape = "
                                   + _shape_str(V.shape))
     _check_device_tensors(Q, K, V)
@@ -787,13 +816,25 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=N
     O = torch.empty(Qb + (V_ch,) + Qs, dtype=Q.dtype, device=Q.device)
     l = torch.empty(Qb + Qs, dtype=torch.float32, device=Q.device)
     m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
-    if window is None:
+    if prefill:
+        ws_bytes = int(L.fa_forward_ragged_prefill_workspace_bytes(prob, g))
+    elif window is None:
         ws_bytes = int(L.fa_forward_ragged_workspace_bytes(prob, g))
     else:
         ws_bytes = int(L.fa_forward_ragged_window_workspace_bytes(prob, g, window))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        if window is not None and fp8:
+        if prefill:
+            if fp8:
+                st = L.fa_forward_ragged_prefill_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
+                                                     V.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
+                                                     k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)), O.data_ptr(),
+                                                     l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+            else:
+                st = L.fa_forward_ragged_prefill(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
+                                                 V.data_ptr(), k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)),
+                                                 O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+        elif window is not None and fp8:
             st = L.fa_forward_ragged_window_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
                                                 V.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
                                                 k_lens.data_ptr(), kv_per_len, window, O.data_ptr(), l.data_ptr(),
@@ -865,7 +906,35 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
     (exact where the two key sets are disjoint: S <= k_lens - Nq - W + 1).
 
     Inference only (no gradient); float16 only; the page size must be a multiple of 64; outside the envelope the
-    call raises NotImplementedError (there is no gather fallback).  Returns ``O`` or ``(O, l, m)``."""
+    call raises NotImplementedError (there is no gather fallback).  More queries than the envelope's
+    g * next_pow2(Nq) <= 128: ``paged_prefill_1d``.  Returns ``O`` or ``(O, l, m)``."""
+    return _paged_forward("paged_1d", False, Q, K_pool, V_pool, block_table, k_lens, tail_causal, returning_l_m, k_scale,
+                          v_scale, window_size)
+
+
+def paged_prefill_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False, k_scale=None,
+                     v_scale=None):
+    """``paged_1d`` for any number of queries (chunked prefill against the paged cache, long speculative drafts):
+    the same pools, block table, lengths, ``tail_causal`` rule, empty rows, FP8 pools and scales, with Nq >= 1
+    unbounded and 1 <= g <= 128.  The queries are worked in blocks of P = the largest power of two with
+    g * P <= 128; where one block holds them all the call is ``paged_1d`` itself, bit for bit.  There is no
+    ``window_size``.  The new tokens' keys are appended to the pools first (``paged_1d`` shows how), so that
+    ``k_lens`` counts them.
+
+    A batch that mixes prefill with decode right-aligns each sequence's real queries in the Nq slots (with
+    ``tail_causal`` the last slot is the sequence's last position).  The padding queries in front compute earlier
+    positions' rows, or empty rows where they lie before position 0; the caller ignores them.
+
+    Nothing is read on the host; table entries of pages without a live key are never loaded and loaded entries are
+    clamped.  Inference only; float16 only; the page size must be a multiple of 64; outside the envelope the call
+    raises NotImplementedError.  Returns ``O`` or ``(O, l, m)``."""
+    return _paged_forward("paged_prefill_1d", True, Q, K_pool, V_pool, block_table, k_lens, tail_causal, returning_l_m,
+                          k_scale, v_scale, None)
+
+
+def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_causal, returning_l_m, k_scale, v_scale,
+                   window_size):
+    """``paged_1d`` (``prefill`` False) and ``paged_prefill_1d``: one validation, the entry points differ."""
     if len(K_pool.shape) != 4 or len(V_pool.shape) != 4:
         raise InvalidArgumentError("K_pool and V_pool should be [num_pages, Hk, channels, page], but K_pool_shape = "
                                    + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
@@ -904,26 +973,29 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
     if block_table.device != Q.device or k_lens.device != Q.device:
         raise InvalidArgumentError("block_table and k_lens must be on the device of Q, K_pool and V_pool")
     if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, K_pool, V_pool)):
-        raise RuntimeError("paged_1d is inference only and has no gradient; call it under torch.no_grad() or "
+        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
                            "detach its inputs")
     if page < 1 or page % 64 != 0:
-        raise NotImplementedError("paged_1d: " + _PAGE_CONDITION + ", got page = " + str(page))
+        raise NotImplementedError(what + ": " + _PAGE_CONDITION + ", got page = " + str(page))
     g, max_pages = hq // hk, int(block_table.shape[-1])
     cap = max_pages * page
     if cap > 2 ** 30:
         raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
-    window = _decode_window("paged_1d", window_size, tail_causal, nq)
+    window = _decode_window(what, window_size, tail_causal, nq)
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_ch)
     L = _lib.lib()
     plan = (ctypes.c_int32 * 8)()
-    if window is None:
+    if prefill:
+        st = L.fa_forward_paged_prefill_plan(prob, g, page, plan)
+    elif window is None:
         st = L.fa_forward_paged_plan(prob, g, page, plan)
     else:
         st = L.fa_forward_paged_window_plan(prob, g, page, window, plan)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     if plan[0] == 0:
-        raise NotImplementedError("paged_1d: outside the fused envelope (" + _RAGGED_ENVELOPE + "; and "
+        raise NotImplementedError(what + ": outside the fused envelope ("
+                                  + (_PREFILL_ENVELOPE if prefill else _RAGGED_ENVELOPE) + "; and "
                                   + _PAGE_CONDITION + "), got Q_shape = " + _shape_str(Q.shape) + ", K_pool_shape = "
                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape))
     _check_device_tensors(Q, K_pool, V_pool)
@@ -932,13 +1004,27 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
     O = torch.empty(batch + (hq, v_ch, nq), dtype=Q.dtype, device=Q.device)
     l = torch.empty(batch + (hq, nq), dtype=torch.float32, device=Q.device)
     m = torch.empty(batch + (hq, nq), dtype=Q.dtype, device=Q.device)
-    if window is None:
+    if prefill:
+        ws_bytes = int(L.fa_forward_paged_prefill_workspace_bytes(prob, g, page))
+    elif window is None:
         ws_bytes = int(L.fa_forward_paged_workspace_bytes(prob, g, page))
     else:
         ws_bytes = int(L.fa_forward_paged_window_workspace_bytes(prob, g, page, window))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        if window is not None and fp8:
+        if prefill:
+            if fp8:
+                st = L.fa_forward_paged_prefill_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
+                                                    V_pool.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
+                                                    block_table.data_ptr(), max_pages, page, num_pages,
+                                                    k_lens.data_ptr(), hk, int(bool(tail_causal)), O.data_ptr(),
+                                                    l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+            else:
+                st = L.fa_forward_paged_prefill(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
+                                                V_pool.data_ptr(), block_table.data_ptr(), max_pages, page, num_pages,
+                                                k_lens.data_ptr(), hk, int(bool(tail_causal)), O.data_ptr(),
+                                                l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+        elif window is not None and fp8:
             st = L.fa_forward_paged_window_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
                                                V_pool.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
                                                block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(),
