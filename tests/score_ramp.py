@@ -677,6 +677,58 @@ def emulate_ragged_f16(Q, K, V, kv_lens, g, tail):
     return o, l, m
 
 
+def kv8_split(k_scale):
+    """(e, r) with k_scale = 2^e * r as kv8_mul (csrc/fa_fwd_f16_fewq.h) splits the float32 scale: e = round(log2)
+    clamped to [-8, 7] from the scale's bits, r the exact float32 quotient."""
+    kb = int(np.float32(k_scale).view(np.uint32))
+    e = (kb >> 23) - 127 + (1 if (kb & 0x7FFFFF) >= 0x3504F3 else 0)
+    e = min(max(e, -8), 7)
+    return e, np.float32(np.float32(k_scale) * np.float32(2.0 ** -e))
+
+
+def emulate_cache_f16(Q, K, V, kv_lens, g, tail, window=0, k_scale=None, v_scale=None, hk=1):
+    """emulate_ragged_f16 with a sliding window (window >= 1: tests/window_ref.window_mask in place of the ragged
+    mask) and / or an FP8 cache (K, V uint8: e4m3fn bytes; k_scale / v_scale float32 [hk] or None for 1.0, K/V slice
+    s being head s % hk) with the documented split: Q' = fp16(q * (c2 * r)) with the product c2 * r in fp32,
+    K' = k8 * 2^e (exact in fp16) and v_scale multiplying the accumulator.  Only the keys from the first to the
+    last one that some query sees are read."""
+    from tests import fp8_ref, ragged_ref, window_ref
+    b, d, nq = Q.shape
+    vd, cap = V.shape[1], V.shape[2]
+    fp8 = K.dtype == np.uint8
+    c2 = np.float32(np.float32(1.0 / math.sqrt(d)) * np.float32(LOG2E))
+    o = np.zeros((b, vd, nq), np.float16)
+    l = np.zeros((b, nq), np.float32)
+    m = np.full((b, nq), 0xFAFA, np.uint16).view(np.float16)
+    for i in range(b):
+        s = i // g
+        L = min(max(int(kv_lens[s]), 0), cap)
+        mask = window_ref.window_mask(nq, cap, L, window) if window else ragged_ref.ragged_mask(nq, cap, L, tail)
+        has = mask.any(axis=1)
+        if not has.any():
+            continue
+        cols = np.nonzero(mask.any(axis=0))[0]
+        j0, j1 = int(cols[0]), int(cols[-1]) + 1
+        mask = mask[:, j0:j1]
+        e, r = kv8_split(1.0 if k_scale is None else k_scale[s % hk]) if fp8 else (0, np.float32(1.0))
+        vmul = float(np.float32(v_scale[s % hk])) if fp8 and v_scale is not None else 1.0
+        qs16 = (Q[i].astype(np.float32) * np.float32(c2 * r)).astype(np.float16).astype(np.float64)
+        if fp8:
+            k = (fp8_ref.decode(K[s][:, j0:j1]) * 2.0 ** e).astype(np.float16).astype(np.float64)
+            v = fp8_ref.decode(V[s][:, j0:j1])
+        else:
+            k, v = K[s][:, j0:j1].astype(np.float64), V[s][:, j0:j1].astype(np.float64)
+        s2 = np.where(mask, qs16.T @ k, -np.inf)
+        m2 = np.where(has, s2.max(axis=1), 0.0)
+        p16 = np.exp2(s2 - m2[:, None]).astype(np.float16).astype(np.float64)
+        l_run = np.where(has, p16.sum(axis=1), 1.0)
+        o16 = ((v @ p16.T) * vmul / l_run).astype(np.float16)
+        m16 = (m2 / LOG2E).astype(np.float16)
+        l32 = (l_run * np.exp2(m2 - m16.astype(np.float64) * LOG2E)).astype(np.float32)
+        o[i][:, has], l[i][has], m[i][has] = o16[:, has], l32[has], m16[has]
+    return o, l, m
+
+
 # The decode cases.  Plateaus of one 64-key tile.  Chunks are 512 keys up to 64 folded rows and 1024 above (g = 2,
 # nq = 33: pitch 64, 128 rows), so three chunks need a capacity past 1024 / 2048 keys.  Each case holds, in ONE call:
 #   c2 + 148  a length that ends mid-tile with three live tiles in the last chunk (e = 2, 1, 0: the seed, a quiet 2σ0
@@ -731,3 +783,14 @@ DECODE_CASES = [
     _d("grouped-d32-g8q3-causal-elem", "grouped", 32, 32, 8, 3, 1165, tail=True, lens=(1165, 1165)),
 ]
 DECODE_CASE_BY_ID = {c.id: c for c in DECODE_CASES}
+
+
+def windowed_tail_cases():
+    """The tail cases whose lengths all lie below the capacity: at W = capacity - 1 the sliding-window forwards run
+    them un-delegated under the tail plan and the tail mask (tests/test_gpu_decode_score_range.py)."""
+    return [c for c in DECODE_CASES if c.entry == "ragged" and c.tail and max(c.lens) < c.cap]
+
+
+def window_capacity(case, page=0):
+    """the capacity a windowed run of ``case`` uses: its own, or for a paged run that rounded up to the page"""
+    return -(-case.cap // page) * page if page else case.cap

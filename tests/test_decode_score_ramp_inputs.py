@@ -164,6 +164,30 @@ def test_emulation_is_the_base_one_on_full_lengths():
     assert np.array_equal(o, ref["O"]) and np.array_equal(l, ref["l"]) and np.array_equal(m, ref["m"])
 
 
+@pytest.mark.parametrize("page", [0, 64], ids=["ragged", "paged64"])
+@pytest.mark.parametrize("case", R.windowed_tail_cases(), ids=_id)
+def test_a_window_of_capacity_minus_one_is_the_tail_plan_and_the_tail_mask(case, page):
+    """What carries the proofs above over to the windowed run of tests/test_gpu_decode_score_range.py: at
+    W = capacity - 1 the call is not delegated, its plan (the library's, host-only) is the tail plan chunk for chunk,
+    lo = 0 for every length, and every query's interval is the tail rule's.  The paged run's capacity is rounded up to
+    the page of 64 keys, which adds no chunk."""
+    from tests import test_gpu_cache_fuzz as F
+    from tests import test_gpu_window as gw
+    from tests import window_ref
+    cap = R.window_capacity(case, page)
+    window = cap - 1
+    chunks, chunk, pitch = case.plan
+    assert len(R.windowed_tail_cases()) >= 3 and cap - case.cap < 64 and max(case.lens) < case.cap
+    want = (chunks, chunk, cap, chunks, pitch, case.g * pitch, 0, 0)
+    assert gw._plan(case.nq, cap, case.d, case.vd, case.g, window, page or None) == want
+    assert F.window_plan(case.nq, cap, case.g, window) == want and R.decode_plan(case.nq, cap, case.g) == case.plan
+    for L in case.lens:
+        assert window_ref.window_lo(L, case.nq, window, cap) == 0
+        mask = window_ref.window_mask(case.nq, cap, L, window)
+        assert np.array_equal(mask, ragged_ref.ragged_mask(case.nq, cap, L, True))
+        assert np.array_equal(mask[:, :L], case.mask(L)) and not mask[:, L:].any()
+
+
 def _profile_lines():
     yield f"{MARK} (score_ramp.DECODE_CASES; written by `python -m tests.test_decode_score_ramp_inputs`): the"
     yield "emulated deviation under test_gpu_ragged._check_ref, m with the tight bound; every ratio must be <= 0.5."

@@ -2,7 +2,8 @@
 (tests/score_ramp.DECODE_CASES): the ragged partial kernel with per-slice lengths, its tail-causal form, its
 D = 32 / 64 / 128 and element-wise instances, the pitch-64 and pitch-128 wave layouts, ragged_merge_kernel over three
 chunks of which early ones underflow against the merged reference while dead ones are skipped, the same inputs
-through a block table (fa_forward_paged), and fa_forward_grouped at D = 128 and D = 32.
+through a block table (fa_forward_paged), fa_forward_grouped at D = 128 and D = 32, and the tail cases through the sliding-window forwards at
+W = capacity - 1 (the windowed partial kernels and window_merge_kernel under the tail plan and the tail mask).
 
 Every other input of test_gpu_ragged.py and test_gpu_paged.py is U(-2, 2), which never moves a row's reference
 after the seed tile.  tests/test_decode_score_ramp_inputs.py proves on the CPU, chunk by chunk, that these inputs
@@ -26,6 +27,7 @@ _id = lambda c: c.id  # noqa: E731
 RAGGED = [c for c in R.DECODE_CASES if c.entry == "ragged"]
 PAGED = [(c, page) for c in RAGGED for page in c.pages]
 GROUPED = [c for c in R.DECODE_CASES if c.entry == "grouped"]
+WINDOWED = R.windowed_tail_cases()
 SPARE = 3
 
 
@@ -86,3 +88,45 @@ def test_staircase_scores_grouped(monkeypatch, case):
     dO = np.zeros((made["Q"].shape[0], case.vd, case.nq), np.float16)
     _grouped_case(monkeypatch, policy, mode, case.g, (case.nq,), (case.cap,), case.d, case.vd, bkv=len(made["lens"]),
                   inputs=(made["Q"], made["K"], made["V"], dO), m_bound=made["bound"])
+
+
+@pytest.mark.parametrize("form", ["ragged", "paged"])
+@pytest.mark.parametrize("case", WINDOWED, ids=_id)
+def test_staircase_scores_windowed(case, form):
+    """Every tail case whose lengths lie below its capacity through fa_forward_ragged_window / fa_forward_paged_window
+    at W = capacity - 1: not delegated, so the windowed partial kernels and window_merge_kernel run; span_w is the
+    capacity and every lo and klo is 0, so the plan is the tail plan and the mask the tail mask
+    (tests/test_decode_score_ramp_inputs.py asserts both), and the CPU proofs of the tail cases carry over: rebases
+    fire, chunks underflow in the merge, idle rows sit beside rebasing wave-mates.  The paged form runs on pages of
+    64 keys at the capacity rounded up to the page (R.window_capacity; the keys added lie past every length)."""
+    from tests import paged_ref
+    from tests import test_gpu_cache_fuzz as F
+    from tests import test_gpu_window as gw
+    made = _made(case.id)
+    page = 64 if form == "paged" else 0
+    cap = R.window_capacity(case, page)
+    window = cap - 1
+    chunks, chunk, pitch = case.plan
+    assert gw._plan(case.nq, cap, case.d, case.vd, case.g, window, page or None) == \
+        (chunks, chunk, cap, chunks, pitch, case.g * pitch, 0, 0)
+    K, V = (np.concatenate([x, np.repeat(x[:, :, -1:], cap - case.cap, axis=2)], axis=2) for x in (made["K"], made["V"]))
+    bkv = len(made["lens"])
+    c = dict(misalign=False, g=case.g, hk=1, lens=made["lens"], cap=cap, page=page, max_pages=cap // page if page else 0)
+    tq = rg._dev(made["Q"])
+    if form == "ragged":
+        stores = (K, V, None)
+    else:
+        num_pages = bkv * c["max_pages"] + SPARE
+        table = np.random.default_rng(7).permutation(num_pages)[:bkv * c["max_pages"]].reshape(bkv, -1).astype(np.int32)
+
+        def scatter(cache):
+            pool = np.full((num_pages, 1, cache.shape[1], page), np.nan, np.float16)
+            pool[table] = cache.reshape(bkv, 1, cache.shape[1], c["max_pages"], page).transpose(0, 3, 1, 2, 4)
+            return pool
+
+        stores = (scatter(K), scatter(V), table)
+        assert np.array_equal(paged_ref.gather(stores[0], table, page), K)
+    got = F._forward(c, form, "fp16", window, True, tq, *stores, None, None)
+    res = rg._check_ref(got, made["Q"], K, V, made["lens"], case.g, True, m_bound=made["bound"])
+    tail = F._forward(c, form, "fp16", 0, True, tq, *stores, None, None)
+    print(case.id, form, {k: round(v, 3) for k, v in res.items()}, "bitwise the tail call:", rg._same(got, tail))

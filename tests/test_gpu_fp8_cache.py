@@ -6,7 +6,8 @@ The main instrument is bitwise equality with the fp16 twin on the cache converte
 fp16 is exact, the plan, the tiles and the staged LDS image are the same, so an addressing, masking or conversion
 error shows without a tolerance.  Real scales go against the float64 reference on the DEQUANTIZED cache under
 test_gpu_ragged._check_ref, the project's own fp16 forward gate.  tests/fp8_ref.py is the only source of quantized
-data.  Every capacity is test_gpu_paged._max_pages's (about 2600 keys, at least 3 chunks)."""
+data.  Every capacity is test_gpu_paged._max_pages's (about 2600 keys, at least 3 chunks), but the invalid-scale
+test's 1344 keys."""
 
 import numpy as np
 import pytest
@@ -390,3 +391,57 @@ def test_an_empty_batch_is_ok(form):
         st = L.fa_forward_paged_fp8(stream, prob, 4, None, None, None, None, None, None, 41, 64, 8, None, HK, 0, None,
                                     None, None, ws.data_ptr(), int(L.fa_forward_paged_workspace_bytes(prob, 4, 64)))
     assert st == _lib.FA_OK
+
+
+# ------------------------------------------------------------------ 8. invalid scales
+BAD_SCALES = [0.0, -0.0, -1.0, float("inf"), float("nan")]
+
+
+@pytest.mark.parametrize("window", [0, 300], ids=["tail", "w300"])
+@pytest.mark.parametrize("form", FORMS)
+def test_an_invalid_scale_gives_nan_in_its_own_head_only(form, window):
+    """include/fa_api.h: "A scale must be finite and positive; any other value gives NaN output".  2 sequences x 2 K/V
+    heads, g = 2, nq = 4, d = v_d = 64, a capacity of 1344 keys (three chunks), lengths (1344, 700); the un-windowed
+    tail form and W = 300.  0.0, -0.0, -1.0, +Inf and NaN in k_scale[1] and, separately, in v_scale[1]: O of every
+    (live) row of head 1 is NaN in every channel, the rows of head 0 are bitwise the clean call, and no call leaves
+    an error behind.  A positive subnormal scale is valid: finite output."""
+    from tests import test_gpu_window as gw
+    g, nq, d, page, seqs = 2, 4, 64, 64, 2
+    max_pages = 21
+    cap = page * max_pages
+    lens = [cap, 700]
+    Q, K, V = rg._np_inputs(seqs * HK, g, d, d, nq, cap, seed=91)
+    K8, V8 = fp8_ref.encode(K), fp8_ref.encode(V)
+    num_pages = seqs * max_pages + SPARE
+    table = np.random.default_rng(92).permutation(num_pages)[:seqs * max_pages].reshape(seqs, max_pages).astype(np.int32)
+    k8, v8 = _stores(form, K8, V8, table, page)
+    tq, tk, tv = _dev(Q), _dev(k8), _dev(v8)
+    if window:
+        assert gw._plan(nq, cap, d, d, g, window, page if form == "paged" else None)[6] == 0
+
+    def call(ks, vs):
+        ks, vs = _scale_dev(ks), _scale_dev(vs)
+        if window:
+            st, *out = gw._win(form, g, tq, tk, tv, table, lens, window, fp8=True, ks=ks, vs=vs)
+        else:
+            st, *out = _call8(form, g, tq, tk, tv, table, lens, ks, vs, tail=True)
+        assert st == 0, _lib.last_error()
+        return out
+
+    clean_k, clean_v = [0.3, 1.7], [2.5, 0.04]
+    clean = call(clean_k, clean_v)
+    assert all(bool(torch.isfinite(t.float()).all()) for t in clean)
+    head = (np.arange(seqs * HK * g) // g) % HK                   # the K/V head of every Q slice
+    h0, h1 = (torch.from_numpy(np.nonzero(head == h)[0]).to(tq.device) for h in (0, 1))
+    for bad in BAD_SCALES:
+        for which, (ks, vs) in (("k_scale", ([clean_k[0], bad], clean_v)), ("v_scale", (clean_k, [clean_v[0], bad]))):
+            got = call(ks, vs)
+            assert rg._same([t[h0] for t in got], [t[h0] for t in clean]), (which, bad, "head 0 moved")
+            o1 = got[0][h1].float()
+            assert bool(torch.isnan(o1).all()), (which, bad, f"{int((~torch.isnan(o1)).sum())} of {o1.numel()} outputs of "
+                                                 f"head 1 are not NaN; finite max |O| {float(torch.nan_to_num(o1).abs().max())}")
+    tiny = float(np.float32(1e-40))                               # a positive subnormal float32
+    for ks, vs in (([clean_k[0], tiny], clean_v), (clean_k, [clean_v[0], tiny])):
+        got = call(ks, vs)
+        assert all(bool(torch.isfinite(t.float()).all()) for t in got)
+        assert rg._same([t[h0] for t in got], [t[h0] for t in clean])

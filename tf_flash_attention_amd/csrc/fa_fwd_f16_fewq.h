@@ -224,8 +224,11 @@ __device__ __forceinline__ PagedRows paged_rows(const PagedArgs& pa, uint32_t bk
 // [-8, 7]: kmul = 2^e multiplies K exactly in the conversion to fp16, and qmul = r, in [2^-0.5, 2^0.5) inside the
 // clamp, multiplies the Q pre-scale in fp32 before Q is rounded to fp16; all of k_scale there would push Q' towards
 // fp16 subnormals for small scales.  vmul = v_scale.  A null array means 1.0: kmul = qmul = vmul = 1, the fp16
-// forward's bits.  A scale that is not finite and positive becomes a NaN factor, so the output is NaN rather than
-// plausible.  All of this is integer work on the scale's bits (-fno-honor-nans cannot touch it) and wave-uniform.
+// forward's bits.  A k_scale or v_scale that is not finite and positive makes vmul NaN, so O is NaN rather than
+// plausible.  The NaN must not go through the scores: under -fno-honor-nans a row whose scores are all NaN keeps no
+// reference, its record says "no key" and the merge writes O = 0 (tests/test_gpu_fp8_cache.py, the invalid-scale
+// test); so a bad k_scale leaves qmul at 1 and the finite scores carry the NaN accumulator to the merge.  All of
+// this is integer work on the scale's bits (-fno-honor-nans cannot touch it) and wave-uniform.
 struct Kv8Mul {
   float kmul, qmul, vmul;
 };
@@ -239,8 +242,9 @@ __device__ __forceinline__ Kv8Mul kv8_mul(const float* k_scale, const float* v_s
   const float r = __uint_as_float(kb) * __uint_as_float((uint32_t)(127 - e) << 23);  // exact: a power of two
   Kv8Mul s;
   s.kmul = __uint_as_float((uint32_t)(127 + e) << 23);
-  s.qmul = __uint_as_float(kb - 1u < kMaxFinite ? __float_as_uint(r) : kNaN);
-  s.vmul = __uint_as_float(vb - 1u < kMaxFinite ? vb : kNaN);
+  const bool k_ok = kb - 1u < kMaxFinite, v_ok = vb - 1u < kMaxFinite;
+  s.qmul = __uint_as_float(k_ok ? __float_as_uint(r) : kOne);
+  s.vmul = __uint_as_float(k_ok & v_ok ? vb : kNaN);
   return s;
 }
 
