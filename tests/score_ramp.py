@@ -472,7 +472,7 @@ NO_REBASE_CASE = _c("diag-2116-no-rebase", F16, "full", "none_front", 64, 64, 30
 
 
 # --------------------------------------------------------------------------- the few-query decode forwards
-# fa_forward_ragged / fa_forward_paged / fa_forward_grouped (csrc/fa_fwd_f16_ragged.hip, _paged.hip, _gqa.hip): one
+# fa_forward_ragged / fa_forward_paged / fa_forward_grouped (csrc/fa_fwd_f16_decode.hip, _gqa.hip): one
 # workgroup per (K/V slice, key chunk) folds the g heads of the slice into rows rho = head * pitch + query, wave w
 # holds rows [32 w, 32 w + 32), every chunk seeds afresh from its first 64-key tile, and a merge kernel weighs the
 # chunks by 2^(m_chunk - max).  The K/V slice s attends its first L_s keys, so its staircase is that of a problem
@@ -752,14 +752,14 @@ def _d(id, entry, d, vd, g, nq, cap, tail=False, lens=None, **kw):
 
 
 DECODE_CASES = [
-    # ---- fa_forward_ragged, full form, 16-byte staging (ragged_partial_kernel<D, 0, true> + ragged_merge_kernel);
-    # the d = 64 case runs through fa_forward_paged as well (paged_partial_kernel, pages of 64 and 192 keys)
+    # ---- fa_forward_ragged, full form, 16-byte staging (decode_partial_kernel<RaggedCache, D, 0, true> + ragged_merge_kernel);
+    # the d = 64 case runs through fa_forward_paged as well (the same kernel over PagedCache, pages of 64 and 192 keys)
     _d("ragged-d64-g4q4-full", "ragged", 64, 64, 4, 4, 1344, pages=(64, 192)),
     _d("ragged-d128-g2q33-full", "ragged", 128, 128, 2, 33, 2568),     # pitch 64: a wave holds a run of one head's queries
     _d("ragged-d32-g8q1-full", "ragged", 32, 32, 8, 1, 1336),         # decode: eight heads side by side in one wave
-    # ---- element-wise staging (capacity % 8 != 0, d != v_d): ragged_partial_kernel<128, 0, false>
+    # ---- element-wise staging (capacity % 8 != 0, d != v_d): decode_partial_kernel<RaggedCache, 128, 0, false>
     _d("ragged-d96v40-g3q3-elem", "ragged", 96, 40, 3, 3, 1341),
-    # ---- tail-causal: ragged_partial_kernel<D, 1, .> through RaggedRows::lane_interval
+    # ---- tail-causal: decode_partial_kernel<RaggedCache, D, 1, .> through RaggedRows::lane_interval
     _d("ragged-d64-g2q16-tail", "ragged", 64, 64, 2, 16, 1344, tail=True, pages=(64, 192)),
     _d("ragged-d128-g1q33-tail", "ragged", 128, 128, 1, 33, 1336, tail=True),
     # the doubled σ0 where the rows' tops differ: at c2 + 1, + 65 and + 129 the window of the last 16 keys lies across

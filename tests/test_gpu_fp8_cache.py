@@ -1,5 +1,5 @@
 """GPU tests of the FP8 (e4m3fn) K/V cache of the ragged and the paged few-query forwards
-(csrc/fa_fwd_f16_ragged_fp8.hip, fa_fwd_f16_paged_fp8.hip, fa_forward_ragged_fp8 / fa_forward_paged_fp8, the k_scale /
+(csrc/fa_fwd_f16_decode.h: RaggedCache8 and PagedCache8, fa_forward_ragged_fp8 / fa_forward_paged_fp8, the k_scale /
 v_scale arguments of flash_attention.ragged_1d / paged_1d).
 
 The main instrument is bitwise equality with the fp16 twin on the cache converted to fp16 at unit scales: e4m3fn ->

@@ -1,4 +1,4 @@
-"""GPU tests of the paged few-query forward (csrc/fa_fwd_f16_paged.hip, fa_forward_paged, flash_attention.paged_1d;
+"""GPU tests of the paged few-query forward (csrc/fa_fwd_f16_decode.hip over PagedCache, fa_forward_paged, flash_attention.paged_1d;
 DESIGN.md §3.10): K and V live in pools of pages [num_pages, Hk, channels, page], a device block table says which
 page holds keys [p * page, (p + 1) * page) of which sequence, and the lengths are device data.
 

@@ -1,4 +1,4 @@
-"""GPU tests of the ragged few-query forward (csrc/fa_fwd_f16_ragged.hip, fa_forward_ragged,
+"""GPU tests of the ragged few-query forward (csrc/fa_fwd_f16_decode.hip over RaggedCache, fa_forward_ragged,
 flash_attention.ragged_1d): K and V are laid out for a capacity, K/V slice bkv attends its first
 k_lens[bkv / kv_per_len] keys, and the lengths are device data.
 

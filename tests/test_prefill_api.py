@@ -172,11 +172,12 @@ class _Recorder:
     """Stands in for the library object: every plan is one chunk, every workspace 0 bytes, every forward FA_OK."""
 
     def __init__(self):
-        self.calls = []
+        self.calls, self.nargs = [], []
 
     def __getattr__(self, name):
         def f(*a):
             self.calls.append(name)
+            self.nargs.append(len(a))
             if name.endswith("_plan"):
                 a[-1][0] = 1
             return 0
@@ -196,3 +197,29 @@ def test_the_call_reaches_the_prefill_entry_points(monkeypatch, call, args, fp8)
     assert rec.calls == [f"fa_forward_{form}_prefill_plan", f"fa_forward_{form}_prefill_workspace_bytes",
                          f"fa_forward_{form}_prefill" + ("_fp8" if fp8 else "")]
     assert out[0].shape == (3, 8, 64, 200) and out[1].shape == out[2].shape == (3, 8, 200)
+
+
+ROUTES = {"plain": dict(), "window": dict(window_size=16), "prefill": dict()}
+
+
+@pytest.mark.parametrize("cache", ["ragged", "paged"])
+@pytest.mark.parametrize("form", list(ROUTES))
+@pytest.mark.parametrize("fp8", [False, True], ids=["f16", "fp8"])
+def test_every_cache_and_form_reaches_its_three_entry_points(monkeypatch, cache, form, fp8):
+    """All twelve routes {ragged, paged} x {plain, window, prefill} x {f16, fp8}: the plan, the workspace size and the
+    forward of that cache and form, in that order, each with as many arguments as the loaded library declares."""
+    real = _lib.lib()
+    rec = _Recorder()
+    monkeypatch.setattr(_lib, "lib", lambda: rec)
+    monkeypatch.setattr(fa, "_check_device_tensors", lambda *t: None)
+    monkeypatch.setattr(fa, "_stream_handle", lambda dev: 0)
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    call = getattr(fa, cache + ("_prefill_1d" if form == "prefill" else "_1d"))
+    nq = 200 if form == "prefill" else 4
+    args = (_ragged if cache == "ragged" else _paged)(nq=nq, kv=torch.float8_e4m3fn if fp8 else torch.float16)
+    out = call(*args, tail_causal=True, returning_l_m=True, **ROUTES[form])
+    stem = f"fa_forward_{cache}" + ("" if form == "plain" else f"_{form}")
+    assert rec.calls == [stem + "_plan", stem + "_workspace_bytes", stem + ("_fp8" if fp8 else "")]
+    assert tuple(rec.calls) == fa.decode_entry_points(cache, form, fp8)
+    assert rec.nargs == [len(getattr(real, name).argtypes) for name in rec.calls]
+    assert out[0].shape == (3, 8, 64, nq) and out[1].shape == out[2].shape == (3, 8, nq)

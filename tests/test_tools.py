@@ -73,3 +73,42 @@ def test_setup_py_builds_through_make():
                        timeout=120)
     assert r.returncode == 0, r.stderr
     assert "BuildHip: make -C" in r.stdout and "tf_flash_attention_amd" in r.stdout
+
+
+# ---- tools/asm_equal.py: the SCALAR-ONLY verdict (equal counts and resources, only s_* lines moved)
+ASM_EQUAL = os.path.join(ROOT, "tools", "asm_equal.py")
+KERNEL_S = """	.type	_Z1kv,@function
+_Z1kv:
+{body}	s_endpgm
+	.amdhsa_kernel _Z1kv
+		.amdhsa_next_free_vgpr 2
+		.amdhsa_next_free_sgpr 6
+	.end_amdhsa_kernel
+.Lfunc_end0:
+; NumVgprs: 2
+"""
+LINES = ["s_load_dword s0, s[4:5], 0x0", "s_mov_b32 s1, 0", "v_mov_b32_e32 v0, s0", "v_add_u32_e32 v1, v0, v0"]
+
+
+def _asm_equal(tmp_path, new_order, *flags):
+    old, new = tmp_path / "old.s", tmp_path / "new.s"
+    old.write_text(KERNEL_S.format(body="".join(f"\t{ln}\n" for ln in LINES)))
+    new.write_text(KERNEL_S.format(body="".join(f"\t{LINES[i]}\n" for i in new_order)))
+    return subprocess.run([sys.executable, ASM_EQUAL, *flags, str(old), str(new)], capture_output=True, text=True)
+
+
+def test_asm_equal_scalar_only(tmp_path):
+    """Two scalar lines swapped: SCALAR-ONLY, counted on its own, and accepted only under --scalar-ok."""
+    r = _asm_equal(tmp_path, [1, 0, 2, 3])
+    assert r.returncode == 1 and r.stdout.startswith("SCALAR-ONLY") and "1 not identical, 1 of them scalar-only" in r.stdout
+    r = _asm_equal(tmp_path, [1, 0, 2, 3], "--scalar-ok")
+    assert r.returncode == 0 and r.stdout.startswith("SCALAR-ONLY")
+    r = _asm_equal(tmp_path, [0, 1, 2, 3])
+    assert r.returncode == 0 and r.stdout.startswith("IDENTICAL") and "0 not identical" in r.stdout
+
+
+def test_asm_equal_vector_line_moved(tmp_path):
+    """The two vector lines swapped (counts and resources still equal): DIFFERS, whatever the flag."""
+    for flags in ((), ("--scalar-ok",)):
+        r = _asm_equal(tmp_path, [0, 1, 3, 2], *flags)
+        assert r.returncode == 1 and r.stdout.startswith("DIFFERS") and "scalar-only" not in r.stdout

@@ -78,6 +78,19 @@ EXPORTED_SYMBOLS = (
 )
 
 
+DECODE_CACHES = ("ragged", "paged")
+DECODE_FORMS = ("plain", "window", "prefill")
+
+
+def decode_entry_points(cache, form, fp8):
+    """The (plan, workspace_bytes, forward) entry-point names of the decode forward over ``cache`` (of
+    DECODE_CACHES) in ``form`` (of DECODE_FORMS); an FP8 cache shares the plan and workspace of the fp16 one."""
+    if cache not in DECODE_CACHES or form not in DECODE_FORMS:
+        raise ValueError(f"no decode forward over cache {cache!r} in form {form!r}")
+    stem = f"fa_forward_{cache}" + ("" if form == "plain" else f"_{form}")
+    return stem + "_plan", stem + "_workspace_bytes", stem + ("_fp8" if fp8 else "")
+
+
 class LibraryNotBuiltError(RuntimeError):
     pass
 
@@ -160,73 +173,27 @@ def _declare(lib):
         lib.fa_forward_grouped_workspace_bytes.restype = ctypes.c_size_t
         lib.fa_forward_grouped.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
         lib.fa_forward_grouped.restype = ctypes.c_int
-    # (absent from a library built before the ragged forward, as above)
-    if hasattr(lib, "fa_forward_ragged"):
-        lib.fa_forward_ragged_plan.argtypes = [P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
-        lib.fa_forward_ragged_plan.restype = ctypes.c_int
-        lib.fa_forward_ragged_workspace_bytes.argtypes = [P, ctypes.c_int32]
-        lib.fa_forward_ragged_workspace_bytes.restype = ctypes.c_size_t
-        lib.fa_forward_ragged.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32,
-                                          vp, vp, vp, vp, ctypes.c_size_t]
-        lib.fa_forward_ragged.restype = ctypes.c_int
-    # (absent from a library built before the paged forward, as above)
-    if hasattr(lib, "fa_forward_paged"):
-        lib.fa_forward_paged_plan.argtypes = [P, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
-        lib.fa_forward_paged_plan.restype = ctypes.c_int
-        lib.fa_forward_paged_workspace_bytes.argtypes = [P, ctypes.c_int32, ctypes.c_int32]
-        lib.fa_forward_paged_workspace_bytes.restype = ctypes.c_size_t
-        lib.fa_forward_paged.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp,
-                                         ctypes.c_size_t]
-        lib.fa_forward_paged.restype = ctypes.c_int
-    # (absent from a library built before the FP8 K/V cache, as above)
-    if hasattr(lib, "fa_forward_ragged_fp8"):
-        lib.fa_forward_ragged_fp8.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32,
-                                              ctypes.c_int32, vp, vp, vp, vp, ctypes.c_size_t]
-        lib.fa_forward_ragged_fp8.restype = ctypes.c_int
-        lib.fa_forward_paged_fp8.argtypes = [vp, P, ctypes.c_int32, vp, vp, vp, vp, vp, vp, ctypes.c_int32,
-                                             ctypes.c_int32, ctypes.c_int64, vp, ctypes.c_int32, ctypes.c_int32,
-                                             vp, vp, vp, vp, ctypes.c_size_t]
-        lib.fa_forward_paged_fp8.restype = ctypes.c_int
-    # (absent from a library built before sliding-window decode, as above): the twins' argument lists with
-    # `window` where tail_causal stands, and `window` after the plan functions' own arguments
-    if hasattr(lib, "fa_forward_ragged_window"):
-        i32 = ctypes.c_int32
-        lib.fa_forward_ragged_window_plan.argtypes = [P, i32, i32, ctypes.POINTER(i32)]
-        lib.fa_forward_ragged_window_plan.restype = ctypes.c_int
-        lib.fa_forward_paged_window_plan.argtypes = [P, i32, i32, i32, ctypes.POINTER(i32)]
-        lib.fa_forward_paged_window_plan.restype = ctypes.c_int
-        lib.fa_forward_ragged_window_workspace_bytes.argtypes = [P, i32, i32]
-        lib.fa_forward_ragged_window_workspace_bytes.restype = ctypes.c_size_t
-        lib.fa_forward_paged_window_workspace_bytes.argtypes = [P, i32, i32, i32]
-        lib.fa_forward_paged_window_workspace_bytes.restype = ctypes.c_size_t
-        lib.fa_forward_ragged_window.argtypes = list(lib.fa_forward_ragged.argtypes)
-        lib.fa_forward_ragged_window.restype = ctypes.c_int
-        lib.fa_forward_paged_window.argtypes = list(lib.fa_forward_paged.argtypes)
-        lib.fa_forward_paged_window.restype = ctypes.c_int
-        lib.fa_forward_ragged_window_fp8.argtypes = list(lib.fa_forward_ragged_fp8.argtypes)
-        lib.fa_forward_ragged_window_fp8.restype = ctypes.c_int
-        lib.fa_forward_paged_window_fp8.argtypes = list(lib.fa_forward_paged_fp8.argtypes)
-        lib.fa_forward_paged_window_fp8.restype = ctypes.c_int
-    # (absent from a library built before the query-blocked forwards, as above): the twins' argument lists
-    if hasattr(lib, "fa_forward_ragged_prefill"):
-        i32 = ctypes.c_int32
-        lib.fa_forward_ragged_prefill_plan.argtypes = [P, i32, ctypes.POINTER(i32)]
-        lib.fa_forward_ragged_prefill_plan.restype = ctypes.c_int
-        lib.fa_forward_paged_prefill_plan.argtypes = [P, i32, i32, ctypes.POINTER(i32)]
-        lib.fa_forward_paged_prefill_plan.restype = ctypes.c_int
-        lib.fa_forward_ragged_prefill_workspace_bytes.argtypes = [P, i32]
-        lib.fa_forward_ragged_prefill_workspace_bytes.restype = ctypes.c_size_t
-        lib.fa_forward_paged_prefill_workspace_bytes.argtypes = [P, i32, i32]
-        lib.fa_forward_paged_prefill_workspace_bytes.restype = ctypes.c_size_t
-        lib.fa_forward_ragged_prefill.argtypes = list(lib.fa_forward_ragged.argtypes)
-        lib.fa_forward_ragged_prefill.restype = ctypes.c_int
-        lib.fa_forward_paged_prefill.argtypes = list(lib.fa_forward_paged.argtypes)
-        lib.fa_forward_paged_prefill.restype = ctypes.c_int
-        lib.fa_forward_ragged_prefill_fp8.argtypes = list(lib.fa_forward_ragged_fp8.argtypes)
-        lib.fa_forward_ragged_prefill_fp8.restype = ctypes.c_int
-        lib.fa_forward_paged_prefill_fp8.argtypes = list(lib.fa_forward_paged_fp8.argtypes)
-        lib.fa_forward_paged_prefill_fp8.restype = ctypes.c_int
+    # The decode forwards (include/fa_api.h): a cache times a form times the cache's precision, every argument
+    # list made of the same pieces.  A paged cache adds (page) to the plan functions and (block_table, max_pages,
+    # page, num_pages) to the forward, an FP8 cache (k_scale, v_scale) to the forward, a window `window` after the
+    # plan functions' own arguments and where the forward's tail_causal stands.  (Each is absent from a library
+    # built before its feature, as above.)
+    i32, i64 = ctypes.c_int32, ctypes.c_int64
+    for cache in DECODE_CACHES:
+        for form in DECODE_FORMS:
+            own = [P, i32] + ([i32] if cache == "paged" else []) + ([i32] if form == "window" else [])
+            for fp8 in (False, True):
+                plan, ws_bytes, forward = decode_entry_points(cache, form, fp8)
+                if not hasattr(lib, forward):
+                    continue
+                getattr(lib, plan).argtypes = own + [ctypes.POINTER(i32)]
+                getattr(lib, plan).restype = ctypes.c_int
+                getattr(lib, ws_bytes).argtypes = own
+                getattr(lib, ws_bytes).restype = ctypes.c_size_t
+                getattr(lib, forward).argtypes = ([vp, P, i32, vp, vp, vp] + ([vp, vp] if fp8 else [])
+                                                  + ([vp, i32, i32, i64] if cache == "paged" else [])
+                                                  + [vp, i32, i32, vp, vp, vp, vp, ctypes.c_size_t])
+                getattr(lib, forward).restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

@@ -772,77 +772,174 @@ int fa_forward_grouped(void* stream, const fa_problem* p, int32_t kv_group, cons
                     [&](int64_t) { return fa::launch_fwd_f16_gqa(ga, s); });
 }
 
-int fa_forward_ragged_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]) {
-  const int st = check_ragged(p, kv_group);
+// ---- the decode forwards (include/fa_api.h): a K/V cache times a form.  The cache is
+// ragged or paged, fp16 or FP8; the form plain, sliding-window or query-blocked.  What a call is:
+struct PagedPart {  // the block table of a paged cache
+  const int32_t* block_table;
+  int32_t max_pages, page;
+  int64_t num_pages;
+};
+struct Kv8 {  // the scales of an FP8 cache (either may be null)
+  const float *k_scale, *v_scale;
+};
+struct DecodeKind {
+  const PagedPart* paged;  // null: a ragged cache
+  const Kv8* kv8;          // null: an fp16 cache
+  const int32_t* window;   // null: no window
+  bool prefill;            // the query-blocked form
+};
+
+// the checks and the un-windowed, un-blocked plan of a cache; `page` null: ragged
+static int check_cache(const fa_problem* p, int32_t kv_group, const int32_t* page) {
+  return page ? check_paged(p, kv_group, *page) : check_ragged(p, kv_group);
+}
+static GroupedPlan cache_plan(const fa_problem* p, int32_t kv_group, const int32_t* page) {
+  return page ? paged_plan(p, kv_group, *page) : ragged_plan(p, kv_group);
+}
+
+// the _plan and _workspace_bytes entry points of every cache and form (the FP8 caches share the fp16 ones')
+static int decode_plan(const fa_problem* p, int32_t kv_group, const int32_t* page, const int32_t* window, bool prefill,
+                       int32_t* out) {
+  const int st = check_cache(p, kv_group, page);
   if (st != FA_OK) return st;
+  const int wst = window ? check_window(*window) : FA_OK;
+  if (wst != FA_OK) return wst;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  write_plan(out, ragged_plan(p, kv_group));
+  const GroupedPlan base = cache_plan(p, kv_group, page);
+  if (window) write_window_plan(out, window_plan(p, base, *window));
+  else if (prefill) write_prefill_plan(out, prefill_plan(p, kv_group, base, page ? *page : 0));
+  else write_plan(out, base);
   return FA_OK;
 }
 
-size_t fa_forward_ragged_workspace_bytes(const fa_problem* p, int32_t kv_group) {
-  if (check_ragged(p, kv_group) != FA_OK) return 0;
-  const GroupedPlan s = ragged_plan(p, kv_group);
-  return s.nchunks ? grouped_ws_bytes(p, kv_group, s) : 0;
+static size_t decode_workspace_bytes(const fa_problem* p, int32_t kv_group, const int32_t* page, const int32_t* window,
+                                     bool prefill) {
+  if (check_cache(p, kv_group, page) != FA_OK || (window && check_window(*window) != FA_OK)) return 0;
+  const GroupedPlan base = cache_plan(p, kv_group, page);
+  if (prefill) {
+    const PrefillPlan w = prefill_plan(p, kv_group, base, page ? *page : 0);
+    return w.g.nchunks ? prefill_ws_bytes(p, kv_group, w) : 0;
+  }
+  const GroupedPlan g = window ? window_plan(p, base, *window).g : base;
+  return g.nchunks ? grouped_ws_bytes(p, kv_group, g) : 0;
 }
 
-// An FP8 K/V cache of the ragged / paged forward: null for an fp16 cache, else the scales (either may be null)
-struct Kv8 {
-  const float *k_scale, *v_scale;
-};
-
-// fa_forward_ragged, and fa_forward_ragged_fp8 with kv8: the same checks, plan, workspace and launches.  With
-// `window` the sliding-window forms: the tail form itself where the window reaches the capacity, else the
-// window's plan and kernels.  With `prefill` the query-blocked forms: the twin itself where one block holds the
-// queries, else the blocked plan and kernels.
-static int forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
-                          const Kv8* kv8, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l,
-                          void* m, void* workspace, size_t workspace_bytes, const int32_t* window = nullptr,
-                          bool prefill = false) {
-  const int st = check_ragged(p, kv_group);
+// Every decode forward: the same checks, plan, workspace and launches.  K and V are the cache or the pools.  With
+// a window the sliding-window form: the tail form itself where the window reaches the capacity, else the window's
+// plan and kernels.  With `prefill` the query-blocked form: the twin itself where one block holds the queries, else
+// the blocked plan and kernels.
+static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
+                          const DecodeKind& c, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
+                          void* l, void* m, void* workspace, size_t workspace_bytes) {
+  const PagedPart* pg = c.paged;
+  const int32_t* page = pg ? &pg->page : nullptr;
+  const std::string name = pg ? "paged" : "ragged";
+  const int st = check_cache(p, kv_group, page);
   if (st != FA_OK) return st;
   const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
   if (kst != FA_OK) return kst;
-  const int wst = window ? check_window(*window) : FA_OK;
+  const int wst = c.window ? check_window(*c.window) : FA_OK;
   if (wst != FA_OK) return wst;
-  const WindowPlan wp = window_plan(p, ragged_plan(p, kv_group), window ? *window : 0x7fffffff);
-  const PrefillPlan pp = prefill ? prefill_plan(p, kv_group, wp.g, 0) : PrefillPlan{};
-  const bool blocked = prefill && !pp.delegated;
+  if (pg) {
+    if (pg->max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages must be >= 1");
+    if ((int64_t)pg->max_pages * pg->page != p->k_seq[0])
+      return set_error(FA_ERR_INVALID_ARGUMENT,
+                       "paged forward: max_pages * page = " + std::to_string((int64_t)pg->max_pages * pg->page) +
+                           " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
+    if (pg->num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: num_pages must be >= 1");
+  }
+  const WindowPlan wp = window_plan(p, cache_plan(p, kv_group, page), c.window ? *c.window : 0x7fffffff);
+  const PrefillPlan pp = c.prefill ? prefill_plan(p, kv_group, wp.g, pg ? pg->page : 0) : PrefillPlan{};
+  const bool blocked = c.prefill && !pp.delegated;
   const GroupedPlan& gp = blocked ? pp.g : wp.g;
-  const bool win = window && !wp.delegated;
+  const bool win = c.window && !wp.delegated;
   if (gp.nchunks == 0)
     return set_error(FA_ERR_UNSUPPORTED,
-                     prefill ? "ragged prefill forward: outside the envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
-                               "1 <= kv_group <= 128, nq >= 1, nk >= 1)"
-                             : "ragged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
-                               "kv_group * pitch <= 128, nq >= 1, nk >= 1)");
+                     name + (c.prefill ? " prefill forward: outside the envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                                         "1 <= kv_group <= 128, nq >= 1, nk >= 1"
+                                       : " forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                                         "kv_group * pitch <= 128, nq >= 1, nk >= 1") +
+                         (pg ? ", page % 64 == 0)" : ")"));
   if (!workspace || workspace_bytes < (blocked ? prefill_ws_bytes(p, kv_group, pp) : grouped_ws_bytes(p, kv_group, gp)))
-    return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
-                     prefill ? "forward workspace is smaller than fa_forward_ragged_prefill_workspace_bytes()"
-                             : "forward workspace is smaller than fa_forward_ragged_workspace_bytes()");
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "forward workspace is smaller than fa_forward_" + name +
+                                                     (c.prefill ? "_prefill" : "") + "_workspace_bytes()");
   FA_DIAG_COUNT(0);
   if (p->b == 0) return FA_OK;
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
-  fa::RaggedFp8Args fa8;  // (ra alone for an fp16 cache)
-  fa::RaggedArgs& ra = fa8.r;
+  if (pg && !pg->block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null block_table");
+  if (pg && (!K || !V)) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null K_pool or V_pool");
+  fa::PagedFp8Args all = {};  // the widest cache's arguments: a narrower cache sends the part it has
+  fa::PagedArgs& pa = all.p;
+  fa::RaggedArgs& ra = pa.r;
   fill_ragged(p, gp, kv_group, k_lens, kv_per_len, tail_causal, &ra);
-  if (kv8) { fa8.k_scale = kv8->k_scale; fa8.v_scale = kv8->v_scale; }
+  if (c.kv8) { all.k_scale = c.kv8->k_scale; all.v_scale = c.kv8->v_scale; }
+  FewqPtrs ptrs = {Q, K, V, O, l, m, workspace, c.kv8 ? 1 : 2};
+  if (pg) {
+    pa.block_table = pg->block_table; pa.max_pages = pg->max_pages; pa.page = pg->page;
+    pa.last_page = (int32_t)(pg->num_pages - 1 < 0x7fffffff ? pg->num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
+    ra.g.s.f.K = K; ra.g.s.f.V = V;  // the pools are not sliced per launch: the table says where a slice's keys are
+    ptrs.K = ptrs.V = nullptr;
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return fewq_slabs(p, {Q, K, V, O, l, m, workspace, kv8 ? 1 : 2}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
+  // the form picks the launcher, the argument struct its instance
+  auto launch = [&](const auto& args) {
+    using Args = std::decay_t<decltype(args)>;
+    if (win) return fa::launch_fwd_f16_window<Args>({args, *c.window}, s);
+    if (blocked) return fa::launch_fwd_f16_prefill<Args>({args, pp.nqb}, s);
+    return fa::launch_fwd_f16_decode(args, s);
+  };
+  return fewq_slabs(p, ptrs, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
     ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
-    if (win)
-      return kv8 ? fa::launch_fwd_f16_window_ragged_fp8({fa8, *window}, s) : fa::launch_fwd_f16_window_ragged({ra, *window}, s);
-    if (blocked)
-      return kv8 ? fa::launch_fwd_f16_prefill_ragged_fp8({fa8, pp.nqb}, s) : fa::launch_fwd_f16_prefill_ragged({ra, pp.nqb}, s);
-    return kv8 ? fa::launch_fwd_f16_ragged_fp8(fa8, s) : fa::launch_fwd_f16_ragged(ra, s);
+    if (pg && c.kv8) return launch(all);
+    if (pg) return launch(pa);
+    if (c.kv8) return launch(fa::RaggedFp8Args{ra, all.k_scale, all.v_scale});
+    return launch(ra);
   }, blocked ? pp.nqb : 1);
+}
+
+// the twelve forwards and their plans: ragged / paged, then the same with a window (the tail rule is implied) and
+// over query blocks
+int fa_forward_ragged_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]) {
+  return decode_plan(p, kv_group, nullptr, nullptr, false, out);
+}
+size_t fa_forward_ragged_workspace_bytes(const fa_problem* p, int32_t kv_group) {
+  return decode_workspace_bytes(p, kv_group, nullptr, nullptr, false);
+}
+int fa_forward_paged_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]) {
+  return decode_plan(p, kv_group, &page, nullptr, false, out);
+}
+size_t fa_forward_paged_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page) {
+  return decode_workspace_bytes(p, kv_group, &page, nullptr, false);
+}
+int fa_forward_ragged_window_plan(const fa_problem* p, int32_t kv_group, int32_t window, int32_t out[8]) {
+  return decode_plan(p, kv_group, nullptr, &window, false, out);
+}
+size_t fa_forward_ragged_window_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t window) {
+  return decode_workspace_bytes(p, kv_group, nullptr, &window, false);
+}
+int fa_forward_paged_window_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window, int32_t out[8]) {
+  return decode_plan(p, kv_group, &page, &window, false, out);
+}
+size_t fa_forward_paged_window_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window) {
+  return decode_workspace_bytes(p, kv_group, &page, &window, false);
+}
+int fa_forward_ragged_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t out[8]) {
+  return decode_plan(p, kv_group, nullptr, nullptr, true, out);
+}
+size_t fa_forward_ragged_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group) {
+  return decode_workspace_bytes(p, kv_group, nullptr, nullptr, true);
+}
+int fa_forward_paged_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[8]) {
+  return decode_plan(p, kv_group, &page, nullptr, true, out);
+}
+size_t fa_forward_paged_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page) {
+  return decode_workspace_bytes(p, kv_group, &page, nullptr, true);
 }
 
 int fa_forward_ragged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
                       const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m,
                       void* workspace, size_t workspace_bytes) {
-  return forward_ragged(stream, p, kv_group, Q, K, V, nullptr, k_lens, kv_per_len, tail_causal, O, l, m, workspace,
-                        workspace_bytes);
+  return forward_decode(stream, p, kv_group, Q, K, V, {}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_ragged_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K8,
@@ -850,136 +947,30 @@ int fa_forward_ragged_fp8(void* stream, const fa_problem* p, int32_t kv_group, c
                           int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m, void* workspace,
                           size_t workspace_bytes) {
   const Kv8 kv8 = {k_scale, v_scale};
-  return forward_ragged(stream, p, kv_group, Q, K8, V8, &kv8, k_lens, kv_per_len, tail_causal, O, l, m, workspace,
-                        workspace_bytes);
-}
-
-int fa_forward_paged_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]) {
-  const int st = check_paged(p, kv_group, page);
-  if (st != FA_OK) return st;
-  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  write_plan(out, paged_plan(p, kv_group, page));
-  return FA_OK;
-}
-
-size_t fa_forward_paged_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page) {
-  if (check_paged(p, kv_group, page) != FA_OK) return 0;
-  const GroupedPlan s = paged_plan(p, kv_group, page);
-  return s.nchunks ? grouped_ws_bytes(p, kv_group, s) : 0;
-}
-
-// fa_forward_paged, and fa_forward_paged_fp8 with kv8
-static int forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
-                         const void* V_pool, const Kv8* kv8, const int32_t* block_table, int32_t max_pages, int32_t page,
-                         int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
-                         void* l, void* m, void* workspace, size_t workspace_bytes, const int32_t* window = nullptr,
-                         bool prefill = false) {
-  const int st = check_paged(p, kv_group, page);
-  if (st != FA_OK) return st;
-  const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
-  if (kst != FA_OK) return kst;
-  const int wst = window ? check_window(*window) : FA_OK;
-  if (wst != FA_OK) return wst;
-  if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages must be >= 1");
-  if ((int64_t)max_pages * page != p->k_seq[0])
-    return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages * page = " + std::to_string((int64_t)max_pages * page) +
-                                                  " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
-  if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: num_pages must be >= 1");
-  const WindowPlan wp = window_plan(p, paged_plan(p, kv_group, page), window ? *window : 0x7fffffff);
-  const PrefillPlan pp = prefill ? prefill_plan(p, kv_group, wp.g, page) : PrefillPlan{};
-  const bool blocked = prefill && !pp.delegated;
-  const GroupedPlan& gp = blocked ? pp.g : wp.g;
-  const bool win = window && !wp.delegated;
-  if (gp.nchunks == 0)
-    return set_error(FA_ERR_UNSUPPORTED,
-                     prefill ? "paged prefill forward: outside the envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
-                               "1 <= kv_group <= 128, nq >= 1, nk >= 1, page % 64 == 0)"
-                             : "paged forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
-                               "kv_group * pitch <= 128, nq >= 1, nk >= 1, page % 64 == 0)");
-  if (!workspace || workspace_bytes < (blocked ? prefill_ws_bytes(p, kv_group, pp) : grouped_ws_bytes(p, kv_group, gp)))
-    return set_error(FA_ERR_WORKSPACE_TOO_SMALL,
-                     prefill ? "forward workspace is smaller than fa_forward_paged_prefill_workspace_bytes()"
-                             : "forward workspace is smaller than fa_forward_paged_workspace_bytes()");
-  FA_DIAG_COUNT(0);
-  if (p->b == 0) return FA_OK;
-  if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
-  if (!block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null block_table");
-  if (!K_pool || !V_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null K_pool or V_pool");
-  fa::PagedFp8Args pa8;  // (pa alone for fp16 pools)
-  fa::PagedArgs& pa = pa8.p;
-  fa::RaggedArgs& ra = pa.r;
-  if (kv8) { pa8.k_scale = kv8->k_scale; pa8.v_scale = kv8->v_scale; }
-  fill_ragged(p, gp, kv_group, k_lens, kv_per_len, tail_causal, &ra);
-  pa.block_table = block_table; pa.max_pages = max_pages; pa.page = page;
-  pa.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
-  ra.g.s.f.K = K_pool; ra.g.s.f.V = V_pool;  // the pools are not sliced per launch: the table says where a slice's keys are
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return fewq_slabs(p, {Q, nullptr, nullptr, O, l, m, workspace}, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
-    ra.len0 = b0 / kv_per_len; ra.rem0 = (int32_t)(b0 % kv_per_len);
-    if (win)
-      return kv8 ? fa::launch_fwd_f16_window_paged_fp8({pa8, *window}, s) : fa::launch_fwd_f16_window_paged({pa, *window}, s);
-    if (blocked)
-      return kv8 ? fa::launch_fwd_f16_prefill_paged_fp8({pa8, pp.nqb}, s) : fa::launch_fwd_f16_prefill_paged({pa, pp.nqb}, s);
-    return kv8 ? fa::launch_fwd_f16_paged_fp8(pa8, s) : fa::launch_fwd_f16_paged(pa, s);
-  }, blocked ? pp.nqb : 1);
+  return forward_decode(stream, p, kv_group, Q, K8, V8, {nullptr, &kv8}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_paged(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
                      const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
                      const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m,
                      void* workspace, size_t workspace_bytes) {
-  return forward_paged(stream, p, kv_group, Q, K_pool, V_pool, nullptr, block_table, max_pages, page, num_pages, k_lens,
-                       kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  return forward_decode(stream, p, kv_group, Q, K_pool, V_pool, {&pg}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_paged_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool8,
                          const void* V_pool8, const float* k_scale, const float* v_scale, const int32_t* block_table,
                          int32_t max_pages, int32_t page, int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len,
                          int32_t tail_causal, void* O, void* l, void* m, void* workspace, size_t workspace_bytes) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
   const Kv8 kv8 = {k_scale, v_scale};
-  return forward_paged(stream, p, kv_group, Q, K_pool8, V_pool8, &kv8, block_table, max_pages, page, num_pages, k_lens,
-                       kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
-}
-
-// ---- the sliding-window forms (include/fa_api.h): the twins' paths with the window's plan
-
-int fa_forward_ragged_window_plan(const fa_problem* p, int32_t kv_group, int32_t window, int32_t out[8]) {
-  const int st = check_ragged(p, kv_group);
-  if (st != FA_OK) return st;
-  const int wst = check_window(window);
-  if (wst != FA_OK) return wst;
-  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  write_window_plan(out, window_plan(p, ragged_plan(p, kv_group), window));
-  return FA_OK;
-}
-
-size_t fa_forward_ragged_window_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t window) {
-  if (check_ragged(p, kv_group) != FA_OK || check_window(window) != FA_OK) return 0;
-  const WindowPlan w = window_plan(p, ragged_plan(p, kv_group), window);
-  return w.g.nchunks ? grouped_ws_bytes(p, kv_group, w.g) : 0;
-}
-
-int fa_forward_paged_window_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window, int32_t out[8]) {
-  const int st = check_paged(p, kv_group, page);
-  if (st != FA_OK) return st;
-  const int wst = check_window(window);
-  if (wst != FA_OK) return wst;
-  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  write_window_plan(out, window_plan(p, paged_plan(p, kv_group, page), window));
-  return FA_OK;
-}
-
-size_t fa_forward_paged_window_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window) {
-  if (check_paged(p, kv_group, page) != FA_OK || check_window(window) != FA_OK) return 0;
-  const WindowPlan w = window_plan(p, paged_plan(p, kv_group, page), window);
-  return w.g.nchunks ? grouped_ws_bytes(p, kv_group, w.g) : 0;
+  return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_ragged_window(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K,
                              const void* V, const int32_t* k_lens, int32_t kv_per_len, int32_t window, void* O, void* l,
                              void* m, void* workspace, size_t workspace_bytes) {
-  return forward_ragged(stream, p, kv_group, Q, K, V, nullptr, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes,
-                        &window);
+  return forward_decode(stream, p, kv_group, Q, K, V, {nullptr, nullptr, &window}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_ragged_window_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K8,
@@ -987,16 +978,15 @@ int fa_forward_ragged_window_fp8(void* stream, const fa_problem* p, int32_t kv_g
                                  int32_t kv_per_len, int32_t window, void* O, void* l, void* m, void* workspace,
                                  size_t workspace_bytes) {
   const Kv8 kv8 = {k_scale, v_scale};
-  return forward_ragged(stream, p, kv_group, Q, K8, V8, &kv8, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes,
-                        &window);
+  return forward_decode(stream, p, kv_group, Q, K8, V8, {nullptr, &kv8, &window}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_paged_window(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
                             const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page,
                             int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t window, void* O, void* l,
                             void* m, void* workspace, size_t workspace_bytes) {
-  return forward_paged(stream, p, kv_group, Q, K_pool, V_pool, nullptr, block_table, max_pages, page, num_pages, k_lens,
-                       kv_per_len, 1, O, l, m, workspace, workspace_bytes, &window);
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  return forward_decode(stream, p, kv_group, Q, K_pool, V_pool, {&pg, nullptr, &window}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_paged_window_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool8,
@@ -1004,46 +994,15 @@ int fa_forward_paged_window_fp8(void* stream, const fa_problem* p, int32_t kv_gr
                                 int32_t max_pages, int32_t page, int64_t num_pages, const int32_t* k_lens,
                                 int32_t kv_per_len, int32_t window, void* O, void* l, void* m, void* workspace,
                                 size_t workspace_bytes) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
   const Kv8 kv8 = {k_scale, v_scale};
-  return forward_paged(stream, p, kv_group, Q, K_pool8, V_pool8, &kv8, block_table, max_pages, page, num_pages, k_lens,
-                       kv_per_len, 1, O, l, m, workspace, workspace_bytes, &window);
-}
-
-// ---- the query-blocked forms (include/fa_api.h): the twins' paths with the blocked plan
-
-int fa_forward_ragged_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t out[8]) {
-  const int st = check_ragged(p, kv_group);
-  if (st != FA_OK) return st;
-  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  write_prefill_plan(out, prefill_plan(p, kv_group, ragged_plan(p, kv_group), 0));
-  return FA_OK;
-}
-
-size_t fa_forward_ragged_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group) {
-  if (check_ragged(p, kv_group) != FA_OK) return 0;
-  const PrefillPlan w = prefill_plan(p, kv_group, ragged_plan(p, kv_group), 0);
-  return w.g.nchunks ? prefill_ws_bytes(p, kv_group, w) : 0;
-}
-
-int fa_forward_paged_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[8]) {
-  const int st = check_paged(p, kv_group, page);
-  if (st != FA_OK) return st;
-  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  write_prefill_plan(out, prefill_plan(p, kv_group, paged_plan(p, kv_group, page), page));
-  return FA_OK;
-}
-
-size_t fa_forward_paged_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page) {
-  if (check_paged(p, kv_group, page) != FA_OK) return 0;
-  const PrefillPlan w = prefill_plan(p, kv_group, paged_plan(p, kv_group, page), page);
-  return w.g.nchunks ? prefill_ws_bytes(p, kv_group, w) : 0;
+  return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, &window}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_ragged_prefill(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K,
                               const void* V, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
                               void* l, void* m, void* workspace, size_t workspace_bytes) {
-  return forward_ragged(stream, p, kv_group, Q, K, V, nullptr, k_lens, kv_per_len, tail_causal, O, l, m, workspace,
-                        workspace_bytes, nullptr, true);
+  return forward_decode(stream, p, kv_group, Q, K, V, {nullptr, nullptr, nullptr, true}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_ragged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K8,
@@ -1051,16 +1010,15 @@ int fa_forward_ragged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_
                                   int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m, void* workspace,
                                   size_t workspace_bytes) {
   const Kv8 kv8 = {k_scale, v_scale};
-  return forward_ragged(stream, p, kv_group, Q, K8, V8, &kv8, k_lens, kv_per_len, tail_causal, O, l, m, workspace,
-                        workspace_bytes, nullptr, true);
+  return forward_decode(stream, p, kv_group, Q, K8, V8, {nullptr, &kv8, nullptr, true}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_paged_prefill(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
                              const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page,
                              int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
                              void* l, void* m, void* workspace, size_t workspace_bytes) {
-  return forward_paged(stream, p, kv_group, Q, K_pool, V_pool, nullptr, block_table, max_pages, page, num_pages, k_lens,
-                       kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes, nullptr, true);
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  return forward_decode(stream, p, kv_group, Q, K_pool, V_pool, {&pg, nullptr, nullptr, true}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool8,
@@ -1068,9 +1026,9 @@ int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_g
                                  int32_t max_pages, int32_t page, int64_t num_pages, const int32_t* k_lens,
                                  int32_t kv_per_len, int32_t tail_causal, void* O, void* l, void* m, void* workspace,
                                  size_t workspace_bytes) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
   const Kv8 kv8 = {k_scale, v_scale};
-  return forward_paged(stream, p, kv_group, Q, K_pool8, V_pool8, &kv8, block_table, max_pages, page, num_pages, k_lens,
-                       kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes, nullptr, true);
+  return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, nullptr, true}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
 size_t fa_backward_workspace_bytes(const fa_problem* p) {

@@ -3,22 +3,22 @@
 // fwd_f16_core runs one workgroup's share of a (batch, head) slice: 32*NW query rows from q0
 // against the key tiles [kt0, kt0 + 64*ntiles), from the prologue loads through the last
 // ring step, and hands back each wave's unnormalised accumulator and softmax statistics
-// (WaveState).  Seven
-// kernels wrap it and differ only in which block gets which rows and keys and in the epilogue:
+// (WaveState).  Six
+// kernel templates wrap it and differ only in which block gets which rows and keys and in the epilogue:
 //   * fwd_f16_kernel (fa_fwd_f16.hip): block -> (slice, query block), the rule-bounded key
 //     range of that block, normalises and writes O, l, m;
 //   * splitk_partial_kernel (fa_fwd_f16_splitk.hip): block -> (slice, key chunk) of the single
 //     query block, writes the partial and its statistics to the workspace;
 //   * gqa_partial_kernel (fa_fwd_f16_gqa.hip): block -> (K/V slice, key chunk) with the query heads that
 //     share the K/V slice folded into the block's rows (FoldedRows below), the same partial format;
-//   * ragged_partial_kernel (fa_fwd_f16_ragged.hip): the same block with a per-slice key length read on
-//     the device (the row maps' key_limit / lane_interval below);
-//   * paged_partial_kernel (fa_fwd_f16_paged.hip): the ragged block with each key tile read from a page pool
-//     through a device block table (the row maps' tile below);
-//   * ragged_fp8_partial_kernel / paged_fp8_partial_kernel (fa_fwd_f16_ragged_fp8.hip, _paged_fp8.hip): the last
-//     two over a K/V cache of e4m3fn bytes, converted to fp16 on the way into LDS (KvOf below).
-// The window_* and prefill_* partial kernels (fa_fwd_f16_window.h, fa_fwd_f16_prefill.h) are the last four again, with a
-// lower interval end, and over one block of a longer query axis (a map with kQBlock below).
+//   * decode_partial_kernel (fa_fwd_f16_decode.hip) over the four K/V caches of fa_fwd_f16_decode.h: the same
+//     block with a per-slice key length read on the device (RaggedCache: the row maps' key_limit / lane_interval
+//     below); with each key tile read from a page pool through a device block table (PagedCache: the row maps'
+//     tile below); and the two over a K/V cache of e4m3fn bytes, converted to fp16 on the way into LDS
+//     (RaggedCache8, PagedCache8: KvOf below);
+//   * window_partial_kernel and prefill_partial_kernel (fa_fwd_f16_window.h / .hip, fa_fwd_f16_prefill.h / .hip):
+//     the same four caches again, with a lower interval end, and over one block of a longer query axis (a map
+//     with kQBlock below).
 // The partial kernels share what surrounds the core, and their merge, in fa_fwd_f16_fewq.h.
 // The structure:
 //   * Sᵀ = Kᵀ·Q and Oᵀ = V·Pᵀ on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
@@ -96,7 +96,7 @@ __device__ __forceinline__ u32x2 keep_first(u32x2 v, int n) {
   }
   return v;
 }
-// The element format of K / V.  fp16 unless the row map says kKv8 (fa_fwd_f16_ragged_fp8.hip, _paged_fp8.hip): then
+// The element format of K / V.  fp16 unless the row map says kKv8 (fa_fwd_f16_decode.h: the FP8 caches): then
 // K and V are OCP e4m3fn bytes in the same layouts, a staged chunk is its 8 raw bytes (half the staging registers),
 // and store_from converts it to the fp16 LDS image that the key loop reads, so nothing after the staging knows.
 // The conversion is exact (v_cvt_scalef32_pk_f16_fp8: every e4m3fn value times a power of two 2^e, -8 <= e <= 7,
@@ -152,14 +152,14 @@ struct WaveRegs {
 // The map also says how many of a slice's keys are live and which of them a query may see: key_limit(nk)
 // bounds the staging guards, the whole-tile path, the tile class and the tail mask, while nk itself stays
 // the row stride of K and V; lane_interval is the POL 1 interval of query qi.  These two maps answer nk and
-// the rule's own interval.  A map with kRagged (fa_fwd_f16_ragged.hip) answers a per-slice length below nk,
+// the rule's own interval.  A map with kRagged (fa_fwd_f16_decode.h) answers a per-slice length below nk,
 // and the core then zeroes staged K / V past it element by element: what lies there is not the caller's
 // data, and a NaN or Inf times P = 0 would poison the PV product.
 // Last, where a key tile lies: for a tile-aligned k0, the K and V pointers of channel row 0 at key k0 and the row
 // stride there.  For these maps and RaggedRows (kPaged false) that is K + k0, V + k0 and nk, the contiguous slice,
 // and load_into keeps indexing the slice's rows from key 0 as it always has: a hook that had every map hand back
 // K + k0, V + k0 and nk moved the register allocation of 72 of the 75 existing kernels
-// (profiles/paged_core_asm_equal.txt).  A map with kPaged (fa_fwd_f16_paged.hip) is asked, tile(K, V, k0, ...):
+// (profiles/paged_core_asm_equal.txt).  A map with kPaged (fa_fwd_f16_decode.h) is asked, tile(K, V, k0, ...):
 // it looks the tile's page up in a block table and answers a pointer into a page pool with the page as the
 // stride; a page is a multiple of the 64-key tile, so a tile never straddles two pages.
 // A map with kQBlock (fa_fwd_f16_prefill.h) folds one BLOCK of a longer query axis: it carries the block's first

@@ -1,7 +1,7 @@
 // fa_fwd_f16_fewq.h — the partial + merge pair of the few-query fp16 forwards (gfx950 MFMA).
 //
 // Few queries against many keys leave the GPU empty when one workgroup walks a slice's whole key range, so the
-// split-key, grouped, ragged and paged forwards (fa_fwd_f16_splitk.hip, _gqa.hip, _ragged.hip, _paged.hip) cut
+// split-key, grouped and decode forwards (fa_fwd_f16_splitk.hip, _gqa.hip, _decode.hip, _window.hip, _prefill.hip) cut
 // the key range into the chunks of a plan (fa_api.hip) and run two kernels:
 //   * a partial kernel, one workgroup of 4 waves per (slice, chunk), runs fwd_f16_core (fa_fwd_f16_core.h) over
 //     its chunk only and writes the UNNORMALISED fp32 accumulator of its live rows with their statistics to the
@@ -170,7 +170,7 @@ __device__ __forceinline__ void merge_folded(const GqaArgs& ga, Chunks&& chunks)
   merge_row(ga.s, folded_rows(ga).rec_stride(ga.s.f.rule.q.n), bkv, j * ga.pitch + q, v, chunks(bkv), bkv * ga.g + j, q);
 }
 
-// RaggedRows plus the block table (fa_fwd_f16_core.h: the row maps; the layout: fa_fwd_f16_paged.hip).  K and V
+// RaggedRows plus the block table (fa_fwd_f16_core.h: the row maps; the layout: fa_fwd_f16_decode.h).  K and V
 // handed to tile() are the pools.
 // The core asks for its tiles in ascending order, one per key-loop step, and the entry is a dependent load in
 // front of the tile's K / V loads; asked for on the spot it stalls the wave for a memory round trip per tile
@@ -218,7 +218,7 @@ __device__ __forceinline__ PagedRows paged_rows(const PagedArgs& pa, uint32_t bk
           row[(uint32_t)kt0 / (uint32_t)pa.page]};  // (kt0 < len: a page with a live key)
 }
 
-// ---- an 8-bit K/V cache (fa_fwd_f16_core.h: KvOf; fa_fwd_f16_ragged_fp8.hip, fa_fwd_f16_paged_fp8.hip)
+// ---- an 8-bit K/V cache (fa_fwd_f16_core.h: KvOf; fa_fwd_f16_decode.h: RaggedCache8, PagedCache8)
 
 // The scales of head hk as the core takes them.  k_scale = 2^e * r with e = round(log2 k_scale) clamped to
 // [-8, 7]: kmul = 2^e multiplies K exactly in the conversion to fp16, and qmul = r, in [2^-0.5, 2^0.5) inside the

@@ -1,5 +1,5 @@
-// fa_fwd_f16_prefill.h — what the query-blocked forms of the ragged and paged few-query forwards share
-// (fa_fwd_f16_prefill_ragged.hip, _paged.hip, _ragged_fp8.hip, _paged_fp8.hip).
+// fa_fwd_f16_prefill.h — the query-blocked form of the ragged and paged few-query forwards: what its kernel
+// template over the four caches (fa_fwd_f16_prefill.hip; the caches: fa_fwd_f16_decode.h) is made of.
 //
 // The twins stop at one workgroup's 128 rows.  Here the nq queries are cut into nqb = ceil(nq / P) blocks of
 // P = GqaArgs::pitch queries, P the largest power of two with g * P <= 128, and the g heads of a group are folded

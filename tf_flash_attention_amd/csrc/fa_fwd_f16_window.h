@@ -1,5 +1,5 @@
-// fa_fwd_f16_window.h — what the sliding-window forms of the ragged and paged few-query forwards share
-// (fa_fwd_f16_window_ragged.hip, _paged.hip, _ragged_fp8.hip, _paged_fp8.hip).
+// fa_fwd_f16_window.h — the sliding-window form of the ragged and paged few-query forwards: what its kernel
+// template over the four caches (fa_fwd_f16_window.hip; the caches: fa_fwd_f16_decode.h) is made of.
 //
 // The nq queries are the last nq positions of a sequence of len live keys (the tail rule): query i sits at
 // position len - nq + i and sees the W keys [max(0, pos - W + 1), pos].  The block as a whole sees [lo, len),

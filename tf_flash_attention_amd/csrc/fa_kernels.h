@@ -66,7 +66,7 @@ struct GqaArgs {
   int32_t log2_pitch;
 };
 
-// ragged few-query fp16 forward (fa_fwd_f16_ragged.hip): the grouped forward's layout and plan over the
+// ragged few-query fp16 forward (fa_fwd_f16_decode.h): the grouped forward's layout and plan over the
 // capacity nk = g.s.f.rule.k.n, with the live keys of each K/V slice read on the device
 struct RaggedArgs {
   GqaArgs g;              // g.g >= 1; g.s.k_first = 0 and g.s.k_end = nk (the full rule over the capacity)
@@ -77,7 +77,7 @@ struct RaggedArgs {
   int32_t tail_causal;    // != 0: query i sees keys j <= len - nq + i
 };
 
-// paged few-query fp16 forward (fa_fwd_f16_paged.hip): the ragged forward over a capacity of max_pages * page
+// paged few-query fp16 forward (fa_fwd_f16_decode.h): the ragged forward over a capacity of max_pages * page
 // keys, with K and V held in pools of pages, [num_pages][Hk][channels][page] halfs, and a block table on the
 // device.  r.g.s.f.K / V are the POOLS' base pointers (never advanced per launch) and r.kv_per_len is Hk:
 // K/V slice bkv of the whole call is head bkv % Hk of sequence bkv / Hk.
@@ -89,9 +89,9 @@ struct PagedArgs {
   int32_t last_page;           // num_pages - 1: every loaded entry is clamped to [0, last_page]
 };
 
-// the ragged and the paged forward over an FP8 K/V cache (fa_fwd_f16_ragged_fp8.hip, fa_fwd_f16_paged_fp8.hip):
-// K / V (or the pools) are OCP e4m3fn bytes in the same layouts, and the scales are device arrays of kv_per_len
-// floats, one per K/V head of a sequence, that only the kernels read (null: 1.0)
+// the ragged and the paged forward over an FP8 K/V cache (fa_fwd_f16_decode.h): K / V (or the pools) are OCP
+// e4m3fn bytes in the same layouts, and the scales are device arrays of kv_per_len floats, one per K/V head of a
+// sequence, that only the kernels read (null: 1.0)
 struct RaggedFp8Args {
   RaggedArgs r;
   const float* k_scale;  // true key = k_scale[head] * K8
@@ -215,32 +215,19 @@ hipError_t launch_fwd_f16_splitk(const SplitArgs& sa, hipStream_t s);
 // grouped-query: the same over the group's folded query rows, one workgroup per (K/V slice, key chunk), and the
 // merge writes each query slice's O, l, m — fa_fwd_f16_gqa.hip
 hipError_t launch_fwd_f16_gqa(const GqaArgs& ga, hipStream_t s);
-// the grouped forward with a per-slice key length: a chunk at or past its slice's length returns at once, and
-// the merge folds only the chunks below it — fa_fwd_f16_ragged.hip
-hipError_t launch_fwd_f16_ragged(const RaggedArgs& ra, hipStream_t s);
-hipError_t launch_fwd_f16_ragged_merge(const RaggedArgs& ra, hipStream_t s);  // its second kernel alone
-// the ragged forward over a page pool and a device block table: the same chunks, records and merge, with each
-// key tile's address looked up in the table — fa_fwd_f16_paged.hip
-hipError_t launch_fwd_f16_paged(const PagedArgs& pa, hipStream_t s);
-// the two over an FP8 (e4m3fn) cache with per-head scales: the same kernels with an 8-bit staging, the same merge —
-// fa_fwd_f16_ragged_fp8.hip, fa_fwd_f16_paged_fp8.hip
-hipError_t launch_fwd_f16_ragged_fp8(const RaggedFp8Args& fa8, hipStream_t s);
-hipError_t launch_fwd_f16_paged_fp8(const PagedFp8Args& pa8, hipStream_t s);
-// the same four with a sliding window: work for the window's chunks only — fa_fwd_f16_window_ragged.hip,
-// _window_paged.hip, _window_ragged_fp8.hip, _window_paged_fp8.hip (shared: fa_fwd_f16_window.h)
-hipError_t launch_fwd_f16_window_ragged(const WindowOf<RaggedArgs>& wa, hipStream_t s);
-hipError_t launch_fwd_f16_window_merge(const WindowOf<RaggedArgs>& wa, hipStream_t s);  // the merge of all four
-hipError_t launch_fwd_f16_window_paged(const WindowOf<PagedArgs>& wa, hipStream_t s);
-hipError_t launch_fwd_f16_window_ragged_fp8(const WindowOf<RaggedFp8Args>& wa, hipStream_t s);
-hipError_t launch_fwd_f16_window_paged_fp8(const WindowOf<PagedFp8Args>& wa, hipStream_t s);
-// the same four for any number of queries: one workgroup per (K/V slice, query block, key chunk) —
-// fa_fwd_f16_prefill_ragged.hip, _prefill_paged.hip, _prefill_ragged_fp8.hip, _prefill_paged_fp8.hip (shared:
-// fa_fwd_f16_prefill.h)
-hipError_t launch_fwd_f16_prefill_ragged(const PrefillOf<RaggedArgs>& pf, hipStream_t s);
-hipError_t launch_fwd_f16_prefill_merge(const PrefillOf<RaggedArgs>& pf, hipStream_t s);  // the merge of all four
-hipError_t launch_fwd_f16_prefill_paged(const PrefillOf<PagedArgs>& pf, hipStream_t s);
-hipError_t launch_fwd_f16_prefill_ragged_fp8(const PrefillOf<RaggedFp8Args>& pf, hipStream_t s);
-hipError_t launch_fwd_f16_prefill_paged_fp8(const PrefillOf<PagedFp8Args>& pf, hipStream_t s);
+// The decode forwards: a K/V cache times a form (fa_fwd_f16_decode.h).  Args, the cache: RaggedArgs (the grouped
+// forward with a per-slice key length), PagedArgs (the same over a page pool and a device block table),
+// RaggedFp8Args or PagedFp8Args (the two over an FP8 cache with per-head scales); each launcher is instantiated
+// for these four.  The form: plain (a chunk at or past its slice's length returns at once, and the merge folds only
+// the chunks below it) — fa_fwd_f16_decode.hip; with a sliding window (work for the window's chunks only) —
+// fa_fwd_f16_window.hip; for any number of queries (one workgroup per (K/V slice, query block, key chunk)) —
+// fa_fwd_f16_prefill.hip.
+template <class Args>
+hipError_t launch_fwd_f16_decode(const Args& args, hipStream_t s);
+template <class Args>
+hipError_t launch_fwd_f16_window(const WindowOf<Args>& wa, hipStream_t s);
+template <class Args>
+hipError_t launch_fwd_f16_prefill(const PrefillOf<Args>& pf, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

@@ -708,8 +708,18 @@ def _kv_cache_scales(what, Q, K, V, hk, k_scale, v_scale):
     return fp8
 
 
-def _scale_ptr(t):
-    return t.data_ptr() if t is not None else None
+def _scale_ptrs(fp8, k_scale, v_scale):
+    """The (k_scale, v_scale) arguments that an FP8 forward takes after V (None: 1.0); none for a float16 cache."""
+    return tuple(t.data_ptr() if t is not None else None for t in (k_scale, v_scale)) if fp8 else ()
+
+
+# (cache, form, fp8) -> the names of the (plan, workspace_bytes, forward) entry points
+decode_entry_points = _lib.decode_entry_points
+
+
+def _decode_form(prefill, window):
+    """The form of a decode call: query-blocked, under a window (an int), or plain."""
+    return "prefill" if prefill else "plain" if window is None else "window"
 
 
 def _decode_window(what, window_size, tail_causal, nq):
@@ -797,13 +807,10 @@ def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, 
     window = _decode_window(what, window_size, tail_causal, int(Qs[0]))
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(Qb), Qs, Ks, Q_ch, V_ch)
     L = _lib.lib()
+    plan_name, ws_name, forward_name = decode_entry_points("ragged", _decode_form(prefill, window), fp8)
+    own = (prob, g) + (() if window is None else (window,))  # the plan functions' own arguments
     plan = (ctypes.c_int32 * 8)()
-    if prefill:
-        st = L.fa_forward_ragged_prefill_plan(prob, g, plan)
-    elif window is None:
-        st = L.fa_forward_ragged_plan(prob, g, plan)
-    else:
-        st = L.fa_forward_ragged_window_plan(prob, g, window, plan)
+    st = getattr(L, plan_name)(*own, plan)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     if plan[0] == 0:
@@ -816,42 +823,13 @@ def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, 
     O = torch.empty(Qb + (V_ch,) + Qs, dtype=Q.dtype, device=Q.device)
     l = torch.empty(Qb + Qs, dtype=torch.float32, device=Q.device)
     m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
-    if prefill:
-        ws_bytes = int(L.fa_forward_ragged_prefill_workspace_bytes(prob, g))
-    elif window is None:
-        ws_bytes = int(L.fa_forward_ragged_workspace_bytes(prob, g))
-    else:
-        ws_bytes = int(L.fa_forward_ragged_window_workspace_bytes(prob, g, window))
+    ws_bytes = int(getattr(L, ws_name)(*own))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        if prefill:
-            if fp8:
-                st = L.fa_forward_ragged_prefill_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
-                                                     V.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
-                                                     k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)), O.data_ptr(),
-                                                     l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
-            else:
-                st = L.fa_forward_ragged_prefill(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
-                                                 V.data_ptr(), k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)),
-                                                 O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
-        elif window is not None and fp8:
-            st = L.fa_forward_ragged_window_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
-                                                V.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
-                                                k_lens.data_ptr(), kv_per_len, window, O.data_ptr(), l.data_ptr(),
-                                                m.data_ptr(), ws.data_ptr(), ws_bytes)
-        elif window is not None:
-            st = L.fa_forward_ragged_window(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(),
-                                            V.data_ptr(), k_lens.data_ptr(), kv_per_len, window, O.data_ptr(),
-                                            l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
-        elif fp8:
-            st = L.fa_forward_ragged_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
-                                         _scale_ptr(k_scale), _scale_ptr(v_scale), k_lens.data_ptr(), kv_per_len,
-                                         int(bool(tail_causal)), O.data_ptr(), l.data_ptr(), m.data_ptr(),
-                                         ws.data_ptr(), ws_bytes)
-        else:
-            st = L.fa_forward_ragged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
-                                     k_lens.data_ptr(), kv_per_len, int(bool(tail_causal)), O.data_ptr(), l.data_ptr(),
-                                     m.data_ptr(), ws.data_ptr(), ws_bytes)
+        st = getattr(L, forward_name)(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
+                                      *_scale_ptrs(fp8, k_scale, v_scale), k_lens.data_ptr(), kv_per_len,
+                                      int(bool(tail_causal)) if window is None else window, O.data_ptr(),
+                                      l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
@@ -984,13 +962,10 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
     window = _decode_window(what, window_size, tail_causal, nq)
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_ch)
     L = _lib.lib()
+    plan_name, ws_name, forward_name = decode_entry_points("paged", _decode_form(prefill, window), fp8)
+    own = (prob, g, page) + (() if window is None else (window,))  # the plan functions' own arguments
     plan = (ctypes.c_int32 * 8)()
-    if prefill:
-        st = L.fa_forward_paged_prefill_plan(prob, g, page, plan)
-    elif window is None:
-        st = L.fa_forward_paged_plan(prob, g, page, plan)
-    else:
-        st = L.fa_forward_paged_window_plan(prob, g, page, window, plan)
+    st = getattr(L, plan_name)(*own, plan)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     if plan[0] == 0:
@@ -1004,48 +979,14 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
     O = torch.empty(batch + (hq, v_ch, nq), dtype=Q.dtype, device=Q.device)
     l = torch.empty(batch + (hq, nq), dtype=torch.float32, device=Q.device)
     m = torch.empty(batch + (hq, nq), dtype=Q.dtype, device=Q.device)
-    if prefill:
-        ws_bytes = int(L.fa_forward_paged_prefill_workspace_bytes(prob, g, page))
-    elif window is None:
-        ws_bytes = int(L.fa_forward_paged_workspace_bytes(prob, g, page))
-    else:
-        ws_bytes = int(L.fa_forward_paged_window_workspace_bytes(prob, g, page, window))
+    ws_bytes = int(getattr(L, ws_name)(*own))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        if prefill:
-            if fp8:
-                st = L.fa_forward_paged_prefill_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
-                                                    V_pool.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
-                                                    block_table.data_ptr(), max_pages, page, num_pages,
-                                                    k_lens.data_ptr(), hk, int(bool(tail_causal)), O.data_ptr(),
-                                                    l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
-            else:
-                st = L.fa_forward_paged_prefill(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
-                                                V_pool.data_ptr(), block_table.data_ptr(), max_pages, page, num_pages,
-                                                k_lens.data_ptr(), hk, int(bool(tail_causal)), O.data_ptr(),
-                                                l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
-        elif window is not None and fp8:
-            st = L.fa_forward_paged_window_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
-                                               V_pool.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
-                                               block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(),
-                                               hk, window, O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(),
-                                               ws_bytes)
-        elif window is not None:
-            st = L.fa_forward_paged_window(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
-                                           V_pool.data_ptr(), block_table.data_ptr(), max_pages, page, num_pages,
-                                           k_lens.data_ptr(), hk, window, O.data_ptr(), l.data_ptr(), m.data_ptr(),
-                                           ws.data_ptr(), ws_bytes)
-        elif fp8:
-            st = L.fa_forward_paged_fp8(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
-                                        V_pool.data_ptr(), _scale_ptr(k_scale), _scale_ptr(v_scale),
-                                        block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(), hk,
-                                        int(bool(tail_causal)), O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(),
-                                        ws_bytes)
-        else:
-            st = L.fa_forward_paged(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
-                                    V_pool.data_ptr(), block_table.data_ptr(), max_pages, page, num_pages,
-                                    k_lens.data_ptr(), hk, int(bool(tail_causal)), O.data_ptr(), l.data_ptr(),
-                                    m.data_ptr(), ws.data_ptr(), ws_bytes)
+        st = getattr(L, forward_name)(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
+                                      V_pool.data_ptr(), *_scale_ptrs(fp8, k_scale, v_scale), block_table.data_ptr(),
+                                      max_pages, page, num_pages, k_lens.data_ptr(), hk,
+                                      int(bool(tail_causal)) if window is None else window, O.data_ptr(),
+                                      l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
