@@ -394,6 +394,64 @@ int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_g
                                  void* O, void* l, void* m,
                                  void* workspace, size_t workspace_bytes);
 
+/* Fused K/V append: the write side of the four caches above.  New tokens' keys and values are stored IN PLACE into a
+ * ragged cache or into page pools, fp16 or FP8, by one kernel launch enqueued on `stream`: a forward enqueued after it
+ * on that stream sees the tokens.  Every control value is device data; the host reads nothing and does not
+ * synchronise, so the call may be captured in a graph and replayed after any of them was overwritten in place.
+ *   K_new [sequences][kv_heads][d][n_new], V_new [sequences][kv_heads][v_d][n_new]: fp16, channel-first.
+ *   k_lens: DEVICE int32 [sequences], the length AFTER the append, the array the attention call of this step takes;
+ *     L = clamp(k_lens[s], 0, nk).
+ *   new_lens: DEVICE int32 [sequences] or null: the real new tokens of sequence s, RIGHT-ALIGNED in the n_new slots
+ *     (the query-blocked forwards' mixed-batch convention: the last slot is the sequence's last position);
+ *     n = min(clamp(new_lens[s], 0, n_new), L), and n = min(n_new, L) for a null array.
+ *   Slot n_new - n + t is stored at key position L - n + t for t in [0, n).  The slots in front are padding: never
+ *     loaded, whatever they hold.
+ *   ragged: K [sequences][kv_heads][d][nk], V [sequences][kv_heads][v_d][nk]; the position is the last index.
+ *   paged:  position pos goes to K_pool[entry][h][c][pos % page], entry = clamp(block_table[s][pos / page], 0,
+ *     num_pages - 1), nk = max_pages * page.  pos < L <= nk keeps pos / page inside the table row, so every store lies
+ *     inside the pools whatever the table holds.  Only the entries of pages that receive a new position are loaded.
+ *   _fp8: the cache holds OCP e4m3fn bytes; the stored byte is the fp32 quotient fp32(x) / scale[h], correctly
+ *     rounded, encoded round-to-nearest-even and saturating at +-448.  k_scale / v_scale: DEVICE fp32 [kv_heads], null
+ *     means 1.0.  For NaN input, or a scale that is not finite and positive, the byte is unspecified (in bounds).
+ *     An fp16 cache stores a bit copy.
+ * Guarantees: every stored byte belongs to a new position; no other byte of the cache is written, not even with its
+ *   old value (partial 8-key chunks are stored element by element).  A page that is not named at a written position
+ *   (a shared prefix) is untouched.  Two sequences that name one page at a written position race: in bounds,
+ *   otherwise unspecified.
+ * The call does NOT allocate pages, change k_lens, new_lens or the table, compute scales, or copy shared pages on
+ *   write.  It takes no workspace and has no plan function.
+ * Envelope: page % 64 == 0 in the paged forms (no other pool can be read here); any d, v_d >= 1.  Outside it, or where
+ *   sequences * kv_heads * ceil((d + v_d) * ((n_new + 14) / 8) / 256) blocks exceed 2^31 - 1: FA_ERR_UNSUPPORTED,
+ *   nothing written.
+ * FA_ERR_INVALID_ARGUMENT with text in fa_last_error(), before any device call: sequences < 0, n_new < 0; kv_heads, d,
+ *   v_d or nk < 1; page < 1, max_pages < 1, max_pages * page != nk, num_pages < 1; and where there is work a null
+ *   K_new, V_new, cache, k_lens or block_table.
+ * sequences == 0 or n_new == 0: FA_OK, nothing launched.  Every n == 0: FA_OK, nothing stored. */
+int fa_append_ragged(void* stream, int64_t sequences,
+                     int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new, int32_t nk,
+                     const void* K_new, const void* V_new,
+                     void* K, void* V,
+                     const int32_t* k_lens, const int32_t* new_lens);
+int fa_append_paged(void* stream, int64_t sequences,
+                    int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new, int32_t nk,
+                    const void* K_new, const void* V_new,
+                    void* K_pool, void* V_pool,
+                    const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                    const int32_t* k_lens, const int32_t* new_lens);
+int fa_append_ragged_fp8(void* stream, int64_t sequences,
+                         int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new, int32_t nk,
+                         const void* K_new, const void* V_new,
+                         void* K8, void* V8,
+                         const float* k_scale, const float* v_scale,
+                         const int32_t* k_lens, const int32_t* new_lens);
+int fa_append_paged_fp8(void* stream, int64_t sequences,
+                        int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new, int32_t nk,
+                        const void* K_new, const void* V_new,
+                        void* K_pool8, void* V_pool8,
+                        const float* k_scale, const float* v_scale,
+                        const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                        const int32_t* k_lens, const int32_t* new_lens);
+
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);

@@ -60,6 +60,10 @@ EXPORTED_SYMBOLS = (
     "fa_forward_paged_prefill",
     "fa_forward_ragged_prefill_fp8",
     "fa_forward_paged_prefill_fp8",
+    "fa_append_ragged",
+    "fa_append_paged",
+    "fa_append_ragged_fp8",
+    "fa_append_paged_fp8",
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_backward_split_plan",
@@ -89,6 +93,13 @@ def decode_entry_points(cache, form, fp8):
         raise ValueError(f"no decode forward over cache {cache!r} in form {form!r}")
     stem = f"fa_forward_{cache}" + ("" if form == "plain" else f"_{form}")
     return stem + "_plan", stem + "_workspace_bytes", stem + ("_fp8" if fp8 else "")
+
+
+def append_entry_point(cache, fp8):
+    """The name of the fused K/V append into ``cache`` (of DECODE_CACHES)."""
+    if cache not in DECODE_CACHES:
+        raise ValueError(f"no append into cache {cache!r}")
+    return f"fa_append_{cache}" + ("_fp8" if fp8 else "")
 
 
 class LibraryNotBuiltError(RuntimeError):
@@ -194,6 +205,17 @@ def _declare(lib):
                                                   + ([vp, i32, i32, i64] if cache == "paged" else [])
                                                   + [vp, i32, i32, vp, vp, vp, vp, ctypes.c_size_t])
                 getattr(lib, forward).restype = ctypes.c_int
+    # The fused K/V appends (include/fa_api.h): the same pieces again, the caches written instead of read; (k_scale,
+    # v_scale) after an FP8 cache, (block_table, max_pages, page, num_pages) after a paged one.  (Absent as above.)
+    for cache in DECODE_CACHES:
+        for fp8 in (False, True):
+            append = append_entry_point(cache, fp8)
+            if not hasattr(lib, append):
+                continue
+            getattr(lib, append).argtypes = ([vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+                                             + ([vp, vp] if fp8 else [])
+                                             + ([vp, i32, i32, i64] if cache == "paged" else []) + [vp, vp])
+            getattr(lib, append).restype = ctypes.c_int
     lib.fa_estimate_forward_flops.argtypes = [P]
     lib.fa_estimate_forward_flops.restype = ctypes.c_double
     lib.fa_allowed_pairs.argtypes = [P]

@@ -1031,6 +1031,88 @@ int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_g
   return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, nullptr, true}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
 }
 
+// ---- the fused K/V append of the same four caches (include/fa_api.h): every check on the host
+// before any device call, then one launch of fa_cache_append.hip's kernel.  No workspace, no plan.
+static int cache_append(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new,
+                        int32_t nk, const void* K_new, const void* V_new, void* K, void* V, const Kv8* kv8,
+                        const PagedPart* pg, const int32_t* k_lens, const int32_t* new_lens) {
+  const std::string name = pg ? "paged append" : "ragged append";
+  if (sequences < 0 || n_new < 0)
+    return set_error(FA_ERR_INVALID_ARGUMENT, name + ": sequences = " + std::to_string(sequences) + " and n_new = " +
+                                                  std::to_string(n_new) + " must not be negative");
+  if (kv_heads < 1 || d < 1 || v_d < 1 || nk < 1)
+    return set_error(FA_ERR_INVALID_ARGUMENT, name + ": kv_heads = " + std::to_string(kv_heads) + ", d = " + std::to_string(d) +
+                                                  ", v_d = " + std::to_string(v_d) + " and nk = " + std::to_string(nk) +
+                                                  " must be >= 1");
+  if (pg) {
+    if (pg->page < 1) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": page must be >= 1");
+    if (pg->max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": max_pages must be >= 1");
+    if ((int64_t)pg->max_pages * pg->page != nk)
+      return set_error(FA_ERR_INVALID_ARGUMENT,
+                       name + ": max_pages * page = " + std::to_string((int64_t)pg->max_pages * pg->page) +
+                           " is not the capacity nk = " + std::to_string(nk));
+    if (pg->num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": num_pages must be >= 1");
+    if (pg->page % kSplitTile != 0)
+      return set_error(FA_ERR_UNSUPPORTED, name + ": outside the envelope (page % 64 == 0), got page = " + std::to_string(pg->page));
+  }
+  if (sequences == 0 || n_new == 0) return FA_OK;
+  if (!K_new || !V_new) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": null K_new or V_new");
+  if (!K || !V) return set_error(FA_ERR_INVALID_ARGUMENT, name + (pg ? ": null K_pool or V_pool" : ": null K or V"));
+  if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": null k_lens");
+  if (pg && !pg->block_table) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": null block_table");
+  // one thread per (channel row, 8-key chunk), 256 to a block, the blocks of a (sequence, head) together: a grid
+  // that holds fewer blocks than that would have to read more of K_new than a device holds, so there is no slab loop
+  const int64_t kMaxBlocks = 0x7fffffff;
+  const int64_t chunks = ((int64_t)n_new + 14) / 8, slice_threads = ((int64_t)d + v_d) * chunks;
+  const int64_t slice_blocks = (slice_threads + 255) / 256;
+  if (slice_threads > kMaxBlocks || sequences > kMaxBlocks || sequences * kv_heads > kMaxBlocks / slice_blocks)
+    return set_error(FA_ERR_UNSUPPORTED, name + ": sequences * kv_heads * ceil((d + v_d) * ((n_new + 14) / 8) / 256) "
+                                                "blocks do not fit one launch of 2^31 - 1 blocks");
+  fa::AppendArgs a = {};
+  a.K_new = K_new; a.V_new = V_new; a.K = K; a.V = V;
+  if (kv8) { a.k_scale = kv8->k_scale; a.v_scale = kv8->v_scale; }
+  if (pg) {
+    a.block_table = pg->block_table; a.max_pages = pg->max_pages; a.page = pg->page;
+    a.last_page = (int32_t)(pg->num_pages - 1 < 0x7fffffff ? pg->num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
+  }
+  a.k_lens = k_lens; a.new_lens = new_lens;
+  a.kv_heads = kv_heads; a.d = d; a.v_d = v_d; a.n_new = n_new; a.nk = nk;
+  a.chunks = (int32_t)chunks; a.slice_blocks = (int32_t)slice_blocks;
+  const hipError_t e = fa::launch_cache_append(pg != nullptr, kv8 != nullptr, a, sequences * kv_heads * slice_blocks,
+                                               static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return set_error((int)e, std::string("Failed to launch the append kernel: ") + hipGetErrorString(e));
+  return FA_OK;
+}
+
+int fa_append_ragged(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new, int32_t nk,
+                     const void* K_new, const void* V_new, void* K, void* V, const int32_t* k_lens,
+                     const int32_t* new_lens) {
+  return cache_append(stream, sequences, kv_heads, d, v_d, n_new, nk, K_new, V_new, K, V, nullptr, nullptr, k_lens, new_lens);
+}
+
+int fa_append_paged(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new, int32_t nk,
+                    const void* K_new, const void* V_new, void* K_pool, void* V_pool, const int32_t* block_table,
+                    int32_t max_pages, int32_t page, int64_t num_pages, const int32_t* k_lens, const int32_t* new_lens) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  return cache_append(stream, sequences, kv_heads, d, v_d, n_new, nk, K_new, V_new, K_pool, V_pool, nullptr, &pg, k_lens, new_lens);
+}
+
+int fa_append_ragged_fp8(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new,
+                         int32_t nk, const void* K_new, const void* V_new, void* K8, void* V8, const float* k_scale,
+                         const float* v_scale, const int32_t* k_lens, const int32_t* new_lens) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return cache_append(stream, sequences, kv_heads, d, v_d, n_new, nk, K_new, V_new, K8, V8, &kv8, nullptr, k_lens, new_lens);
+}
+
+int fa_append_paged_fp8(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new,
+                        int32_t nk, const void* K_new, const void* V_new, void* K_pool8, void* V_pool8,
+                        const float* k_scale, const float* v_scale, const int32_t* block_table, int32_t max_pages,
+                        int32_t page, int64_t num_pages, const int32_t* k_lens, const int32_t* new_lens) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  const Kv8 kv8 = {k_scale, v_scale};
+  return cache_append(stream, sequences, kv_heads, d, v_d, n_new, nk, K_new, V_new, K_pool8, V_pool8, &kv8, &pg, k_lens, new_lens);
+}
+
 size_t fa_backward_workspace_bytes(const fa_problem* p) {
   if (fa_validate(p) != FA_OK) return 0;
   return ws_layout(p).total;
@@ -1307,7 +1389,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
 }
 
 }  // extern "C"

@@ -122,6 +122,25 @@ struct PrefillOf {
   int32_t nqb;  // query blocks: ceil(nq / P), >= 2
 };
 
+// the write side of the four caches (fa_cache_append.hip): new tokens' K and V stored in place.  Sequence s holds
+// L = clamp(k_lens[s], 0, nk) keys AFTER the append, of which the last n = min(clamp(new_lens[s], 0, n_new), L)
+// (new_lens null: min(n_new, L)) are new: slot n_new - n + t of K_new / V_new goes to key position L - n + t.
+struct AppendArgs {
+  const void* K_new;           // [sequences][kv_heads][d][n_new] fp16
+  const void* V_new;           // [sequences][kv_heads][v_d][n_new] fp16
+  void* K;                     // ragged: [sequences][kv_heads][d][nk]; paged: the pool [num_pages][kv_heads][d][page]
+  void* V;                     //   the same over v_d rows; fp16 or e4m3fn bytes
+  const float* k_scale;        // FP8 caches: device, kv_heads values, byte = e4m3fn(fp32(x) / scale[h]); null: 1.0
+  const float* v_scale;
+  const int32_t* block_table;  // paged caches: device [sequences][max_pages], loaded entries clamped to [0, last_page]
+  const int32_t* k_lens;       // device [sequences]
+  const int32_t* new_lens;     // device [sequences], or null
+  int32_t max_pages, page, last_page;
+  int32_t kv_heads, d, v_d, n_new, nk;
+  int32_t chunks;              // 8-key destination chunks a run of n_new positions can touch: (n_new + 14) / 8
+  int32_t slice_blocks;        // 256-thread blocks per (sequence, head): ceil((d + v_d) * chunks / 256)
+};
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;
@@ -228,6 +247,10 @@ template <class Args>
 hipError_t launch_fwd_f16_window(const WindowOf<Args>& wa, hipStream_t s);
 template <class Args>
 hipError_t launch_fwd_f16_prefill(const PrefillOf<Args>& pf, hipStream_t s);
+// The fused K/V append of the same four caches (paged: behind a block table; fp8: e4m3fn bytes with per-head scales):
+// one launch of `blocks` = sequences * kv_heads * a.slice_blocks workgroups, which the caller has checked to fit a
+// grid — fa_cache_append.hip
+hipError_t launch_cache_append(bool paged, bool fp8, const AppendArgs& a, int64_t blocks, hipStream_t s);
 bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);

@@ -65,6 +65,7 @@ __all__ = [
     "Part", "combined_1d", "combined_2d", "merge_partials",
     "grouped_1d", "grouped_2d", "attention_forward_grouped",
     "ragged_1d", "paged_1d", "ragged_prefill_1d", "paged_prefill_1d", "quantize_kv_fp8",
+    "ragged_append_1d", "paged_append_1d",
 ]
 
 
@@ -662,7 +663,9 @@ def quantize_kv_fp8(x, head_axis, scale=None):
     with ``x ~= scale[h] * x8`` along ``head_axis``.  Without ``scale`` it is the head's ``amax / 448`` over all
     other axes (1.0 for a head of zeros); a given ``scale`` is a float32 tensor of shape ``(Hk,)``.  ``x / scale`` is
     clamped to +-448 before the cast, because the cast itself turns what lies beyond the format's range into NaN.
-    Plain torch, on the device of ``x``: appends are a few tokens per step, so this is not a kernel."""
+    Plain torch, on the device of ``x``: appends are a few tokens per step, so this is not a kernel.  The fused
+    appends ``ragged_append_1d`` / ``paged_append_1d`` store the same bytes for given scales, in the cache's own
+    kernel."""
     if getattr(torch, "float8_e4m3fn", None) is None:
         raise NotImplementedError("this torch has no float8_e4m3fn")
     head_axis = head_axis % x.dim()
@@ -681,15 +684,15 @@ def quantize_kv_fp8(x, head_axis, scale=None):
     return x8, scale
 
 
-def _kv_cache_scales(what, Q, K, V, hk, k_scale, v_scale):
+def _kv_cache_scales(what, Q, K, V, hk, k_scale, v_scale, q="Q"):
     """Whether K and V are an FP8 cache, after the checks of their dtypes and of the scales (fp32 device tensors of
-    shape ``(Hk,)``, or None for 1.0)."""
+    shape ``(Hk,)``, or None for 1.0).  ``q`` names the float16 tensor ``Q`` in the messages (an append has no Q)."""
     fp8 = K.dtype in _FP8_CACHE_DTYPES
     if fp8:
         if V.dtype not in _FP8_CACHE_DTYPES:
-            raise TypeError(f"{what} must both be an FP8 cache (float8_e4m3fn or uint8) or both share the dtype of Q")
+            raise TypeError(f"{what} must both be an FP8 cache (float8_e4m3fn or uint8) or both share the dtype of {q}")
     elif K.dtype != Q.dtype or V.dtype != Q.dtype:
-        raise TypeError(f"Q, {what} must share one dtype")
+        raise TypeError(f"{q}, {what} must share one dtype")
     for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
         if t is None:
             continue
@@ -702,7 +705,7 @@ def _kv_cache_scales(what, Q, K, V, hk, k_scale, v_scale):
             raise InvalidArgumentError(f"The shape of {name} should be (Hk,) = " + _shape_str((hk,)) + f", but {name}_shape = "
                                        + _shape_str(t.shape) + " was received")
         if t.device != Q.device:
-            raise InvalidArgumentError(f"{name} must be on the device of Q")
+            raise InvalidArgumentError(f"{name} must be on the device of {q}")
         if not t.is_contiguous():  # (the kernels read the caller's own array on every replay, not a copy)
             raise InvalidArgumentError(f"{name} must be contiguous")
     return fp8
@@ -867,6 +870,8 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
         new8, _ = quantize_kv_fp8(new, head_axis=0, scale=k_scale)
         K_pool[block_table[s, pos // page], :, :, pos % page] = new8
 
+    ``paged_append_1d`` is both recipes as one kernel, for K and V of a whole batch and any number of new tokens.
+
     A sliding window: ``window_size`` = W >= 1 (None: no window), with ``ragged_1d``'s rule: Nq > 1 requires
     ``tail_causal=True``, and query i at position ``pos = k_lens[s] - Nq + i`` sees the W keys
     ``max(0, pos - W + 1) <= j <= pos``.  Work, workspace and time follow W + Nq - 1, not the capacity; ``W >= cap``
@@ -897,7 +902,8 @@ def paged_prefill_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, 
     unbounded and 1 <= g <= 128.  The queries are worked in blocks of P = the largest power of two with
     g * P <= 128; where one block holds them all the call is ``paged_1d`` itself, bit for bit.  There is no
     ``window_size``.  The new tokens' keys are appended to the pools first (``paged_1d`` shows how), so that
-    ``k_lens`` counts them.
+    ``k_lens`` counts them; ``paged_append_1d`` does it in one call, with this function's ``k_lens`` and the real
+    tokens right-aligned as the queries are.
 
     A batch that mixes prefill with decode right-aligns each sequence's real queries in the Nq slots (with
     ``tail_causal`` the last slot is the sequence's last position).  The padding queries in front compute earlier
@@ -990,6 +996,143 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
+
+
+# ----------------------------------------------------------------------------
+# Fused K/V append: the write side of the ragged and the paged cache, fp16 or FP8
+# (include/fa_api.h, "Fused K/V append")
+# ----------------------------------------------------------------------------
+def ragged_append_1d(K, V, K_new, V_new, k_lens, new_lens=None, k_scale=None, v_scale=None):
+    """Appends new tokens' keys and values to the padded cache of ``ragged_1d``, in place, with one kernel: K
+    ``batch + (Hk, C, cap)``, V ``batch + (Hk, Cv, cap)``, float16 or an FP8 cache (``float8_e4m3fn`` or ``uint8``);
+    ``K_new`` ``batch + (Hk, C, Nnew)`` and ``V_new`` ``batch + (Hk, Cv, Nnew)`` float16 (made contiguous if they are
+    not); ``k_lens`` and ``new_lens`` int32 tensors of shape ``batch`` on the cache's device.
+
+    ``k_lens[s]`` is the length AFTER the append, clamped to [0, cap]: the tensor this step's attention call takes.
+    ``new_lens[s]`` (None: Nnew for every sequence) is the number of real new tokens of sequence s, clamped to
+    [0, min(Nnew, k_lens[s])] and RIGHT-ALIGNED in the Nnew slots, as the queries of ``ragged_prefill_1d`` are: the
+    last n slots go to positions ``k_lens[s] - n .. k_lens[s] - 1``.  The slots in front are padding and are never
+    read.  Only those positions are written; nothing else in the cache changes.
+
+    An FP8 cache stores ``e4m3fn(float32(x) / scale[h])``, rounded to nearest even and saturated at +-448: for every
+    finite or infinite x the bytes of ``quantize_kv_fp8(x, scale=...)``.  ``k_scale`` / ``v_scale`` are float32 tensors
+    of shape ``(Hk,)`` on the device, or None for 1.0; a float16 cache takes no scale.
+
+    Nothing is read on the host: no synchronisation, and a captured graph may be replayed after any of the tensors
+    was overwritten in place.  The call runs on the current stream, so a forward called after it sees the tokens.  It
+    does not change ``k_lens`` or ``new_lens`` and computes no scales.  The cache must be contiguous (a copy would
+    silently take the write).  Inference only.  Returns None."""
+    if len(K.shape) < 3 or len(V.shape) != len(K.shape):
+        raise InvalidArgumentError("K and V should be batch + (Hk, channels, cap), but K_shape = " + _shape_str(K.shape)
+                                   + ", V_shape = " + _shape_str(V.shape) + " were received")
+    batch, hk, k_ch, cap = tuple(K.shape[:-3]), int(K.shape[-3]), int(K.shape[-2]), int(K.shape[-1])
+    if tuple(V.shape[:-2]) != batch + (hk,) or int(V.shape[-1]) != cap:
+        raise InvalidArgumentError("K and V should agree in the batch shape, Hk and cap, but K_shape = "
+                                   + _shape_str(K.shape) + ", V_shape = " + _shape_str(V.shape) + " were received")
+    v_ch = int(V.shape[-2])
+    n_new = _append_checks("ragged_append_1d", "K and V", K, V, K_new, V_new, batch, hk, k_ch, v_ch, (("k_lens", k_lens),),
+                           new_lens, k_scale, v_scale)
+    if cap > 2 ** 30:
+        raise InvalidArgumentError("The capacity " + str(cap) + " is above 2^30 keys")
+    _append_call("ragged", K, V, K_new, V_new, batch, hk, k_ch, v_ch, n_new, cap, (), k_lens, new_lens, k_scale, v_scale)
+
+
+def paged_append_1d(K_pool, V_pool, K_new, V_new, block_table, k_lens, new_lens=None, k_scale=None, v_scale=None):
+    """``ragged_append_1d`` into the page pools of ``paged_1d``: ``K_pool`` ``[num_pages, Hk, C, page]``, ``V_pool``
+    ``[num_pages, Hk, Cv, page]``, float16 or FP8; ``K_new`` ``batch + (Hk, C, Nnew)``, ``V_new``
+    ``batch + (Hk, Cv, Nnew)`` float16; ``block_table`` int32 ``batch + (max_pages,)``; ``k_lens`` (the lengths AFTER
+    the append, clamped to ``[0, max_pages * page]``) and ``new_lens`` int32 of shape ``batch``.  Position ``pos`` of
+    sequence s goes to ``K_pool[block_table[s, pos // page], :, :, pos % page]``: the docstring recipe of ``paged_1d``
+    for a whole batch, any number of tokens and pages, and the FP8 quantization, in one kernel.
+
+    Only the table entries of pages that receive a new position are loaded, each clamped to ``[0, num_pages - 1]``:
+    every store lies inside the pools.  A page that no written position names (a shared prefix) is untouched; two
+    sequences that name one page at a written position race, which is the caller's bug.  The call allocates no
+    pages, changes neither the table nor the lengths, computes no scales and does no copy-on-write.
+
+    Lengths, ``new_lens``, scales, FP8 rounding, graph replay, the stream and the contiguous pools: as in
+    ``ragged_append_1d``.  The page size must be a multiple of 64 (NotImplementedError otherwise: nothing here can
+    read such a pool).  Inference only.  Returns None."""
+    if len(K_pool.shape) != 4 or len(V_pool.shape) != 4:
+        raise InvalidArgumentError("K_pool and V_pool should be [num_pages, Hk, channels, page], but K_pool_shape = "
+                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
+                                   + " were received")
+    num_pages, hk, k_ch, page = (int(x) for x in K_pool.shape)
+    if (int(V_pool.shape[0]), int(V_pool.shape[1]), int(V_pool.shape[3])) != (num_pages, hk, page):
+        raise InvalidArgumentError("K_pool and V_pool should agree in num_pages, Hk and page, but K_pool_shape = "
+                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
+                                   + " were received")
+    v_ch = int(V_pool.shape[2])
+    if num_pages < 1:
+        raise InvalidArgumentError("The pools should hold a page, but K_pool_shape = " + _shape_str(K_pool.shape)
+                                   + " was received")
+    batch = tuple(K_new.shape[:-3]) if len(getattr(K_new, "shape", ())) >= 3 else ()
+    n_new = _append_checks("paged_append_1d", "K_pool and V_pool", K_pool, V_pool, K_new, V_new, batch, hk, k_ch, v_ch,
+                           (("block_table", block_table), ("k_lens", k_lens)), new_lens, k_scale, v_scale)
+    if page < 1 or page % 64 != 0:
+        raise NotImplementedError("paged_append_1d: " + _PAGE_CONDITION + ", got page = " + str(page))
+    max_pages = int(block_table.shape[-1])
+    cap = max_pages * page
+    if cap > 2 ** 30:
+        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    _append_call("paged", K_pool, V_pool, K_new, V_new, batch, hk, k_ch, v_ch, n_new, cap,
+                 (block_table, max_pages, page, num_pages), k_lens, new_lens, k_scale, v_scale)
+
+
+def _append_checks(what, caches, K, V, K_new, V_new, batch, hk, k_ch, v_ch, int_tensors, new_lens, k_scale, v_scale):
+    """The checks that ``ragged_append_1d`` and ``paged_append_1d`` share, after those of the cache's own shape and
+    before the page size's: the new tokens, the dtypes and scales, the int32 tensors, grad mode, the contiguous
+    cache.  Returns Nnew."""
+    for name, t in (("K_new", K_new), ("V_new", V_new)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float16:
+            raise TypeError(f"{name} must be a float16 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    n_new = int(K_new.shape[-1]) if len(K_new.shape) >= 1 else 0
+    if tuple(K_new.shape) != batch + (hk, k_ch, n_new) or tuple(V_new.shape) != batch + (hk, v_ch, n_new):
+        raise InvalidArgumentError("K_new and V_new should be batch + (Hk, C, Nnew) and batch + (Hk, Cv, Nnew) with "
+                                   "batch_shape = " + _shape_str(batch) + ", Hk = " + str(hk) + ", C = " + str(k_ch)
+                                   + ", Cv = " + str(v_ch) + ", but K_new_shape = " + _shape_str(K_new.shape)
+                                   + ", V_new_shape = " + _shape_str(V_new.shape) + " were received")
+    _kv_cache_scales(caches, K_new, K, V, hk, k_scale, v_scale, q="K_new and V_new")
+    int_tensors = int_tensors + ((("new_lens", new_lens),) if new_lens is not None else ())
+    for name, t in int_tensors:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    for name, t in int_tensors:
+        if name == "block_table":
+            if tuple(t.shape[:-1]) != batch or len(t.shape) != len(batch) + 1 or t.shape[-1] < 1:
+                raise InvalidArgumentError("The shape of block_table should be the batch shape without the heads plus "
+                                           "(max_pages,), but block_table_shape = " + _shape_str(t.shape)
+                                           + ", batch_shape = " + _shape_str(batch) + " were received")
+        elif tuple(t.shape) != batch:
+            raise InvalidArgumentError(f"The shape of {name} should be the batch shape without the heads, but {name}_shape = "
+                                       + _shape_str(t.shape) + ", batch_shape = " + _shape_str(batch) + " were received")
+    if any(t.device != K.device for t in (V, K_new, V_new)) or any(t.device != K.device for _, t in int_tensors):
+        raise InvalidArgumentError(", ".join(n for n, _ in int_tensors) + f", K_new and V_new must be on the device of {caches}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (K, V, K_new, V_new)):
+        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
+                           "detach its inputs")
+    if not K.is_contiguous() or not V.is_contiguous():
+        raise InvalidArgumentError(f"{what}: {caches} must be contiguous: the append writes in place, and a contiguous "
+                                   "copy would silently take the write")
+    return n_new
+
+
+def _append_call(cache, K, V, K_new, V_new, batch, hk, k_ch, v_ch, n_new, cap, paged_args, k_lens, new_lens, k_scale,
+                 v_scale):
+    """The device check (last, as in the forwards) and the C call of an append."""
+    _check_device_tensors(K, V, K_new, V_new)
+    fp8 = K.dtype in _FP8_CACHE_DTYPES
+    K_new, V_new, k_lens = K_new.contiguous(), V_new.contiguous(), k_lens.contiguous()
+    new_lens = new_lens.contiguous() if new_lens is not None else None
+    if paged_args:
+        paged_args = (paged_args[0].contiguous().data_ptr(),) + tuple(paged_args[1:])
+    with torch.cuda.device(K.device):
+        st = getattr(_lib.lib(), _lib.append_entry_point(cache, fp8))(
+            _stream_handle(K.device), _prod(batch), hk, k_ch, v_ch, n_new, cap, K_new.data_ptr(), V_new.data_ptr(),
+            K.data_ptr(), V.data_ptr(), *_scale_ptrs(fp8, k_scale, v_scale), *paged_args, k_lens.data_ptr(),
+            new_lens.data_ptr() if new_lens is not None else None)
+    if st != _lib.FA_OK:
+        _raise_status(st, "append")
 
 
 # ----------------------------------------------------------------------------
