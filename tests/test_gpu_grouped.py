@@ -328,3 +328,66 @@ def test_python_wrapper_takes_the_fused_path():
     got = fa.grouped_1d(Q, K, V, returning_l_m=True)
     torch.cuda.synchronize()
     assert _same(direct, got)
+
+
+@pytest.mark.parametrize("dtype,seq,policy,mode,g,batch,hk,qs,ks,d,vd,ws,fused", [
+    (np.float16, 1, "full", "none_front", 4, (), 2, (8,), (700,), 64, 40, 1, True),
+    (np.float16, 2, "local", "scale_end", 2, (), 2, (12, 11), (12, 11), 64, 64, 3, False),
+    (np.float16, 1, "causal", "scale_end", 8, (), 1, (40,), (300,), 96, 96, 1, False),
+    (np.float32, 1, "causal", "scale_front", 2, (2,), 3, (50,), (70,), 32, 24, 1, False),
+], ids=["fused-d64-v40", "expanded-2d-local", "mqa-g8", "batch-2x3g"])
+def test_gradients_more_shapes(dtype, seq, policy, mode, g, batch, hk, qs, ks, d, vd, ws, fused):
+    """d != v_d inside the fused envelope, a 2d window, one K/V head under eight query heads, and Q [2, 3 g] over K / V
+    [2, 3]: dQ, dK and dV against tests/union_ref.py's grouped reference (np.repeat, dK / dV folded in float64, the
+    root-sum-square of the members' scales) under gate.grad_ok."""
+    from tests import union_ref
+    assert (_plan(policy, mode, qs, ks, d, vd, g, ws, 0, False, DT[dtype])[0] > 0) == fused
+    rng = np.random.default_rng(d + vd + g)
+    Q, dO = _uniform(rng, dtype, *batch, hk * g, d, *qs), _uniform(rng, dtype, *batch, hk * g, vd, *qs)
+    K, V = _uniform(rng, dtype, *batch, hk, d, *ks), _uniform(rng, dtype, *batch, hk, vd, *ks)
+    dev = torch.device("cuda:0")
+    tq, tk, tv = (torch.from_numpy(x).to(dev).requires_grad_(True) for x in (Q, K, V))
+    o = (fa.grouped_1d if seq == 1 else fa.grouped_2d)(tq, tk, tv, policy, mode, ws, 0, False)
+    o.backward(torch.from_numpy(dO).to(dev))
+    torch.cuda.synchronize()
+    assert tq.grad.shape == tq.shape and tk.grad.shape == tk.shape and tv.grad.shape == tv.shape
+    lead = len(batch) + 1
+    flat = lambda x: x.reshape((int(np.prod(x.shape[:lead])), x.shape[lead], -1))  # noqa: E731
+    prob = O.Problem(policy, seq, mode, ws, 0, False)
+    ref = union_ref.grouped(flat(Q), flat(K), flat(V), flat(dO), O.problem_mask(prob, qs, ks), g, *U_ROUND[dtype])
+    og = flat(o.detach().cpu().numpy()).astype(np.float64)
+    rtol, atol = gate.TOL[dtype]["fwd"]
+    assert (np.abs(og - ref["O"]) <= gate.plain_bound(ref["O"], rtol, atol)).all()
+    for name, got, r, e in (("dQ", tq.grad, ref["dQ"], ref["eQ"]), ("dK", tk.grad, ref["dK"], ref["eK"]),
+                            ("dV", tv.grad, ref["dV"], ref["eV"])):
+        got = flat(got.cpu().numpy()).astype(np.float64)
+        worst = float((np.abs(got - r) / gate.grad_bound(r, e, dtype)).max())
+        print(f"{name}: max err / bound {worst:.3f}, slope {gate.scale_slope(got, r):.3e}")
+        assert gate.grad_ok(got, r, e, dtype, d, got.shape[1]), f"{name}: max err / bound {worst:.3f}"
+
+
+@pytest.mark.parametrize("nq,fused", [(8, True), (200, False)])
+def test_non_contiguous_inputs(nq, fused):
+    """Q, K and V as strided views holding the same values: forward and gradients are bit for bit the contiguous
+    call's, on the fused path and on expanded K / V."""
+    g, nk, d = 4, 300, 64
+    assert (_plan("causal", "scale_end", (nq,), (nk,), d, d, g)[0] > 0) == fused
+    rng = np.random.default_rng(nq)
+    Q, dO, K, V = (_uniform(rng, np.float16, *s) for s in ((2 * g, d, nq), (2 * g, d, nq), (2, d, nk), (2, d, nk)))
+    dev = torch.device("cuda:0")
+
+    def strided(x):
+        buf = torch.zeros(x.shape[:-1] + (2 * x.shape[-1],), dtype=torch.float16, device=dev)
+        buf[..., ::2] = torch.from_numpy(x).to(dev)
+        view = buf[..., ::2]
+        assert not view.is_contiguous()
+        return view
+
+    outs = []
+    for wrap in (lambda x: torch.from_numpy(x).to(dev), strided):
+        tq, tk, tv = (wrap(x).requires_grad_(True) for x in (Q, K, V))
+        res = fa.grouped_1d(tq, tk, tv, "causal", "scale_end", returning_l_m=True)
+        res[0].backward(wrap(dO))
+        torch.cuda.synchronize()
+        outs.append([t.detach() for t in res] + [tq.grad, tk.grad, tv.grad])
+    assert all(a.shape == b.shape for a, b in zip(*outs)) and _same(*outs)

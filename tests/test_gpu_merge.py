@@ -384,30 +384,56 @@ def check_l_m(name, l, m):
     """run_case's checks of l and m (tests/test_gpu_parity.py), against the union's L and M."""
     dtype, _, _, d, _, _ = CASES[name]
     c = case_data(name)
-    b, nq, ha = c["b"], c["nq"], c["ha"]
+    check_l_m_values(dtype, d, c["Q"].reshape(c["b"], d, c["nq"]), c["kcat"], c["mask"], c["ha"], c["L"], c["M"], l, m)
+
+
+def check_l_m_values(dtype, d, Q, kcat, mask, ha, L, M, l, m, offset_scores=False):
+    """check_l_m on explicit values (tests/test_gpu_union_fuzz.py shares it): Q [b, d, nq], the concatenated keys
+    kcat [b, d, nk], the union's mask [nq, nk], its non-empty rows ha and float64 L, M [b, nq] against the stored
+    l and m.  Returns the worst error / tolerance of m and of l.
+
+    offset_scores (the sweep's inputs only; check_l_m never sets it): fp16 scores that carry an offset of up to 12
+    in one channel.  The rounding of the pre-scaled Q that m's tolerance allows every score, (2^-11 + d 2^-24) of
+    sum_c |q_c k_c| / sqrt(d), is then coherent over a part's keys (one product carries it) and smaller than the step
+    of the stored m: l, the sum of exp(s - stored m), moves by that factor while the stored m stays where it
+    is, so l gets exp(that term) - 1 relative beside its own tolerance.  Sweep seed 4 (fp16, d = 64, a 16-key part
+    12 above the others): fp16(2 log2(e) / 8) is 2.1e-4 low, every score of that part 2.5e-3 low, and l 0.25 % low in
+    every row, 1.32 x its un-extended tolerance at the worst one (22 of the sweep's 240 default cases exceed it, all
+    fp16 with an offset of 6 or 12, the worst 2.47 x at seed 21); U(-2, 2) inputs keep the same effect at 6e-4."""
+    b, _, nq = Q.shape
     rtol, atol = TOL[dtype]["fwd"]
     lg = l.reshape(b, nq).astype(np.float64)
     mg = m.reshape(b, nq)
-    M64, L64 = c["M"][:, ha], c["L"][:, ha]
-    m_f = mg[:, ha].astype(np.float64)
-    ulp = np.abs(np.spacing(np.abs(M64).astype(dtype))).astype(np.float64)
-    eps = float(np.finfo(dtype).eps)
-    Qf = c["Q"].reshape(b, d, nq).astype(np.float64)
-    if dtype == np.float16:
-        rowdot = gate.max_abs_dot(Qf, c["kcat"], c["mask"])[:, ha] / math.sqrt(d)
-        m_tol = 2 * ulp + np.maximum(1e-3 * np.maximum(np.abs(M64), 1.0),
-                                     (2.0 ** -11 + d * 2.0 ** -24) * rowdot + 4.9e-4)
-    else:
-        dot_bound = np.abs(Qf).sum(axis=1)[:, ha] * max(float(np.abs(c["kcat"]).max()), 1e-30) / math.sqrt(d)
-        m_tol = 2 * ulp + 1e-6 * np.abs(M64) + np.maximum(1e-6 if dtype != np.float64 else 1e-12, 2 * eps * dot_bound)
-    assert (np.abs(m_f - M64) <= m_tol).all(), f"m: max err {np.abs(m_f - M64).max():.3e}"
-    l_ref = L64 * np.exp(M64 - m_f)    # relative to the stored m
-    l_rtol = max(rtol, 1e-6 if dtype == np.float16 else rtol)
-    scale = max(float(np.abs(l_ref).max()), 1.0)
-    assert (np.abs(lg[:, ha] - l_ref) <= atol * scale + l_rtol * np.abs(l_ref)).all(), "l"
+    worst = dict(m=0.0, l=0.0, l_plain=0.0)
+    if ha.any():
+        M64, L64 = M[:, ha], L[:, ha]
+        m_f = mg[:, ha].astype(np.float64)
+        ulp = np.abs(np.spacing(np.abs(M64).astype(dtype))).astype(np.float64)
+        eps = float(np.finfo(dtype).eps)
+        Qf = Q.astype(np.float64)
+        if dtype == np.float16:
+            rowdot = gate.max_abs_dot(Qf, kcat, mask)[:, ha] / math.sqrt(d)
+            m_tol = 2 * ulp + np.maximum(1e-3 * np.maximum(np.abs(M64), 1.0),
+                                         (2.0 ** -11 + d * 2.0 ** -24) * rowdot + 4.9e-4)
+            score_rounding = (2.0 ** -11 + d * 2.0 ** -24) * rowdot
+        else:
+            dot_bound = np.abs(Qf).sum(axis=1)[:, ha] * max(float(np.abs(kcat).max()), 1e-30) / math.sqrt(d)
+            m_tol = 2 * ulp + 1e-6 * np.abs(M64) + np.maximum(1e-6 if dtype != np.float64 else 1e-12, 2 * eps * dot_bound)
+        assert np.isfinite(m_f).all() and np.isfinite(lg[:, ha]).all(), "l or m is not finite"
+        assert (np.abs(m_f - M64) <= m_tol).all(), f"m: max err {np.abs(m_f - M64).max():.3e}"
+        l_ref = L64 * np.exp(M64 - m_f)    # relative to the stored m
+        l_rtol = max(rtol, 1e-6 if dtype == np.float16 else rtol)
+        scale = max(float(np.abs(l_ref).max()), 1.0)
+        l_tol = atol * scale + l_rtol * np.abs(l_ref)
+        l_plain = float((np.abs(lg[:, ha] - l_ref) / l_tol).max())
+        if offset_scores and dtype == np.float16:
+            l_tol = l_tol + np.expm1(score_rounding) * np.abs(l_ref)
+        assert (np.abs(lg[:, ha] - l_ref) <= l_tol).all(), f"l: max err / tolerance {float((np.abs(lg[:, ha] - l_ref) / l_tol).max()):.3f}"
+        worst = dict(m=float((np.abs(m_f - M64) / m_tol).max()), l=float((np.abs(lg[:, ha] - l_ref) / l_tol).max()), l_plain=l_plain)
     if (~ha).any():
         assert (lg[:, ~ha] == 0).all()
         assert mg[:, ~ha].tobytes() == b"\xfa" * (mg[:, ~ha].size * np.dtype(dtype).itemsize)
+    return worst
 
 
 def run_combined(name):
@@ -540,3 +566,143 @@ def test_user_composition_drops_the_normaliser_gradient():
     r = ratio(tks[1].grad.cpu().numpy().reshape(c["dKs"][1].shape), c["dKs"][1], gb["dKs"][1])
     print(f"combine_gate user_composition dK1={r:.3f}")
     assert r > 1.0, r
+
+
+# ------------------------------------------------------------------------------------------------
+# a part far above or below the others: the dominance ladder (the inputs and the gate of the sweep,
+# tests/test_gpu_union_fuzz.py, on fixed cases)
+# ------------------------------------------------------------------------------------------------
+def _part(policy, ks, delta=0, mode="none_front", ws=1, ls=0, causal=False):
+    return dict(policy=policy, ks=tuple(ks), delta=delta, mode=mode, ws=ws, ls=ls, causal=causal)
+
+
+LADDER = {
+    # name: (dtype, d, v_d, queries, the part that stays at 0, the part that carries the offset)
+    "window_global_f16": (np.float16, 64, 64, 200, _part("local", (200,), ws=33), _part("full", (8,))),
+    "window_global_f32": (np.float32, 64, 64, 200, _part("local", (200,), ws=33), _part("full", (8,))),
+    "causal_sinks_d160_f16": (np.float16, 160, 160, 130, _part("causal", (130,)), _part("full", (4,))),
+    "causal_sinks_d288_f16": (np.float16, 288, 288, 40, _part("causal", (40,)), _part("full", (4,))),
+}
+
+
+def ladder_case(name, delta):
+    """The case in the sweep's form: its inputs are test_gpu_union_fuzz.build's (channel 0 of Q is 2, of the offset
+    part's K delta * sqrt(d) / 2), its gate test_gpu_union_fuzz.check."""
+    dtype, d, v_d, nq, base, lifted = LADDER[name]
+    return dict(kind="combined", dtype=dtype, seq=1, misalign=False, seed=10_000 + sorted(LADDER).index(name), split="",
+                batch=(2,), g=1, hk=1, d=d, vd=v_d, qs=(nq,), parts=[dict(base), dict(lifted, delta=delta)])
+
+
+@pytest.mark.parametrize("delta", [-12, -6, -3, 3, 6, 12])
+@pytest.mark.parametrize("name", sorted(LADDER))
+def test_combined_dominance_ladder(name, delta):
+    """One part's scores lifted or lowered by delta against the other's: at -12 its backward gets a merged m far
+    above its own scores and its P sits in fp16's subnormal range; at +12 it carries nearly the whole mass and the
+    other part's does.  Every gradient under the gate with tests/union_ref.py's scales.  At +-3 the same case with
+    every part's gradients taken from its own (l_i, m_i) (mutation a of tests/test_union_fuzz_draws.py, computed in
+    float64 on the CPU) must fail that gate: the ladder binds."""
+    from tests import test_gpu_union_fuzz as F
+    c = ladder_case(name, delta)
+    p = F.build(c)
+    ref = F.reference(c, p)
+    res = F.check(c, ref, F._call(c, p))
+    print(f"combine_ladder {name} {delta:+d} " + " ".join(f"{k}={v:.3g}" for k, v in res.items()))
+    if abs(delta) == 3:
+        from tests import test_union_fuzz_draws as UD
+        assert UD.applies(c, "a")
+        with pytest.raises(AssertionError):
+            F.check(c, ref, UD.mutated(c, p, ref, "a"))
+
+
+# ------------------------------------------------------------------------------------------------
+# autograd plumbing of combined_1d
+# ------------------------------------------------------------------------------------------------
+PLUMBING = [Spec("full", (100,)), Spec("causal", (64,), "scale_end"), Spec("local", (37,), "scale_front", window_size=5)]
+
+
+def _plumbing_inputs(dtype=np.float16, d=64, v_d=40, nq=77):
+    rng = np.random.default_rng(77)
+    u = lambda *s: rng.uniform(-2, 2, s).astype(dtype)  # noqa: E731
+    return u(2, d, nq), [u(2, d, *s.ks) for s in PLUMBING], [u(2, v_d, *s.ks) for s in PLUMBING], u(2, v_d, nq)
+
+
+def _combined_grads(Q, Ks, Vs, dO, want, wrap=lambda x: _to_dev(x)):
+    """combined_1d over PLUMBING with requires_grad on the tensors named in ``want`` ("Q", "K1", "V2", ...);
+    returns (O, l, m, {name: gradient or None}) as bytes-comparable numpy."""
+    leaves = {"Q": wrap(Q), **{f"K{j}": wrap(x) for j, x in enumerate(Ks)}, **{f"V{j}": wrap(x) for j, x in enumerate(Vs)}}
+    for k in want:
+        leaves[k].requires_grad_(True)
+    parts = [fa.Part(s.policy, leaves[f"K{j}"], leaves[f"V{j}"], s.sync_mode, s.ws, s.ls, s.causal) for j, s in enumerate(PLUMBING)]
+    o, l, m = fa.combined_1d(leaves["Q"], parts, returning_l_m=True)
+    if want:
+        o.backward(_to_dev(dO))
+    torch.cuda.synchronize()
+    grads = {k: (None if t.grad is None else t.grad.cpu().numpy()) for k, t in leaves.items()}
+    return o.detach().cpu().numpy(), l.cpu().numpy(), m.cpu().numpy(), grads
+
+
+ALL_LEAVES = ("Q", "K0", "V0", "K1", "V1", "K2", "V2")
+
+
+@pytest.mark.parametrize("want", [("Q",), ("K1",), ("V2",), ALL_LEAVES[1:]], ids=["Q", "K1", "V2", "all_but_Q"])
+def test_combined_gradient_subsets(want):
+    """_CombinedFn.backward runs or skips a part by needs_input_grad: whatever is asked for is bit for bit the
+    gradient of the run that asks for everything, and nothing else comes back."""
+    inputs = _plumbing_inputs()
+    full = _combined_grads(*inputs, ALL_LEAVES)
+    assert all(full[3][k] is not None and np.abs(full[3][k].astype(np.float64)).max() > 0 for k in ALL_LEAVES)
+    sub = _combined_grads(*inputs, want)
+    for a, b_ in zip(full[:3], sub[:3]):
+        assert a.tobytes() == b_.tobytes()
+    for k in ALL_LEAVES:
+        if k in want:
+            assert sub[3][k] is not None and sub[3][k].tobytes() == full[3][k].tobytes(), k
+        else:
+            assert sub[3][k] is None, k
+
+
+def _strided(x):
+    """x's values as a non-contiguous device view: every second element of a buffer twice as long in the last axis"""
+    buf = torch.zeros(x.shape[:-1] + (2 * x.shape[-1],), dtype=torch.from_numpy(x).dtype, device=_dev())
+    buf[..., ::2] = torch.from_numpy(x).to(_dev())
+    view = buf[..., ::2]
+    assert not view.is_contiguous() or view.numel() <= 1
+    return view
+
+
+def test_combined_non_contiguous_inputs():
+    """Q, every K and every V as strided views: forward and gradients are bit for bit those of the contiguous call."""
+    inputs = _plumbing_inputs()
+    ref = _combined_grads(*inputs, ALL_LEAVES)
+    got = _combined_grads(*inputs, ALL_LEAVES, wrap=_strided)
+    for a, b_ in zip(ref[:3], got[:3]):
+        assert a.tobytes() == b_.tobytes()
+    for k in ALL_LEAVES:
+        assert got[3][k].shape == ref[3][k].shape and got[3][k].tobytes() == ref[3][k].tobytes(), k
+
+
+@pytest.mark.parametrize("policy", ["full", "causal", "local"])
+@pytest.mark.parametrize("dtype", [np.float16, np.float32], ids=_id)
+def test_combined_of_one_part_is_the_plain_wrapper(dtype, policy):
+    """One part: the merge hands (O, l, m) back bit for bit, fa_accumulate_parts is skipped, and the backward gets the
+    statistics its own forward produced: everything equals full_1d / causal_1d / local_1d bitwise."""
+    rng = np.random.default_rng(5)
+    u = lambda *s: rng.uniform(-2, 2, s).astype(dtype)  # noqa: E731
+    Q, K, V, dO = u(2, 48, 150), u(2, 48, 90), u(2, 40, 90), u(2, 40, 150)
+    outs = []
+    for combined in (True, False):
+        tq, tk, tv = (_to_dev(x).requires_grad_(True) for x in (Q, K, V))
+        if combined:
+            rule = (9, 1, True) if policy == "local" else ()
+            res = fa.combined_1d(tq, [fa.Part(policy, tk, tv, "scale_end", *rule)], returning_l_m=True)
+        elif policy == "full":
+            res = fa.full_1d(tq, tk, tv, "scale_end", returning_l_m=True)
+        elif policy == "causal":
+            res = fa.causal_1d(tq, tk, tv, "scale_end", returning_l_m=True)
+        else:
+            res = fa.local_1d(tq, tk, tv, 9, 1, True, "scale_end", returning_l_m=True)
+        res[0].backward(_to_dev(dO))
+        torch.cuda.synchronize()
+        outs.append([t.detach().cpu().numpy() for t in res] + [t.grad.cpu().numpy() for t in (tq, tk, tv)])
+    for name, a, b_ in zip(("O", "l", "m", "dQ", "dK", "dV"), *outs):
+        assert a.tobytes() == b_.tobytes(), name

@@ -776,3 +776,23 @@ def test_f16_backward_read_placement(monkeypatch, diag_lib, variant, d, policy, 
     run_case(np.float16, policy, 1, "none_front", (2,), d, d, (328,), (264,), ws=ws, ls=0, causal=causal,
              seed=int(variant) + d)
     assert calls(1) == before + 1
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda t: np.dtype(t).name)
+def test_past_256_channels_the_backward_is_repeatable(dtype):
+    """Past 256 channels (fa_generic.hip's channel-chunked kernels) dQ used to be summed through atomics from the
+    key-outer pass, and its bits changed from call to call (the combined / grouped sweep, tests/test_gpu_union_fuzz.py:
+    13 of its 60 default cases of that class in one run).  Its query-outer pass walks the key blocks in order: ten key
+    blocks here, five calls, every gradient bit for bit the same; and the oracle's parity for that shape."""
+    d, vd, nq, nk = 288, 264, 70, 300
+    run_case(dtype, "local", 1, "scale_end", (2,), d, vd, (nq,), (nk,), ws=40, causal=True, seed=288)
+    rng = np.random.default_rng(288)
+    Q, K, V, dO = (rng.uniform(-2, 2, s).astype(dtype) for s in ((2, d, nq), (2, d, nk), (2, vd, nk), (2, vd, nq)))
+    dev = torch.device("cuda:0")
+    runs = []
+    for _ in range(5):
+        tq, tk, tv = (_to_dev(x, dev, True, False) for x in (Q, K, V))
+        _fa().full_1d(tq, tk, tv).backward(torch.from_numpy(dO).to(dev))
+        torch.cuda.synchronize()
+        runs.append([t.grad.cpu().numpy().tobytes() for t in (tq, tk, tv)])
+    assert all(r == runs[0] for r in runs[1:])

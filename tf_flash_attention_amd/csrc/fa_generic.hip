@@ -14,7 +14,9 @@
 //             registers and are written exactly once — no inter-workgroup locks.
 //   backward: prep kernel (D = rowsum(dO*O), lse = m + log l), one workgroup per
 //             (batch slice, 32-key block) accumulating dK/dV in registers and dQ
-//             through fp32/fp64 atomics into a workspace, then a cast kernel.
+//             through fp32/fp64 atomics into a workspace, then a cast kernel (the
+//             resident form; the channel-chunked form has a query-outer dQ pass
+//             instead and no atomics).
 #include "fa_device.h"
 #include "fa_kernels.h"
 
@@ -461,10 +463,11 @@ __global__ __launch_bounds__(kThreads) void fwd_generic_ch_kernel(FwdArgs a, int
   }
 }
 
-// backward: one workgroup per (slice, 32-key block, chunk of kVC output channels): S and dP of a
-// query tile are summed over 32-channel chunks of Q / K and dO / V; the workgroup then
-// accumulates dK and dV for its channel chunk and adds its chunk of dQ through atomics (the
-// resident kernel's scheme, bwd_generic_kernel)
+// backward, dK and dV: one workgroup per (slice, 32-key block, chunk of kVC output channels): S and dP
+// of a query tile are summed over 32-channel chunks of Q / K and dO / V; the workgroup then
+// accumulates dK and dV for its channel chunk in registers.  dQ has a query-outer pass of its own
+// (bwd_generic_ch_dq_kernel): summed through atomics from here, as in the resident kernel, its bits
+// changed from one call to the next, and combined / grouped attention promise a repeatable gradient.
 template <typename T>
 __global__ __launch_bounds__(kThreads) void bwd_generic_ch_kernel(BwdArgs a, int noc) {
   using A = typename AccOf<T>::type;
@@ -476,8 +479,7 @@ __global__ __launch_bounds__(kThreads) void bwd_generic_ch_kernel(BwdArgs a, int
   A* Xk = Xq + kDC * kGBQ;             // [kDC][BK] chunk of K or V
   A* Qo = Xk + kDC * kGBK;             // [kOC][BQ] the output chunk's Q rows
   A* dOo = Qo + kOC * kGBQ;            // [kOC][BQ] ... dO rows
-  A* Ko = dOo + kOC * kGBQ;            // [kOC][BK] ... K rows (for dQ; fixed per workgroup)
-  A* Ps = Ko + kOC * kGBK;             // [BQ][BK+1]
+  A* Ps = dOo + kOC * kGBQ;            // [BQ][BK+1]
   A* dSs = Ps + kGBQ * (kGBK + 1);     // [BQ][BK+1]
   A* lse_s = dSs + kGBQ * (kGBK + 1);  // [BQ]
   A* D_s = lse_s + kGBQ;               // [BQ]
@@ -496,12 +498,7 @@ __global__ __launch_bounds__(kThreads) void bwd_generic_ch_kernel(BwdArgs a, int
   const T* dO = static_cast<const T*>(a.dO) + bi * (int64_t)vd * nq;
   const A* gD = static_cast<const A*>(a.ws_D) + bi * (int64_t)nq;
   const A* glse = static_cast<const A*>(a.ws_lse) + bi * (int64_t)nq;
-  A* dQacc = static_cast<A*>(a.ws_dQ) + bi * (int64_t)d * nq;
 
-  for (int idx = tid; idx < kOC * kGBK; idx += kThreads) {
-    const int c = c0 + idx / kGBK, kk = idx % kGBK;
-    Ko[idx] = (c < d && k0 + kk < nk) ? to_acc<A>(K[(int64_t)c * nk + k0 + kk]) : A(0);
-  }
   const int klast = min(k0 + kGBK, nk) - 1;
   int qb, qe;
   q_range_for_k_block(a.rule, k0, klast, &qb, &qe);
@@ -577,17 +574,6 @@ __global__ __launch_bounds__(kThreads) void bwd_generic_ch_kernel(BwdArgs a, int
         dk[i] = acc;
       }
     }
-    {  // dQ[c][q] += sum_j dS[q][j] * K[c][j] for this chunk's channels
-      const int qq = tid & 31, cg = tid >> 5, q = q0 + qq;
-      if (q < qe) {
-        for (int cl = cg; cl < kOC && c0 + cl < d; cl += 8) {
-          A acc = A(0);
-#pragma unroll 8
-          for (int jj = 0; jj < kGBK; ++jj) acc += dSs[qq * (kGBK + 1) + jj] * Ko[cl * kGBK + jj];
-          atomicAdd(&dQacc[(int64_t)(c0 + cl) * nq + q], acc);
-        }
-      }
-    }
   }
 
   if (!kvalid) return;
@@ -598,6 +584,127 @@ __global__ __launch_bounds__(kThreads) void bwd_generic_ch_kernel(BwdArgs a, int
     const int c = c0 + g + 8 * i;
     if (c < d) dK[(int64_t)c * nk + k] = from_acc<T>(dk[i]);
     if (c < vd) dV[(int64_t)c * nk + k] = from_acc<T>(dv[i]);
+  }
+}
+
+// backward, dQ: one workgroup per (slice, 32-query block, chunk of kVC channels of d).  The key blocks
+// the rule allows the query block are walked in order; S and dP are recomputed as above, dS goes
+// through LDS, and every thread keeps its dQ elements in registers: no atomics and no workspace, so
+// an element's bits depend on its inputs only.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void bwd_generic_ch_dq_kernel(BwdArgs a, int noc) {
+  using A = typename AccOf<T>::type;
+  constexpr int kOC = ChunkOf<T>::kVC;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int d = a.d, vd = a.v_d;
+  const int nq = a.rule.q.n, nk = a.rule.k.n;
+  A* Xq = reinterpret_cast<A*>(smem);  // [kDC][BQ] chunk of Q or dO
+  A* Xk = Xq + kDC * kGBQ;             // [kDC][BK] chunk of K or V
+  A* Ko = Xk + kDC * kGBK;             // [kOC][BK] the output chunk's K rows of the current key block
+  A* dSs = Ko + kOC * kGBK;            // [BQ][BK+1]
+  A* lse_s = dSs + kGBQ * (kGBK + 1);  // [BQ]
+  A* D_s = lse_s + kGBQ;               // [BQ]
+
+  const uint32_t nqb = (nq + kGBQ - 1) / kGBQ;
+  const uint32_t bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int oc = bid % noc;
+  const int64_t bi = (bid / noc) / nqb;
+  const int q0 = ((bid / noc) % nqb) * kGBQ;
+  const int c0 = oc * kOC;
+  const int tid = threadIdx.x, j = tid & 31, g = tid >> 5;
+
+  const T* Q = static_cast<const T*>(a.Q) + bi * (int64_t)d * nq;
+  const T* K = static_cast<const T*>(a.K) + bi * (int64_t)d * nk;
+  const T* V = static_cast<const T*>(a.V) + bi * (int64_t)vd * nk;
+  const T* dO = static_cast<const T*>(a.dO) + bi * (int64_t)vd * nq;
+  const A* gD = static_cast<const A*>(a.ws_D) + bi * (int64_t)nq;
+  const A* glse = static_cast<const A*>(a.ws_lse) + bi * (int64_t)nq;
+
+  const int qlast = min(q0 + kGBQ, nq) - 1;
+  int kb, ke;
+  k_range_for_q_block(a.rule, q0, qlast, &kb, &ke);
+  const A scale = static_cast<A>(a.scale);
+  if (tid < kGBQ) {
+    const bool v = q0 + tid < nq;
+    lse_s[tid] = v ? glse[q0 + tid] : pos_inf<A>();
+    D_s[tid] = v ? gD[q0 + tid] : A(0);
+  }
+  int qo[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int q = q0 + g + 8 * i;
+    qo[i] = (q < nq && a.rule.policy != 0) ? seq_order(a.rule.q, a.rule, q) : 0;
+  }
+
+  A dq[kOC / 8];
+#pragma unroll
+  for (int i = 0; i < kOC / 8; ++i) dq[i] = A(0);
+
+  for (int k0 = kb; k0 < ke; k0 += kGBK) {
+    // S = Q^T K and dP = dO^T V over channel chunks (thread: queries g + 8i, key j)
+    A sacc[4] = {A(0), A(0), A(0), A(0)}, pacc[4] = {A(0), A(0), A(0), A(0)};
+    for (int pass = 0; pass < 2; ++pass) {
+      const int cn = pass == 0 ? d : vd;
+      const T* Xg = pass == 0 ? Q : dO;
+      const T* Yg = pass == 0 ? K : V;
+      for (int cc = 0; cc < cn; cc += kDC) {
+        __syncthreads();
+        for (int idx = tid; idx < kDC * kGBQ; idx += kThreads) {
+          const int c = cc + idx / kGBQ, qq = idx % kGBQ;
+          Xq[idx] = (c < cn && q0 + qq < nq) ? to_acc<A>(Xg[(int64_t)c * nq + q0 + qq]) : A(0);
+          const int kk = idx % kGBK;
+          Xk[idx] = (c < cn && k0 + kk < ke) ? to_acc<A>(Yg[(int64_t)c * nk + k0 + kk]) : A(0);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int qq = g + 8 * i;
+          A t = A(0);
+#pragma unroll 8
+          for (int c = 0; c < kDC; ++c) t += Xq[c * kGBQ + qq] * Xk[c * kGBK + j];
+          if (pass == 0) sacc[i] += t; else pacc[i] += t;
+        }
+      }
+    }
+    // (every thread passed a barrier after the previous key block's dQ sums: Ko and dSs are free)
+    for (int idx = tid; idx < kOC * kGBK; idx += kThreads) {
+      const int c = c0 + idx / kGBK, kk = idx % kGBK;
+      Ko[idx] = (c < d && k0 + kk < ke) ? to_acc<A>(K[(int64_t)c * nk + k0 + kk]) : A(0);
+    }
+    const int k = k0 + j;
+    const bool kvalid = k < ke;
+    const int ko = (kvalid && a.rule.policy != 0) ? seq_order(a.rule.k, a.rule, k) : 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int qq = g + 8 * i;
+      bool ok = kvalid && q0 + qq < nq;
+      if (ok && a.rule.policy != 0) ok = check_orders(a.rule, qo[i], ko);
+      const A p = ok ? fa_exp(sacc[i] * scale - lse_s[qq]) : A(0);
+      dSs[qq * (kGBK + 1) + j] = p * (pacc[i] - D_s[qq]) * scale;
+    }
+    __syncthreads();
+    {  // dQ[c][q] += sum_j dS[q][j] * K[c][j] for this chunk's channels, key blocks in order
+      const int qq = tid & 31, cg = tid >> 5;
+#pragma unroll
+      for (int i = 0; i < kOC / 8; ++i) {
+        const int cl = cg + 8 * i;
+        if (c0 + cl < d) {
+          A acc = dq[i];
+#pragma unroll 8
+          for (int jj = 0; jj < kGBK; ++jj) acc += dSs[qq * (kGBK + 1) + jj] * Ko[cl * kGBK + jj];
+          dq[i] = acc;
+        }
+      }
+    }
+  }
+
+  const int qq = tid & 31, cg = tid >> 5, q = q0 + qq;
+  if (q >= nq) return;
+  T* dQ = static_cast<T*>(a.dQ) + bi * (int64_t)d * nq;
+#pragma unroll
+  for (int i = 0; i < kOC / 8; ++i) {
+    const int c = c0 + cg + 8 * i;
+    if (c < d) dQ[(int64_t)c * nq + q] = from_acc<T>(dq[i]);
   }
 }
 
@@ -621,26 +728,26 @@ hipError_t launch_bwd_generic_ch(const BwdArgs& a, hipStream_t stream) {
   using A = typename AccOf<T>::type;
   constexpr int kOC = ChunkOf<T>::kVC;
   const int nq = a.rule.q.n, nk = a.rule.k.n;
-  hipError_t e = hipMemsetAsync(a.ws_dQ, 0, sizeof(A) * (size_t)a.b * a.d * nq, stream);
-  if (e != hipSuccess) return e;
   const int64_t nrows = a.b * (int64_t)nq;
   hipLaunchKernelGGL(bwd_prep_kernel<T>, dim3((unsigned)((nrows + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, a);
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int64_t nkb = (nk + kGBK - 1) / kGBK;
-  const int noc = (max(a.d, a.v_d) + kOC - 1) / kOC;
-  if (a.b * nkb * noc >= (int64_t(1) << 31)) return hipErrorInvalidConfiguration;  // grid.x range
-  const size_t smem = sizeof(A) * ((size_t)kDC * (kGBQ + kGBK) + (size_t)kOC * (2 * kGBQ + kGBK) + 2 * kGBQ * (kGBK + 1) +
-                                   2 * kGBQ);
+  const int64_t nkb = (nk + kGBK - 1) / kGBK, nqb = (nq + kGBQ - 1) / kGBQ;
+  const int noc = (max(a.d, a.v_d) + kOC - 1) / kOC, nocq = (a.d + kOC - 1) / kOC;
+  if (a.b * nkb * noc >= (int64_t(1) << 31) || a.b * nqb * nocq >= (int64_t(1) << 31))
+    return hipErrorInvalidConfiguration;  // grid.x range
+  const size_t smem = sizeof(A) * ((size_t)kDC * (kGBQ + kGBK) + (size_t)kOC * 2 * kGBQ + 2 * kGBQ * (kGBK + 1) + 2 * kGBQ);
   auto kern = bwd_generic_ch_kernel<T>;
   e = set_smem_once(reinterpret_cast<const void*>(kern), (int)smem);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * nkb * noc)), dim3(kThreads), smem, stream, a, noc);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int64_t n = a.b * (int64_t)a.d * nq;
-  hipLaunchKernelGGL(cast_dq_kernel<T>, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream,
-                     static_cast<const A*>(a.ws_dQ), static_cast<T*>(a.dQ), n);
+  const size_t smem_dq = sizeof(A) * ((size_t)kDC * (kGBQ + kGBK) + (size_t)kOC * kGBK + kGBQ * (kGBK + 1) + 2 * kGBQ);
+  auto kern_dq = bwd_generic_ch_dq_kernel<T>;
+  e = set_smem_once(reinterpret_cast<const void*>(kern_dq), (int)smem_dq);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern_dq, dim3((unsigned)(a.b * nqb * nocq)), dim3(kThreads), smem_dq, stream, a, nocq);
   return hipGetLastError();
 }
 
