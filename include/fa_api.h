@@ -453,7 +453,9 @@ int fa_append_paged_fp8(void* stream, int64_t sequences,
                         const int32_t* k_lens, const int32_t* new_lens);
 
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
- * flash_attention_backward.cc:274-283).  Pass that many bytes (or more). */
+ * flash_attention_backward.cc:274-283): the D = rowsum(dO * O) rows and the lse rows,
+ * [b][nq] of fp32 (fp64 problems: fp64), each rounded up to 256 bytes.  There is no dQ
+ * accumulator: every backward writes dQ once, without atomics.  Pass that many bytes (or more). */
 size_t fa_backward_workspace_bytes(const fa_problem* p);
 
 /* Backward: writes dQ, dK, dV from Q, K, V, O, l, m, dO.  Replaces

@@ -190,11 +190,30 @@ def test_backward_rejects_mismatched_dtypes():
 
 
 def test_backward_workspace_size():
+    """The D rows plus the lse rows, [b][nq] of the accumulator type (fp32; fp64 for fp64), each 256-B aligned."""
     p = _prob("causal", [100], [60], b=3, d=16, vd=8, dtype=_lib.F16)
-    n = _lib.lib().fa_backward_workspace_bytes(p)
-    assert n >= 4 * 3 * 16 * 100 + 2 * 4 * 3 * 100
+    assert _lib.lib().fa_backward_workspace_bytes(p) == 2 * 1280  # 4 * 3 * 100 = 1200 -> 1280
     p.dtype = _lib.F64
-    assert _lib.lib().fa_backward_workspace_bytes(p) >= 8 * 3 * 16 * 100
+    assert _lib.lib().fa_backward_workspace_bytes(p) == 2 * 2560  # 8 * 3 * 100 = 2400 -> 2560
+
+
+def test_a_grid_past_the_launch_range_is_refused_on_the_host():
+    """2^31 one-query slices: no MFMA kernel's grid holds them, and the SIMT kernels' does not either.  Both calls
+    are refused by the host predicates (fwd_generic_supported / bwd_generic_supported) before any device call:
+    without a device, any other status would mean a launch was attempted.  The pointers are never read."""
+    L = _lib.lib()
+    p = _prob("full", [1], [1], b=2 ** 31, d=8, vd=8, dtype=_lib.F32)
+    assert L.fa_validate(p) == 0
+    buf = ctypes.create_string_buffer(256)
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    assert L.fa_forward(None, p, ptr, ptr, ptr, ptr, ptr, ptr) == _lib.FA_ERR_UNSUPPORTED
+    assert "2^31 workgroups" in _lib.last_error()
+    L.fa_validate(_prob("full", [16], [16], d=0))  # (another message in between)
+    need = L.fa_backward_workspace_bytes(p)
+    assert need == 2 * 4 * 2 ** 31
+    st = L.fa_backward(None, p, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, need)
+    assert st == _lib.FA_ERR_UNSUPPORTED
+    assert "2^31 workgroups" in _lib.last_error()
 
 
 def test_estimate_flops_is_algorithmic():

@@ -343,7 +343,7 @@ def test_f32_mfma_shapes(d, policy, nq, nk):
     run_case(np.float32, policy, 1, "scale_end", (2, 1), d, d, (nq,), (nk,), ws=41, ls=0, causal=True, seed=d + 1)
 
 
-# fp64 MFMA path (fa_f64.hip): forward any d, v_d <= 128, backward d, v_d <= 64 (generic above)
+# fp64 MFMA path (fa_f64.hip): forward and backward for d, v_d <= 256 (these shapes: up to 128)
 @pytest.mark.parametrize("d", [16, 32, 48, 64, 96, 128])
 @pytest.mark.parametrize("policy", ["full", "causal", "local"])
 @pytest.mark.parametrize("nq,nk", [(256, 256), (130, 1001)])
@@ -420,9 +420,9 @@ def test_odd_channels(d, vd):
 @pytest.mark.parametrize("d,vd", [(160, 160), (256, 256), (130, 300), (520, 72), (300, 1030)])
 @pytest.mark.parametrize("policy,ws,causal", [("full", 1, False), ("causal", 1, False), ("local", 40, True)])
 def test_wide_channels(dtype, d, vd, policy, ws, causal):
-    """Channel counts past 128: the MFMA kernels up to 256 channels (fp16 for aligned tensors, fp32 and
-    fp64 always), the resident / channel-chunked generic kernels past that (the reference has no fixed
-    channel cap either: its key tile is sized from shared memory, flash_attention.cu:1977-2067)."""
+    """Channel counts past 128: the MFMA kernels up to 256 channels (every dtype, any alignment), the
+    channel-chunked generic kernels past that (the reference has no fixed channel cap either: its key
+    tile is sized from shared memory, flash_attention.cu:1977-2067)."""
     run_case(dtype, policy, 1, "scale_front", (2,), d, vd, (97,), (150,), ws=ws, causal=causal, seed=d + vd)
 
 
@@ -622,7 +622,8 @@ def test_config5_full2d_f32_sampled():
 # axis other than x holds 65535 blocks at most).  The shapes follow the *_supported predicates of csrc/.
 MANY_SLICES = [0, 1, 32767, 32768, 65535, 65536, 65537]
 MANY_SLICE_CASES = {
-    # fa_generic.hip, both directions: the only path past 256 channels (an odd count)
+    # fa_generic.hip's channel-chunked kernels (it has no others), both directions: what the dispatch sends past 256
+    # channels (an odd count)
     "generic_simt": (np.float16, "full", 257, 257, (2,), (3,), 1),
     # fa_fwd_f16.hip launch_t<32, 4, 8> (max(d, v_d) <= 32 is never the fast forward) and the two-pass backward of
     # fa_bwd_f16_fast.hip, which takes every fp16 shape up to 256 channels
@@ -795,4 +796,60 @@ def test_past_256_channels_the_backward_is_repeatable(dtype):
         _fa().full_1d(tq, tk, tv).backward(torch.from_numpy(dO).to(dev))
         torch.cuda.synchronize()
         runs.append([t.grad.cpu().numpy().tobytes() for t in (tq, tk, tv)])
+    assert all(r == runs[0] for r in runs[1:])
+
+
+# ------------------------------------------------ the SIMT kernels below their dispatch range
+# fa_generic.hip's channel-chunked kernels serve every d and v_d, but below 257 channels the dispatch reaches them
+# only where an MFMA kernel's 32-bit grid or row offsets run out (2^31 workgroups, a row set past 2^31 bytes).
+# FA_FWD_VARIANT = FA_BWD_VARIANT = 9000 (diagnostic library) skips the MFMA dispatch, so that they run the
+# smallest shapes at which they can go wrong there: d below, at and just past one 32-channel staging chunk, a full
+# and a non-full output chunk (256 channels; 128 at fp64, where (5, 130) and (200, 256) make two), lengths off the
+# 32-row tiles and a single query, every rule family.
+SIMT_CHANNELS = [(d, vd, dt) for d, vd in [(1, 1), (8, 40), (32, 32), (33, 64), (64, 31), (256, 256)] for dt in DTYPES]
+SIMT_CHANNELS += [(5, 130, np.float64), (200, 256, np.float64)]
+SIMT_LENGTHS = [(33, 70), (1, 3), (64, 32)]
+SIMT_RULES = [("full", "none_front", 1, False), ("causal", "scale_end", 1, False), ("local", "none_front", 5, True)]
+
+
+def _simt_pin(monkeypatch):
+    monkeypatch.setenv("FA_FWD_VARIANT", "9000")
+    monkeypatch.setenv("FA_BWD_VARIANT", "9000")
+
+
+@pytest.mark.parametrize("d,vd,dtype", SIMT_CHANNELS, ids=lambda x: str(x) if isinstance(x, int) else np.dtype(x).name)
+def test_simt_kernels_below_257_channels(monkeypatch, diag_lib, d, vd, dtype):
+    _simt_pin(monkeypatch)
+    calls = diag_lib.fa_diag_call_count
+    calls.restype = __import__("ctypes").c_longlong
+    before = calls(0), calls(1)
+    n = 0
+    for nq, nk in SIMT_LENGTHS:
+        for policy, mode, ws, causal in SIMT_RULES:
+            run_case(dtype, policy, 1, mode, (2,), d, vd, (nq,), (nk,), ws=ws, causal=causal, seed=9000 + d + vd + nq)
+            n += 1
+    run_case(dtype, "causal", 2, "scale_front", (2,), d, vd, (8, 24), (16, 16), seed=9000 + d + vd)
+    n += 1
+    assert (calls(0), calls(1)) == (before[0] + n, before[1] + n)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=lambda t: np.dtype(t).name)
+def test_simt_backward_below_257_channels_is_repeatable(monkeypatch, diag_lib, dtype):
+    """The same kernels at d = 40, v_d = 24 over ten key blocks, five calls: every gradient bit for bit the same
+    (no path of the library sums a gradient through atomics)."""
+    _simt_pin(monkeypatch)
+    d, vd, nq, nk = 40, 24, 70, 300
+    rng = np.random.default_rng(9040)
+    Q, K, V, dO = (rng.uniform(-2, 2, s).astype(dtype) for s in ((2, d, nq), (2, d, nk), (2, vd, nk), (2, vd, nq)))
+    dev = torch.device("cuda:0")
+    calls = diag_lib.fa_diag_call_count
+    calls.restype = __import__("ctypes").c_longlong
+    before = calls(1)
+    runs = []
+    for _ in range(5):
+        tq, tk, tv = (_to_dev(x, dev, True, False) for x in (Q, K, V))
+        _fa().full_1d(tq, tk, tv).backward(torch.from_numpy(dO).to(dev))
+        torch.cuda.synchronize()
+        runs.append([t.grad.cpu().numpy().tobytes() for t in (tq, tk, tv)])
+    assert calls(1) == before + 5
     assert all(r == runs[0] for r in runs[1:])

@@ -160,19 +160,15 @@ size_t elem_size(int dtype) { return dtype == FA_F16 ? 2 : (dtype == FA_F32 ? 4 
 
 size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 
+// the backward workspace: the D rows, then the lse rows, [b][nq] of the accumulator type each
 struct WsLayout {
-  size_t dq, D, lse, total;
+  size_t D, lse, total;
 };
 
 WsLayout ws_layout(const fa_problem* p) {
   const int64_t nq = seq_elems(p->q_seq, p->seq_dims);
-  const size_t a = acc_size(p->dtype);
-  WsLayout w;
-  w.dq = 0;
-  w.D = align_up(a * (size_t)p->b * (size_t)p->d * (size_t)nq);
-  w.lse = w.D + align_up(a * (size_t)p->b * (size_t)nq);
-  w.total = w.lse + align_up(a * (size_t)p->b * (size_t)nq);
-  return w;
+  const size_t rows = align_up(acc_size(p->dtype) * (size_t)p->b * (size_t)nq);
+  return {0, rows, 2 * rows};
 }
 
 // Split-key routing of the fp16 forward.  A pure function of the problem WITHOUT b,
@@ -590,7 +586,7 @@ void fill_bwd(const fa_problem* p, const WsLayout& w, const void* Q, const void*
   a->Q = Q; a->K = K; a->V = V; a->O = O; a->l = l; a->m = m; a->dO = dO;
   a->dQ = dQ; a->dK = dK; a->dV = dV;
   char* ws = static_cast<char*>(workspace);
-  a->ws_dQ = ws + w.dq;
+  a->reserved = nullptr;
   a->ws_D = ws + w.D;
   a->ws_lse = ws + w.lse;
   fill_problem(p, a);
@@ -614,7 +610,6 @@ int bwd_slabs(const fa_problem* p, const fa::BwdArgs& whole, int64_t bmax, fa::B
     a->dQ = static_cast<uint16_t*>(whole.dQ) + b0 * p->d * nq;
     a->dK = static_cast<uint16_t*>(whole.dK) + b0 * p->d * nk;
     a->dV = static_cast<uint16_t*>(whole.dV) + b0 * p->v_d * nk;
-    // (ws_dQ stays: the two-pass kernels keep no dQ accumulator)
     a->ws_D = static_cast<float*>(whole.ws_D) + b0 * nq;
     a->ws_lse = static_cast<float*>(whole.ws_lse) + b0 * nq;
     FA_DIAG_SLAB();
@@ -676,9 +671,16 @@ long long fa_diag_call_count(int which) { return (which == 0 || which == 1) ? g_
 #define FA_DIAG_COUNT(w) g_diag_calls[w].fetch_add(1)
 // slab launches of the four slab loops (fewq_slabs, bwd_slabs, the merge and the accumulate loop)
 long long fa_diag_slab_count(void) { return g_diag_slabs.load(); }
+// FA_FWD_VARIANT / FA_BWD_VARIANT = 9000 skips the MFMA dispatch of fa_forward / fa_backward, so that a test can
+// run the SIMT kernels at the small shapes they otherwise serve only when an MFMA predicate fails
+#define FA_DIAG_SIMT(name) (fa::diag_variant(name) == 9000)
 #else
 #define FA_DIAG_COUNT(w) ((void)0)
+#define FA_DIAG_SIMT(name) false
 #endif
+
+static const char kGenericUnsupported[] =
+    "no kernel takes this shape: more than 65536 channels, or a launch grid of 2^31 workgroups or more";
 
 int fa_forward(void* stream, const fa_problem* p, const void* Q, const void* K, const void* V, void* O, void* l,
                void* m) {
@@ -690,17 +692,18 @@ int fa_forward(void* stream, const fa_problem* p, const void* Q, const void* K, 
   fill_problem(p, &a);
   if (a.b == 0 || a.rule.q.n == 0) return FA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool mfma = !FA_DIAG_SIMT("FA_FWD_VARIANT");
   hipError_t e;
-  if (p->dtype == FA_F16 && fa::fwd_f16_supported(a)) {
+  if (mfma && p->dtype == FA_F16 && fa::fwd_f16_supported(a)) {
     e = fa::launch_fwd_f16(a, s);
-  } else if (p->dtype == FA_F32 && fa::fwd_f32_supported(a)) {
+  } else if (mfma && p->dtype == FA_F32 && fa::fwd_f32_supported(a)) {
     e = fa::launch_fwd_f32(a, s);
-  } else if (p->dtype == FA_F64 && fa::fwd_f64_supported(a)) {
+  } else if (mfma && p->dtype == FA_F64 && fa::fwd_f64_supported(a)) {
     e = fa::launch_fwd_f64(a, s);
-  } else {
-    if (p->d > fa::generic_max_channels(p->dtype) || p->v_d > fa::generic_max_channels(p->dtype))
-      return set_error(FA_ERR_UNSUPPORTED, "channel dimension exceeds the supported maximum for this dtype");
+  } else if (fa::fwd_generic_supported(p->dtype, a)) {
     e = fa::launch_fwd_generic(p->dtype, a, s);
+  } else {
+    return set_error(FA_ERR_UNSUPPORTED, kGenericUnsupported);
   }
   if (e != hipSuccess)
     return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
@@ -1131,6 +1134,7 @@ int fa_backward(void* stream, const fa_problem* p, const void* Q, const void* K,
   fill_bwd(p, w, Q, K, V, O, l, m, dO, dQ, dK, dV, workspace, &a);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.b == 0) return FA_OK;
+  const bool mfma = !FA_DIAG_SIMT("FA_BWD_VARIANT");
   hipError_t e = hipSuccess;
   if (a.rule.q.n == 0 || a.rule.k.n == 0) {
     // nothing attends: every gradient is zero
@@ -1138,16 +1142,16 @@ int fa_backward(void* stream, const fa_problem* p, const void* Q, const void* K,
     if (a.rule.q.n) e = hipMemsetAsync(dQ, 0, es * (size_t)a.b * a.d * a.rule.q.n, s);
     if (e == hipSuccess && a.rule.k.n) e = hipMemsetAsync(dK, 0, es * (size_t)a.b * a.d * a.rule.k.n, s);
     if (e == hipSuccess && a.rule.k.n) e = hipMemsetAsync(dV, 0, es * (size_t)a.b * a.v_d * a.rule.k.n, s);
-  } else if (p->dtype == FA_F16 && fa::bwd_f16_supported(a)) {
-    e = fa::launch_bwd_f16(a, s);
-  } else if (p->dtype == FA_F32 && fa::bwd_f32_supported(a)) {
+  } else if (mfma && p->dtype == FA_F16 && fa::bwd_f16_fast_supported(a)) {
+    e = fa::launch_bwd_f16_fast(a, s);
+  } else if (mfma && p->dtype == FA_F32 && fa::bwd_f32_supported(a)) {
     e = fa::launch_bwd_f32(a, s);
-  } else if (p->dtype == FA_F64 && fa::bwd_f64_supported(a)) {
+  } else if (mfma && p->dtype == FA_F64 && fa::bwd_f64_supported(a)) {
     e = fa::launch_bwd_f64(a, s);
-  } else {
-    if (p->d > fa::generic_max_channels(p->dtype) || p->v_d > fa::generic_max_channels(p->dtype))
-      return set_error(FA_ERR_UNSUPPORTED, "channel dimension exceeds the supported maximum for this dtype");
+  } else if (fa::bwd_generic_supported(p->dtype, a)) {
     e = fa::launch_bwd_generic(p->dtype, a, s);
+  } else {
+    return set_error(FA_ERR_UNSUPPORTED, kGenericUnsupported);
   }
   if (e != hipSuccess)
     return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
@@ -1389,7 +1393,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV) / single-pass), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
 }
 
 }  // extern "C"

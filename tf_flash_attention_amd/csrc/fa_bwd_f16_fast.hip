@@ -21,8 +21,8 @@
 //              Sᵀ = Kᵀ·Q' (C = -lse2)    dPᵀ = Vᵀ·dO (C = -D)
 //              dQ += K·(Pᵀ∘dPᵀ)
 // The dq pass recomputes Sᵀ and dPᵀ (4d of the 14d MFMA FLOPs per allowed pair
-// against the algorithmic 10d) in exchange for writing dQ exactly once; the
-// single-kernel alternative (fa_bwd_f16.hip) spends that in fp32 atomics, which
+// against the algorithmic 10d) in exchange for writing dQ exactly once; a
+// single-kernel backward (round 1's, since removed) spends that in fp32 atomics, which
 // cap it at ≈ 1.3 TB/s of added bytes (MI355X_MICROARCH.md 'Global float atomics').
 // With one query block against a long key range the dq pass would run one workgroup per slice;
 // launch_bwd_f16_split runs it on one workgroup per (slice, key chunk) instead (bwd_dq_kernel's SPLIT

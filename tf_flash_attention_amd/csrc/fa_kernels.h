@@ -34,7 +34,9 @@ struct BwdArgs {
   void* dQ;
   void* dK;
   void* dV;
-  void* ws_dQ;   // accumulator: b*d*nq of AccT
+  // never read: holds the 8 bytes of the former dQ accumulator pointer, so that every later member keeps its
+  // kernarg offset and the backward kernels their instruction streams (profiles/fallback_retire_asm_equal.txt)
+  void* reserved;
   void* ws_D;    // b*nq AccT
   void* ws_lse;  // b*nq AccT
   int64_t b;
@@ -189,13 +191,15 @@ hipError_t launch_merge(int dtype, int n_parts, const MergeArgs& a, hipStream_t 
 int64_t accumulate_max_count();
 hipError_t launch_accumulate(int dtype, int n_parts, const AccumulateArgs& a, hipStream_t s);
 
-// generic (any dtype) path — fa_generic.hip
+// generic (any dtype, any channel count) SIMT path, channel-chunked — fa_generic.hip.  The caller refuses
+// what the predicates do not take (a channel count past 65536, a grid of 2^31 blocks or more).
+bool fwd_generic_supported(int dtype, const FwdArgs& a);
 hipError_t launch_fwd_generic(int dtype, const FwdArgs& a, hipStream_t s);
+bool bwd_generic_supported(int dtype, const BwdArgs& a);
 hipError_t launch_bwd_generic(int dtype, const BwdArgs& a, hipStream_t s);
-int generic_max_channels(int dtype);
 
-// fp16 MFMA path — fa_fwd_f16.hip / fa_bwd_f16.hip.  Return hipErrorNotSupported
-// when the shape is outside what the MFMA kernels take (caller falls back).
+// The MFMA paths: where a *_supported predicate fails, the caller falls back to the generic path.
+// fp16 MFMA forward — fa_fwd_f16.hip (dispatch over the kernels below)
 bool fwd_f16_supported(const FwdArgs& a);
 hipError_t launch_fwd_f16(const FwdArgs& a, hipStream_t s);
 // streamlined fp16 forward for d == v_d in {64, 128} under full / interval rules — fa_fwd_f16_fast.hip
@@ -251,7 +255,6 @@ hipError_t launch_fwd_f16_prefill(const PrefillOf<Args>& pf, hipStream_t s);
 // one launch of `blocks` = sequences * kv_heads * a.slice_blocks workgroups, which the caller has checked to fit a
 // grid — fa_cache_append.hip
 hipError_t launch_cache_append(bool paged, bool fp8, const AppendArgs& a, int64_t blocks, hipStream_t s);
-bool bwd_f16_supported(const BwdArgs& a);
 // fp32 MFMA forward — fa_fwd_f32.hip
 bool fwd_f32_supported(const FwdArgs& a);
 hipError_t launch_fwd_f32(const FwdArgs& a, hipStream_t s);
@@ -260,7 +263,6 @@ hipError_t launch_fwd_f32_wide(const FwdArgs& a, hipStream_t s);  // fa_fwd_f32_
 bool bwd_f32_supported(const BwdArgs& a);
 hipError_t launch_bwd_f32(const BwdArgs& a, hipStream_t s);
 hipError_t launch_bwd_f32_wide(const BwdArgs& a, hipStream_t s);  // fa_bwd_f32_wide.hip (D = 256, after the prep)
-hipError_t launch_bwd_f16(const BwdArgs& a, hipStream_t s);
 // fp64 MFMA forward and two-pass backward (d, v_d <= 128) — fa_f64.hip
 bool fwd_f64_supported(const FwdArgs& a);
 hipError_t launch_fwd_f64(const FwdArgs& a, hipStream_t s);
@@ -270,8 +272,9 @@ hipError_t launch_bwd_f64(const BwdArgs& a, hipStream_t s);
 // diag/fa_bwd_f16_k64.hip (diagnostic library only: FA_BWD_VARIANT 1700)
 bool bwd_dkdv_k64_supported(const BwdArgs& a);
 hipError_t launch_dkdv_k64(const BwdArgs& a, hipStream_t s);
-// two-pass fp16 backward (dK/dV key-outer + dQ query-outer, no atomics) — fa_bwd_f16_fast.hip (prep, dK/dV,
-// dispatch), fa_bwd_f16_dq.hip (dQ), fa_bwd_f16_wide.hip (D = 256); shared pieces in fa_bwd_f16_parts.h
+// the fp16 MFMA backward, max(d, v_d) <= 256: two passes (dK/dV key-outer + dQ query-outer, no atomics) —
+// fa_bwd_f16_fast.hip (prep, dK/dV, dispatch), fa_bwd_f16_dq.hip (dQ), fa_bwd_f16_wide.hip (D = 256); shared
+// pieces in fa_bwd_f16_parts.h
 bool bwd_f16_fast_supported(const BwdArgs& a);
 hipError_t launch_bwd_f16_fast(const BwdArgs& a, hipStream_t s);
 // the same backward for one query block (nq <= 128, max(d, v_d) <= 128) against a long key range: the

@@ -5,20 +5,27 @@ trace shows which kernels serve them:
   rocprofv3 --kernel-trace --stats -d gpurun_out/disp -o run -- python3 tools/dispatch_trace.py
 
 The two-pass backward (bwd_dkdv_kernel / bwd_dq_kernel) should be the only backward kernels in the
-trace: no bwd_f16_kernel (single-pass, atomics) and no bwd_generic_kernel.
+trace: no *_generic_*.
 
 With the argument f64 it runs fp64 forward + backward at 128 < D <= 256 over every rule class instead
 (the trace should show fwd_f64_kernel / bwd_dkdv_f64_kernel / bwd_dq_f64_kernel and no *_generic_*).
 With f16w: fp16 at 128 < D <= 256 in the shapes past the 16-B chunk staging and the interval rules
 (odd lengths, a misaligned pointer, strided 1d and 2d local windows): fwd_f16_wide_kernel and the
 four-role bwd_dkdv_w4_kernel / bwd_dq_w4_kernel only, no *_generic_*.
+With simt: one tiny forward + backward per dtype through the diagnostic library with FA_FWD_VARIANT =
+FA_BWD_VARIANT = 9000, the pin that skips the MFMA dispatch: fwd_generic_ch_kernel, bwd_prep_kernel,
+bwd_generic_ch_kernel and bwd_generic_ch_dq_kernel only (the torch kernels that fill the inputs aside).
 """
 import os
 import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+if sys.argv[1:2] == ["simt"]:  # (before the package is imported: it reads FA_HIP_LIB once)
+    os.environ["FA_HIP_LIB"] = os.path.join(ROOT, "tf_flash_attention_amd", "libfa_hip_diag.so")
+    os.environ["FA_FWD_VARIANT"] = os.environ["FA_BWD_VARIANT"] = "9000"
 from tf_flash_attention_amd import flash_attention as fa  # noqa: E402
 
 SHAPES = [
@@ -51,13 +58,16 @@ SHAPES_F16W = [
 ]
 
 
+SHAPES_SIMT = [("causal", 1, 40, (33,), (70,), 1, 0, False, False)]
+
+
 def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(0)
     mode = sys.argv[1] if len(sys.argv) > 1 else ""
-    dt = torch.float64 if mode == "f64" else torch.float16
-    shapes = {"f64": SHAPES_F64, "f16w": SHAPES_F16W}.get(mode, SHAPES)
-    for policy, sd, d, qs, ks, ws, ls, causal, mis in shapes:
+    shapes = {"f64": SHAPES_F64, "f16w": SHAPES_F16W, "simt": SHAPES_SIMT}.get(mode, SHAPES)
+    dtypes = {"f64": [torch.float64], "simt": [torch.float16, torch.float32, torch.float64]}.get(mode, [torch.float16])
+    for dt, (policy, sd, d, qs, ks, ws, ls, causal, mis) in ((dt, s) for dt in dtypes for s in shapes):
         def mk(shape):
             n = 1
             for x in shape:

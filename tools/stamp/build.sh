@@ -10,7 +10,7 @@ cd build/pkg
 for f in csrc/*.hip; do
   extra=""
   case $(basename $f) in fa_bwd_f16_fast.hip|fa_bwd_f16_dq.hip|fa_bwd_f16_wide.hip|fa_fwd_f16_fast.hip|fa_fwd_f16_wide.hip|fa_fwd_f32_wide.hip|fa_bwd_f32_wide.hip) extra="-mllvm -amdgpu-mfma-vgpr-form=1";; esac
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -fno-slp-vectorize -fno-honor-nans -w $extra \
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -fno-honor-nans -w $extra \
     -DFA_SRC_HASH=\"stamp\" -I../include -c $f -o ${f%.hip}.o || exit 1 &
   while [ $(jobs -r | wc -l) -ge 8 ]; do sleep 1; done
 done
