@@ -26,6 +26,17 @@
  * (flash_attention.h:181-185).  All buffers are device memory owned by the
  * caller.  Every output element is written by the library (no caller memset).
  *
+ * Pointers of the dense entry points (fa_forward, fa_forward_ws, fa_backward, fa_backward_split): every
+ * tensor need only be aligned to its own element type (2 bytes for fp16 Q / K / V / O / m / dO / dQ / dK /
+ * dV, 4 for an fp32 l, and so on), each on its own: the library picks its 16-byte paths per call from the
+ * pointers and lengths it is given and takes element-wise ones otherwise, so alignment changes the kernel,
+ * never the contract.  Nothing outside [ptr, ptr + bytes) of any tensor influences a result or is written,
+ * whatever those bytes hold (NaN included), and no input is written.  A workspace is the library's own
+ * layout (regions at multiples of 256 bytes from its base, read and written 16 bytes at a time) and must
+ * be 256-byte aligned; the library never reads a workspace byte it has not written in the same call, and
+ * writes none past the size its *_workspace_bytes function reports.  tests/test_gpu_guarded.py holds the
+ * library to this paragraph.
+ *
  * Threading: every entry point is reentrant; all work is enqueued on `stream`
  * (a hipStream_t, NULL = default stream) with no host synchronisation, so the
  * calls are safe inside hipGraph capture.

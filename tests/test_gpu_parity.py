@@ -81,38 +81,28 @@ def _to_dev(x, dev, bwd, misalign):
     return t.requires_grad_(bwd)
 
 
-def run_case(dtype, policy, seq_dims, mode, batch, d, vd, qs, ks, ws=1, ls=0, causal=False, seed=0, bwd=True,
-             slices=None, inputs=None, misalign=False, m_bound=None):
-    """m_bound (optional, [batch, nq] or a scalar): the caller's bound on the rounding of the row max, used in
-    place of the dot-product term of m's tolerance (gate.m_tol_bounded); every other check is unchanged."""
-    rng = np.random.default_rng(seed)
+def check_outputs(dtype, policy, seq_dims, mode, d, vd, qs, ks, ws, ls, causal, Qf, Kf, Vf, dOf, o, l, m, grads=None,
+                  slices=None, m_bound=None, seed=0, oracle=None):
+    """The checks of run_case on numpy results: O, l and m against forward_f64, the rows that attend nothing, and (with
+    grads = (dQ, dK, dV)) the gradients through the gate.  Every array is [b, channels, *seq] (l, m: [b, *seq]) over
+    the flattened batch; `slices` picks the slices that are checked.  `oracle` (optional) is what oracle_outputs
+    returned for the same inputs, problem and slices: a caller that checks several results of one case computes it
+    once."""
     qs, ks = tuple(qs), tuple(ks)
-    if inputs is None:
-        Q = rng.uniform(-2, 2, tuple(batch) + (d,) + qs).astype(dtype)
-        K = rng.uniform(-2, 2, tuple(batch) + (d,) + ks).astype(dtype)
-        V = rng.uniform(-2, 2, tuple(batch) + (vd,) + ks).astype(dtype)
-        dO = rng.uniform(-2, 2, tuple(batch) + (vd,) + qs).astype(dtype)
-    else:
-        Q, K, V, dO = inputs
-    dev = torch.device("cuda:0")
-    tq, tk, tv = (_to_dev(x, dev, bwd, misalign) for x in (Q, K, V))
-    o, l, m = _call(policy, seq_dims, tq, tk, tv, mode, ws, ls, causal)
-    if bwd:
-        o.backward(torch.from_numpy(dO).to(dev))
-    torch.cuda.synchronize()
-    prob = O.Problem(policy, seq_dims, mode, ws, ls, causal)
-    b = int(np.prod(batch))
-    flat = lambda x: x.reshape((b,) + x.shape[len(batch):])  # noqa: E731
+    b = Qf.shape[0]
     sl = list(range(b)) if slices is None else list(slices)
-    Qf, Kf, Vf, dOf = flat(Q), flat(K), flat(V), flat(dO)
-    O64, L64, M64, has_any = O.forward_f64(Qf, Kf, Vf, prob, slices=sl)
+    bwd = grads is not None
+    if oracle is None:
+        oracle = oracle_outputs(dtype, policy, seq_dims, mode, ws, ls, causal, Qf, Kf, Vf, dOf, sl, bwd)
+    prob = oracle["prob"]
+    O64, L64, M64, has_any = oracle["fwd"]
     rtol, atol = TOL[dtype]["fwd"]
-    og = flat(o.detach().cpu().numpy())[sl]
+    og = o[sl]
     res = {"O": _close("O", og, O64, rtol, atol)}
     # l, m
     nq = int(np.prod(qs))
-    lg = flat(l.cpu().numpy()).reshape(b, nq)[sl].astype(np.float64)
-    mg = flat(m.cpu().numpy()).reshape(b, nq)[sl]
+    lg = l.reshape(b, nq)[sl].astype(np.float64)
+    mg = m.reshape(b, nq)[sl]
     M64 = M64.reshape(len(sl), nq)
     L64 = L64.reshape(len(sl), nq)
     ha = has_any
@@ -136,8 +126,10 @@ def run_case(dtype, policy, seq_dims, mode, batch, d, vd, qs, ks, ws=1, ls=0, ca
         # plus the packed-P max approximation (< 4.9e-4); that bound matters at the
         # reference's own shapes (N up to 4096, d = 8..32) for rows whose max is small
         if dtype == np.float16:
-            rowdot = gate.max_abs_dot(Qf[sl].reshape(len(sl), d, nq), Kf[sl].reshape(len(sl), d, -1),
-                                      O.problem_mask(prob, qs, ks))[:, ha] / math.sqrt(d)
+            if "rowdot" not in oracle:  # (a function of the inputs alone: kept with the oracle's values)
+                oracle["rowdot"] = gate.max_abs_dot(Qf[sl].reshape(len(sl), d, nq), Kf[sl].reshape(len(sl), d, -1),
+                                                    O.problem_mask(prob, qs, ks))
+            rowdot = oracle["rowdot"][:, ha] / math.sqrt(d)
             f16_dot = (2.0 ** -11 + d * 2.0 ** -24) * rowdot + 4.9e-4
         m_tol = 2 * ulp + (np.maximum(1e-3 * np.maximum(np.abs(M64[:, ha]), 1.0), f16_dot)
                            if dtype == np.float16
@@ -154,11 +146,10 @@ def run_case(dtype, policy, seq_dims, mode, batch, d, vd, qs, ks, ws=1, ls=0, ca
         assert (lg[:, ~ha] == 0).all()
         assert mg[:, ~ha].tobytes() == b"\xfa" * (mg[:, ~ha].size * np.dtype(dtype).itemsize)
     if bwd:
-        dQ, dK, dV = O.backward_f64(Qf, Kf, Vf, dOf, prob, slices=sl)
-        eQ, eK, eV = O.backward_rounding_scale_f64(Qf, Kf, Vf, dOf, prob, *U_ROUND[dtype], slices=sl)
+        dQ, dK, dV = oracle["bwd"]
+        eQ, eK, eV = oracle["scale"]
         rtol, atol = TOL[dtype]["bwd"]
-        grads = {"dQ": (flat(tq.grad.cpu().numpy())[sl], dQ, eQ), "dK": (flat(tk.grad.cpu().numpy())[sl], dK, eK),
-                 "dV": (flat(tv.grad.cpu().numpy())[sl], dV, eV)}
+        grads = {"dQ": (grads[0][sl], dQ, eQ), "dK": (grads[1][sl], dK, eK), "dV": (grads[2][sl], dV, eV)}
         stats_file = os.environ.get("FA_GATE_STATS")
         if stats_file:  # gate statistics for DESIGN §4 (not part of the verdict)
             with open(stats_file, "a") as f:
@@ -176,6 +167,43 @@ def run_case(dtype, policy, seq_dims, mode, batch, d, vd, qs, ks, ws=1, ls=0, ca
                 f"{name}: scale slope {gate.scale_slope(got, ref):.3e} > "
                 f"{gate.slope_tol_eff(ref, e, dtype, d, ch):.3e}")
     return res
+
+
+def oracle_outputs(dtype, policy, seq_dims, mode, ws, ls, causal, Qf, Kf, Vf, dOf, sl, bwd):
+    """The float64 oracle's values check_outputs compares against, for the slices `sl` of the flattened batch."""
+    prob = O.Problem(policy, seq_dims, mode, ws, ls, causal)
+    out = {"prob": prob, "fwd": O.forward_f64(Qf, Kf, Vf, prob, slices=sl)}
+    if bwd:
+        out["bwd"] = O.backward_f64(Qf, Kf, Vf, dOf, prob, slices=sl)
+        out["scale"] = O.backward_rounding_scale_f64(Qf, Kf, Vf, dOf, prob, *U_ROUND[dtype], slices=sl)
+    return out
+
+
+def run_case(dtype, policy, seq_dims, mode, batch, d, vd, qs, ks, ws=1, ls=0, causal=False, seed=0, bwd=True,
+             slices=None, inputs=None, misalign=False, m_bound=None):
+    """m_bound (optional, [batch, nq] or a scalar): the caller's bound on the rounding of the row max, used in
+    place of the dot-product term of m's tolerance (gate.m_tol_bounded); every other check is unchanged."""
+    rng = np.random.default_rng(seed)
+    qs, ks = tuple(qs), tuple(ks)
+    if inputs is None:
+        Q = rng.uniform(-2, 2, tuple(batch) + (d,) + qs).astype(dtype)
+        K = rng.uniform(-2, 2, tuple(batch) + (d,) + ks).astype(dtype)
+        V = rng.uniform(-2, 2, tuple(batch) + (vd,) + ks).astype(dtype)
+        dO = rng.uniform(-2, 2, tuple(batch) + (vd,) + qs).astype(dtype)
+    else:
+        Q, K, V, dO = inputs
+    dev = torch.device("cuda:0")
+    tq, tk, tv = (_to_dev(x, dev, bwd, misalign) for x in (Q, K, V))
+    o, l, m = _call(policy, seq_dims, tq, tk, tv, mode, ws, ls, causal)
+    if bwd:
+        o.backward(torch.from_numpy(dO).to(dev))
+    torch.cuda.synchronize()
+    b = int(np.prod(batch))
+    flat = lambda x: x.reshape((b,) + x.shape[len(batch):])  # noqa: E731
+    grads = tuple(flat(t.grad.cpu().numpy()) for t in (tq, tk, tv)) if bwd else None
+    return check_outputs(dtype, policy, seq_dims, mode, d, vd, qs, ks, ws, ls, causal, flat(Q), flat(K), flat(V),
+                         flat(dO), flat(o.detach().cpu().numpy()), flat(l.cpu().numpy()), flat(m.cpu().numpy()), grads,
+                         slices=slices, m_bound=m_bound, seed=seed)
 
 
 DTYPES = [np.float16, np.float32, np.float64]
@@ -715,7 +743,7 @@ def test_f16_forward_structures_d128(monkeypatch, diag_lib, variant, policy, seq
              bwd=False, seed=int(variant) + d + ws)
 
 
-# the one-wave D = 128 gap-stream forward (csrc/diag/fa_fwd_f16_gap128.hip, FA_FWD_VARIANT=2700): full,
+# the one-wave D = 128 gap-stream forward (csrc/fa_fwd_f16_gap128.hip, FA_FWD_VARIANT=2700): full,
 # causal (the heavy / light pairs), 1d local and 2d interval rules, lengths off the 256-query block and the
 # 64-key tile, d != v_d, channels below 128
 GAP128_CASES = [
