@@ -573,6 +573,14 @@ int64_t fa_allowed_pairs(const fa_problem* p);
 int fa_rule_mask(const fa_problem* p, uint8_t* mask);
 int fa_rule_probe(const fa_problem* p, int32_t q0, int32_t q1, int32_t k0, int32_t k1, int32_t* out);
 
+/* Host-side dispatch inspection (tests / tooling; launches nothing and reads of the pointers only their
+ * alignment): the kernel fa_forward would launch for this problem and these operands, from the same function
+ * fa_forward launches through.  For fp16 the kernel instance as a kernel trace prints it, e.g.
+ * "fwd_f16_fast_kernel<64, 8, 1, 14>"; for the other paths the family, "fwd_f32", "fwd_f64" or "fwd_generic";
+ * "none" where fa_forward fails or launches nothing.  The string lives as long as the library.  (The diagnostic
+ * library honours FA_FWD_VARIANT here as in the launch.) */
+const char* fa_forward_kernel(const fa_problem* p, const void* Q, const void* K, const void* V);
+
 /* Human-readable text for a status code / the calling thread's last error. */
 const char* fa_error_string(int status);
 const char* fa_last_error(void);

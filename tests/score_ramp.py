@@ -387,9 +387,8 @@ def _c(id, dtype, policy, mode, d, vd, qs, ks, W, tile, big=False, E=None, **kw)
 
 F16, F32, F64 = np.float16, np.float32, np.float64
 # nk = 64·12 + 8 = 776 where the 16-byte staging needs nk % 8 == 0, 64·12 + 5 = 773 for the element-wise
-# one: 13 plateaus with a ragged last one.  Routes are worked out from launch_fwd_f16 (fa_fwd_f16.hip),
-# fwd_f16_fast_supported / launch_fwd_f16_fast (fa_fwd_f16_fast.hip), fwd_f16_{band,pingpong,gap128,
-# pingpong128,wide}_supported, launch_fwd_f32 (fa_fwd_f32.hip) and launch_fwd_f64 (fa_f64.hip).  fp16
+# one: 13 plateaus with a ragged last one.  Routes are worked out from fwd_f16_choice (fa_fwd_f16_choice.h),
+# fwd_f16_band_positions (fa_fwd_f16_band.hip), launch_fwd_f32 (fa_fwd_f32.hip) and launch_fwd_f64 (fa_f64.hip).  fp16
 # cases carry bwd=True only where the emulated deviation passes the backward gate at half the allowance
 # (profiles/score_ramp_gate.txt).
 CASES = [
@@ -399,7 +398,7 @@ CASES = [
     # fwd_f16_fast_kernel<64, 8, POL 1>: causal is an interval rule, not a 1d local one -> the 8-wave kernel
     _c("f16-8wave-d64-causal", F16, "causal", "none_front", 64, 64, 776, 776, 64, 64),
     _c("f16-8wave-d64-causal-big", F16, "causal", "scale_end", 64, 64, 300, 776, 64, 64, big=True),
-    # fwd_f16_fast_kernel<64, 4, POL 1>: 1d local, v_d = 48 != 64 so fwd_f16_band_supported declines
+    # fwd_f16_fast_kernel<64, 4, POL 1>: 1d local, v_d = 48 != 64 so fwd_f16_band_positions declines
     _c("f16-4wave-d64-local", F16, "local", "none_front", 64, 48, 1000, 1000, 64, 64, ws=100),
     # fwd_f16_band_kernel: 1d local, ls = 0, d = v_d = 64, nq % 8 == nk % 8 == 0
     _c("f16-band-local", F16, "local", "none_front", 64, 64, 1000, 1000, 64, 64, ws=100),
@@ -415,7 +414,7 @@ CASES = [
     _c("f16-wide-causal", F16, "causal", "none_front", 256, 256, 776, 776, 64, 64),
     _c("f16-wide-full-elem", F16, "full", "none_front", 256, 256, 300, 773, 64, 64),
     _c("f16-wide-strided-elem", F16, "local", "none_front", 256, 256, 773, 773, 64, 64, ws=60, ls=2, big=True),
-    # fwd_f16_kernel<32, 4, 0, FAST>: max(d, v_d) <= 32 is outside fwd_f16_fast_supported
+    # fwd_f16_kernel<32, 4, 0, FAST>: max(d, v_d) <= 32 is below the tuned kernels
     _c("f16-core-d32-full", F16, "full", "none_front", 32, 32, 300, 776, 64, 64),
     # fwd_f16_kernel<64, 8, 0, elem> and <128, 4, 1, elem>: nk % 8 != 0
     _c("f16-core-d64-full-elem", F16, "full", "none_front", 64, 64, 300, 773, 64, 64),

@@ -13,9 +13,8 @@ the contract of include/fa_api.h, which asks for element alignment only.  The wo
 
 b = 3 (a first, a middle and a last slice), inputs U(-2, 2) from a per-case seed.  The shapes are the smallest that
 keep a ragged tail on every axis where the family can have one.  The route beside each case is read from
-fa_forward / fa_backward (fa_api.hip), launch_fwd_f16 (fa_fwd_f16.hip), fwd_f16_fast_supported / launch_fwd_f16_fast
-(fa_fwd_f16_fast.hip), fwd_f16_{band,pingpong,gap128,pingpong128,wide}_supported, with_pol_fast / fast_staging
-(fa_fwd_f16_core.h), launch_bwd_f16_fast / launch_prep / launch_dkdv_pass (fa_bwd_f16_fast.hip), launch_bwd_f16_dq
+fa_forward / fa_backward (fa_api.hip), fwd_f16_choice (fa_fwd_f16_choice.h; fa_forward_kernel names its result),
+fwd_f16_band_positions (fa_fwd_f16_band.hip), with_pol_fast / fast_staging (fa_fwd_f16_core.h), launch_bwd_f16_fast / launch_prep / launch_dkdv_pass (fa_bwd_f16_fast.hip), launch_bwd_f16_dq
 (fa_bwd_f16_dq.hip), bwd_aligned / with_pol_aln (fa_bwd_f16_parts.h), launch_bwd_f16_wide, launch_fwd_f32 /
 launch_bwd_f32, launch_fwd_f64 / launch_bwd_f64 and fa_generic.hip, for the variant "none"; the three split plans are
 asserted, in both directions."""
@@ -63,10 +62,10 @@ def _c(id, dtype, policy, d, vd, qs, ks, **kw):
 # bwd_dkdv_w4_kernel<POL, ALN> + bwd_dq_w4_kernel<POL, ALN>.  ALN = bwd_aligned: Q, K, V, dO 16-byte aligned and
 # nq % 8 == nk % 8 == 0; POL 0 full, 1 interval rules, 2 other windows.  "bwd ALN / elem" below names which.
 CASES = [
-    # fwd_f16_kernel<32, 4, POL 0, elem> (launch_t<32, 4, 8>: max(d, v_d) <= 32 is outside fwd_f16_fast_supported;
+    # fwd_f16_kernel<32, 4, POL 0, elem> (launch_t<32, 4, 8>: max(d, v_d) <= 32 is below the tuned kernels;
     # d != 32, so fast_staging declines); bwd elem, prep
     _c("f16-core-d32-full", F16, "full", 24, 20, 37, 75),
-    # fwd_f16_kernel<64, 8, POL 0, elem> (nk % 8 != 0: not fast_supported, not fast_staging); bwd elem, prep
+    # fwd_f16_kernel<64, 8, POL 0, elem> (nk % 8 != 0: not fwd_f16_tuned_operands, not fast_staging); bwd elem, prep
     _c("f16-core-d64-full-elem", F16, "full", 64, 64, 37, 77),
     # fwd_f16_kernel<128, 4, POL 1, elem>; bwd elem: bwd_dkdv_pc_kernel<128, 1, false> + bwd_dq_kernel<128, 4, 1, 1, false>
     _c("f16-core-d128-causal-elem", F16, "causal", 128, 128, 77, 77),
@@ -84,7 +83,7 @@ CASES = [
     _c("f16-band-local", F16, "local", 40, 64, 264, 264, ws=40),
     # the same kernel, causal window, nq != nk under scale_front
     _c("f16-band-local-causal", F16, "local", 64, 64, 264, 528, ws=40, causal=True, mode="scale_front"),
-    # fwd_f16_fast_kernel<64, 4, POL 1> (v_d = 48 != 64: fwd_f16_band_supported declines)
+    # fwd_f16_fast_kernel<64, 4, POL 1> (v_d = 48 != 64: fwd_f16_band_positions declines)
     _c("f16-4wave-d64-local", F16, "local", 64, 48, 264, 264, ws=40),
     # fwd_f16_gap128_kernel<0>; bwd ALN: bwd_dkdv_pc_kernel<128, 0, true> + bwd_dq_pc_kernel<128, 0, true>, prep8
     _c("f16-gap128-full", F16, "full", 96, 128, 72, 136),
@@ -127,8 +126,8 @@ CASES = [
     _c("f32-simt-d257", F32, "full", 257, 260, 33, 70),
     _c("f64-simt-d257", F64, "full", 257, 260, 33, 70),
 ]
-# The ping-pong fallback at 64 < d <= 128 (fa_fwd_f16_pingpong128.hip) is behind the gap-stream kernel in the product
-# library wherever both apply at small shapes: FA_FWD_VARIANT=2301 of the diagnostic library pins it.  Forward only.
+# The ping-pong kernel at 64 < d <= 128 (csrc/diag/fa_fwd_f16_pingpong128.hip) is a study: the gap-stream kernel takes
+# every shape it takes, so only the diagnostic library holds it, behind FA_FWD_VARIANT=2301.  Forward only.
 PINGPONG128 = _c("diag-2301-pingpong128", F16, "full", 128, 128, 72, 136)
 
 

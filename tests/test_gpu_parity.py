@@ -656,7 +656,7 @@ MANY_SLICE_CASES = {
     # fa_fwd_f16.hip launch_t<32, 4, 8> (max(d, v_d) <= 32 is never the fast forward) and the two-pass backward of
     # fa_bwd_f16_fast.hip, which takes every fp16 shape up to 256 channels
     "f16_general": (np.float16, "causal", 16, 16, (24,), (40,), 1),
-    # fa_fwd_f16_fast.hip launch_fast_t<64, 8, ...> at the smallest shape fwd_f16_fast_supported takes (more than 32
+    # fa_fwd_f16_fast.hip launch_fast_t<64, 8, ...> at the smallest shape the tuned kernels take (fwd_f16_choice) (more than 32
     # channels, nk % 8 == 0, an interval rule; causal, so not the full policy's ping-pong kernel) + the same backward
     "f16_fast": (np.float16, "causal", 40, 40, (16,), (8,), 1),
     # fa_fwd_f32.hip / fa_bwd_f32.hip launch_t<32>

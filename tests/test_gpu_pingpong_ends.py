@@ -32,7 +32,7 @@ KBM = 256    # queries per block
 
 
 def _assert_pingpong(policy, d, vd, nq, nk, b):
-    """The dispatcher's conditions for fwd_f16_pingpong_kernel (launch_fwd_f16_fast, fwd_f16_pingpong_supported)."""
+    """The dispatcher's conditions for fwd_f16_pingpong_kernel (fwd_f16_choice, csrc/fa_fwd_f16_choice.h)."""
     from tf_flash_attention_amd import _lib
     assert policy == "full"
     assert 32 < max(d, vd) <= 64

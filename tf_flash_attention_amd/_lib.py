@@ -79,6 +79,7 @@ EXPORTED_SYMBOLS = (
     "fa_build_info",
     "fa_rule_mask",
     "fa_rule_probe",
+    "fa_forward_kernel",
 )
 
 
@@ -229,6 +230,10 @@ def _declare(lib):
     lib.fa_rule_probe.argtypes = [P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                   ctypes.POINTER(ctypes.c_int32)]
     lib.fa_rule_probe.restype = ctypes.c_int
+    # (absent from a library built before the forward's choice function, as above)
+    if hasattr(lib, "fa_forward_kernel"):
+        lib.fa_forward_kernel.argtypes = [P, vp, vp, vp]
+        lib.fa_forward_kernel.restype = ctypes.c_char_p
     lib.fa_build_info.argtypes = []
     lib.fa_build_info.restype = ctypes.c_char_p
     # the diagnostic library only (libfa_hip_diag.so): calls that reached a launch (0 forward, 1 backward), and

@@ -30,6 +30,7 @@
 // relative to the stored fp16 m.  Replaces the reference's ForwardImpl (flash_attention.cu:425-1077)
 // for these shapes.
 #include "../fa_device.h"
+#include "../fa_fwd_f16_choice.h"
 #include "../fa_kernels.h"
 #include "../fa_mfma.h"
 
@@ -552,20 +553,12 @@ __global__ __launch_bounds__(kNW * 64, 1) void fwd_f16_gap_kernel(FwdArgs a) {
 
 }  // namespace
 
-// the full policy only (the headline): other rules go to the band, pingpong128 or fast kernels
-bool fwd_f16_gap_supported(const FwdArgs& a) {
-  const int nk = a.rule.k.n;
-  const int dm = max(a.d, a.v_d);
-  return a.rule.policy == 0 && dm > 32 && dm <= kD && (nk % 8 == 0) && nk > 0 && (int64_t)dm * nk * 2 < (1ll << 31) &&
-         (int64_t)dm * a.rule.q.n * 2 < (1ll << 31) && (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) &&
-         (reinterpret_cast<uintptr_t>(a.V) % 16 == 0) && a.b * ((a.rule.q.n + kBM - 1) / kBM) < (1ll << 31);
-}
-
-hipError_t launch_fwd_f16_gap(const FwdArgs& a, hipStream_t s) {
+// the full policy only (the headline): other rules go to the band, gap128 or fast kernels
+hipError_t launch_fwd_f16_gap(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
   const int64_t nqb = (a.rule.q.n + kBM - 1) / kBM;
   auto kern = fwd_f16_gap_kernel<0>;
 #ifdef FA_DIAG
-  switch (diag_variant("FA_FWD_VARIANT") - 2600) {  // timing ablations (outputs wrong)
+  switch (c.variant - 2600) {  // timing ablations (outputs wrong)
     case 1: kern = fwd_f16_gap_kernel<0, 1>; break;
     case 2: kern = fwd_f16_gap_kernel<0, 2>; break;
     case 4: kern = fwd_f16_gap_kernel<0, 4>; break;
@@ -576,10 +569,7 @@ hipError_t launch_fwd_f16_gap(const FwdArgs& a, hipStream_t s) {
     default: break;
   }
 #endif
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), kSmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * nqb)), dim3(kNW * 64), kSmem, s, a);
-  return hipGetLastError();
+  return launch_smem(kern, (unsigned)(a.b * nqb), kNW * 64, kSmem, s, a);
 }
 
 }  // namespace fa

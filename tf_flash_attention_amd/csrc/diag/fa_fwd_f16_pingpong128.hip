@@ -1,5 +1,7 @@
 // fa_fwd_f16_pingpong128.hip — the ping-pong fp16 forward (fa_fwd_f16_pingpong.hip) for
-// 64 < max(d, v_d) <= 128, full policy and interval rules.
+// 64 < max(d, v_d) <= 128, full policy and interval rules.  A study since the gap-stream kernel
+// (fa_fwd_f16_gap128.hip) takes every shape this one takes: diagnostic library only, FA_FWD_VARIANT 2301
+// (DESIGN.md §3.17).
 //
 // Same two-group structure: eight waves, waves w and w+4 share SIMD w, and every barrier
 // interval is an MFMA phase for one group and the softmax phase for the other.  At d = 128 the
@@ -34,9 +36,10 @@
 // with c&2, transposed reads with the key permutation; V: 16-B chunks XOR-swizzled by (c>>1)&7, b128
 // operand reads).  Numerics as fa_fwd_f16.hip.  Replaces the reference's ForwardImpl
 // (flash_attention.cu:425-1077) for these shapes.
-#include "fa_device.h"
-#include "fa_kernels.h"
-#include "fa_mfma.h"
+#include "../fa_device.h"
+#include "../fa_fwd_f16_choice.h"
+#include "../fa_kernels.h"
+#include "../fa_mfma.h"
 
 namespace fa {
 namespace {
@@ -449,22 +452,10 @@ __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong128_kernel(FwdArg
 
 }  // namespace
 
-bool fwd_f16_pingpong128_supported(const FwdArgs& a) {
-  const int nk = a.rule.k.n;
-  const int dm = max(a.d, a.v_d);
-  return dm > 64 && dm <= kD && (nk % 8 == 0) && nk > 0 && (int64_t)dm * nk * 2 < (1ll << 31) &&
-         (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) && (reinterpret_cast<uintptr_t>(a.V) % 16 == 0) &&
-         rule_is_interval(a.rule) && a.b * ((a.rule.q.n + kBM - 1) / kBM) < (1ll << 31);
-}
-
-hipError_t launch_fwd_f16_pingpong128(const FwdArgs& a, hipStream_t s) {
+hipError_t launch_fwd_f16_pingpong128(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
   const int64_t nqb = (a.rule.q.n + kBM - 1) / kBM;
-  const int pol = a.rule.policy == 0 ? 0 : 1;
-  auto kern = pol == 0 ? fwd_f16_pingpong128_kernel<0> : fwd_f16_pingpong128_kernel<1>;
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), kSmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * pp128_groups(nqb, pol))), dim3(kNW * 64), kSmem, s, a);
-  return hipGetLastError();
+  auto kern = c.pol == 0 ? fwd_f16_pingpong128_kernel<0> : fwd_f16_pingpong128_kernel<1>;
+  return launch_smem(kern, (unsigned)(a.b * pp128_groups(nqb, c.pol)), kNW * 64, kSmem, s, a);
 }
 
 }  // namespace fa

@@ -34,6 +34,7 @@
 // log2-domain lazy rebase with threshold 8, l relative to the stored fp16 m).
 // Replaces the reference's ForwardImpl (flash_attention.cu:425-1077) for these shapes.
 #include "../fa_device.h"
+#include "../fa_fwd_f16_choice.h"
 #include "../fa_kernels.h"
 #include "../fa_mfma.h"
 
@@ -486,18 +487,10 @@ __global__ __launch_bounds__(kNW * 64, 1) void fwd_f16_pp_kernel(FwdArgs a) {
 
 }  // namespace
 
-bool fwd_f16_pp_supported(const FwdArgs& a) {
-  const int nk = a.rule.k.n;
-  const int dm = max(a.d, a.v_d);
-  return dm > 32 && dm <= kD && (nk % 8 == 0) && nk > 0 && (int64_t)dm * nk * 2 < (1ll << 31) &&
-         (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) && (reinterpret_cast<uintptr_t>(a.V) % 16 == 0) &&
-         rule_is_interval(a.rule) && a.b * ((a.rule.q.n + kBM - 1) / kBM) < (1ll << 31);
-}
-
-hipError_t launch_fwd_f16_pp(const FwdArgs& a, hipStream_t s) {
+hipError_t launch_fwd_f16_pp(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
   const int64_t nqb = (a.rule.q.n + kBM - 1) / kBM;
-  auto kern = a.rule.policy == 0 ? fwd_f16_pp_kernel<0> : fwd_f16_pp_kernel<1>;
-  switch (diag_variant("FA_FWD_VARIANT") - 2100) {  // ablations, full policy only (timing diagnostics)
+  auto kern = c.pol == 0 ? fwd_f16_pp_kernel<0> : fwd_f16_pp_kernel<1>;
+  switch (c.variant - 2100) {  // ablations, full policy only (timing diagnostics)
     case 1: kern = fwd_f16_pp_kernel<0, 1>; break;
     case 2: kern = fwd_f16_pp_kernel<0, 2>; break;
     case 3: kern = fwd_f16_pp_kernel<0, 3>; break;
@@ -514,11 +507,7 @@ hipError_t launch_fwd_f16_pp(const FwdArgs& a, hipStream_t s) {
     case 96: kern = fwd_f16_pp_kernel<0, 96>; break;
     default: break;
   }
-  hipError_t e =
-      set_smem_once(reinterpret_cast<const void*>(kern), kSmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * nqb)), dim3(kNW * 64), kSmem, s, a);
-  return hipGetLastError();
+  return launch_smem(kern, (unsigned)(a.b * nqb), kNW * 64, kSmem, s, a);
 }
 
 }  // namespace fa

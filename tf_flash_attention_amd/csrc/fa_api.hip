@@ -16,12 +16,14 @@
 
 #include <atomic>
 #include <mutex>
+#include <set>
 #include <shared_mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/fa_api.h"
 #include "fa_device.h"
+#include "fa_fwd_f16_choice.h"
 #include "fa_kernels.h"
 #include "fa_rules.h"
 
@@ -682,6 +684,18 @@ long long fa_diag_slab_count(void) { return g_diag_slabs.load(); }
 static const char kGenericUnsupported[] =
     "no kernel takes this shape: more than 65536 channels, or a launch grid of 2^31 workgroups or more";
 
+// the kernel family of a forward call that launches something, and for fp16 the kernel (fa_fwd_f16_choice.h):
+// what fa_forward launches and fa_forward_kernel names
+enum class FwdFamily { kNone, kF16, kF32, kF64, kGeneric };
+
+static FwdFamily forward_family(const fa_problem* p, const fa::FwdArgs& a, fa::FwdF16Choice* f16) {
+  const bool mfma = !FA_DIAG_SIMT("FA_FWD_VARIANT");
+  if (mfma && p->dtype == FA_F16 && (*f16 = fa::choose_fwd_f16(a)).kernel != fa::FwdF16::kNone) return FwdFamily::kF16;
+  if (mfma && p->dtype == FA_F32 && fa::fwd_f32_supported(a)) return FwdFamily::kF32;
+  if (mfma && p->dtype == FA_F64 && fa::fwd_f64_supported(a)) return FwdFamily::kF64;
+  return fa::fwd_generic_supported(p->dtype, a) ? FwdFamily::kGeneric : FwdFamily::kNone;
+}
+
 int fa_forward(void* stream, const fa_problem* p, const void* Q, const void* K, const void* V, void* O, void* l,
                void* m) {
   int st = fa_validate(p);
@@ -692,22 +706,39 @@ int fa_forward(void* stream, const fa_problem* p, const void* Q, const void* K, 
   fill_problem(p, &a);
   if (a.b == 0 || a.rule.q.n == 0) return FA_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool mfma = !FA_DIAG_SIMT("FA_FWD_VARIANT");
+  fa::FwdF16Choice f16;
   hipError_t e;
-  if (mfma && p->dtype == FA_F16 && fa::fwd_f16_supported(a)) {
-    e = fa::launch_fwd_f16(a, s);
-  } else if (mfma && p->dtype == FA_F32 && fa::fwd_f32_supported(a)) {
-    e = fa::launch_fwd_f32(a, s);
-  } else if (mfma && p->dtype == FA_F64 && fa::fwd_f64_supported(a)) {
-    e = fa::launch_fwd_f64(a, s);
-  } else if (fa::fwd_generic_supported(p->dtype, a)) {
-    e = fa::launch_fwd_generic(p->dtype, a, s);
-  } else {
-    return set_error(FA_ERR_UNSUPPORTED, kGenericUnsupported);
+  switch (forward_family(p, a, &f16)) {
+    case FwdFamily::kF16: e = fa::launch_fwd_f16(a, f16, s); break;
+    case FwdFamily::kF32: e = fa::launch_fwd_f32(a, s); break;
+    case FwdFamily::kF64: e = fa::launch_fwd_f64(a, s); break;
+    case FwdFamily::kGeneric: e = fa::launch_fwd_generic(p->dtype, a, s); break;
+    default: return set_error(FA_ERR_UNSUPPORTED, kGenericUnsupported);
   }
   if (e != hipSuccess)
     return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
   return FA_OK;
+}
+
+const char* fa_forward_kernel(const fa_problem* p, const void* Q, const void* K, const void* V) {
+  if (fa_validate(p) != FA_OK) return "none";
+  fa::FwdArgs a;
+  a.Q = Q; a.K = K; a.V = V; a.O = nullptr; a.l = nullptr; a.m = nullptr;
+  fill_problem(p, &a);
+  if (a.b == 0 || a.rule.q.n == 0) return "none";
+  fa::FwdF16Choice f16;
+  switch (forward_family(p, a, &f16)) {
+    case FwdFamily::kF16: break;
+    case FwdFamily::kF32: return "fwd_f32";
+    case FwdFamily::kF64: return "fwd_f64";
+    case FwdFamily::kGeneric: return "fwd_generic";
+    default: return "none";
+  }
+  // one copy of every name handed out, kept for the life of the library
+  static std::mutex mu;
+  static std::set<std::string> names;
+  std::lock_guard<std::mutex> lock(mu);
+  return names.insert(fa::fwd_f16_choice_name(f16)).first->c_str();
 }
 
 size_t fa_forward_workspace_bytes(const fa_problem* p) {

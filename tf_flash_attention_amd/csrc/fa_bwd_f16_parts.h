@@ -312,14 +312,7 @@ auto with_pol_aln(const BwdArgs& a, Pick&& pick) {
   return bwd_aligned(a) ? (pol == 0 ? pick(IC<0>{}, T{}) : pol == 1 ? pick(IC<1>{}, T{}) : pick(IC<2>{}, T{}))
                         : (pol == 0 ? pick(IC<0>{}, F{}) : pol == 1 ? pick(IC<1>{}, F{}) : pick(IC<2>{}, F{}));
 }
-// one launch with `bytes` of dynamic LDS (above the default limit: set once per kernel)
-template <class Args>
-hipError_t launch_smem(void (*kern)(Args), unsigned grid, unsigned block, int bytes, hipStream_t s, const Args& args) {
-  const hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), bytes, s, args);
-  return hipGetLastError();
-}
+// (the launch of a picked kernel: launch_smem, fa_device.h)
 
 }  // namespace bwdp
 

@@ -57,6 +57,14 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nwg) {
 // host: hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), thread-safe
 // (fa_api.hip); later launches of the same kernel on the same device skip the runtime call
 hipError_t set_smem_once(const void* kern, int bytes);
+// host: one launch with `bytes` of dynamic LDS (above the default limit: set once per kernel)
+template <class Args>
+hipError_t launch_smem(void (*kern)(Args), unsigned grid, unsigned block, int bytes, hipStream_t s, const Args& args) {
+  const hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), bytes, s, args);
+  return hipGetLastError();
+}
 
 // host: compute units of the current device, cached per device id (fa_api.hip; thread-safe).
 // Persistent grids size themselves from it.

@@ -11,8 +11,8 @@
 // The key loop itself (staging, transposed scores on MFMA, log2-domain online
 // softmax, tile classes, the three POL forms) is fwd_f16_core in
 // fa_fwd_f16_core.h, shared with the split-key forward; this file maps a block
-// to its query rows and key range, normalises and writes O, l, m, and chooses
-// the instantiation.
+// to its query rows and key range, normalises and writes O, l, m, and launches the kernel that the choice
+// (fa_fwd_f16_choice.h) names: its own instances here, the tuned kernels through their files' launchers.
 #include "fa_fwd_f16_core.h"
 
 #include <stdlib.h>
@@ -66,63 +66,65 @@ __global__ __launch_bounds__(NW * 64, waves_per_eu(D, F)) void fwd_f16_kernel(Fw
 }
 
 template <int D, int NW, int F>
-hipError_t launch_t(const FwdArgs& a, hipStream_t s) {
-  return with_pol_fast<D>(a, [&](auto pol, auto fast) {
+hipError_t launch_t(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
+  return with_pol_fast(c.pol, c.aligned, [&](auto pol, auto fast) {
     auto kern = fwd_f16_kernel<D, NW, decltype(pol)::value, decltype(fast)::value != 0, F>;
     const int64_t nqb = (a.rule.q.n + Smem<D, NW>::kBM - 1) / Smem<D, NW>::kBM;
-    const int smem = Smem<D, NW>::kTotal;
-    hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), smem);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * nqb)), dim3(NW * 64), smem, s, a);
-    return hipGetLastError();
+    return launch_smem(kern, (unsigned)(a.b * nqb), NW * 64, Smem<D, NW>::kTotal, s, a);
   });
+}
+
+// the instance <D, NW, F> of a kGeneral choice
+constexpr int inst(int d, int nw, int f) { return (d * 16 + nw) * 128 + f; }
+
+hipError_t launch_general(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
+  switch (inst(c.d, c.nw, c.f)) {
+    case inst(32, 4, 8): return launch_t<32, 4, 8>(a, c, s);
+    case inst(64, 4, 8): return launch_t<64, 4, 8>(a, c, s);
+    case inst(64, 8, 8): return launch_t<64, 8, 8>(a, c, s);
+    case inst(128, 4, 8): return launch_t<128, 4, 8>(a, c, s);
+#ifdef FA_DIAG
+    // the pins below 1000: at d <= 32 dot2c row sums (the round-3 default) against MFMA row sums
+    case inst(32, 4, 8 | kFMfmaSum): return launch_t<32, 4, 8 | kFMfmaSum>(a, c, s);
+    case inst(32, 8, 8): return launch_t<32, 8, 8>(a, c, s);
+    case inst(32, 8, 8 | kFMfmaSum): return launch_t<32, 8, 8 | kFMfmaSum>(a, c, s);
+    case inst(64, 4, 0): return launch_t<64, 4, 0>(a, c, s);
+    case inst(64, 4, 24): return launch_t<64, 4, 24>(a, c, s);
+    case inst(64, 4, 56): return launch_t<64, 4, 56>(a, c, s);
+    case inst(64, 8, 0): return launch_t<64, 8, 0>(a, c, s);
+    case inst(64, 8, 40): return launch_t<64, 8, 40>(a, c, s);
+#endif
+    default: return hipErrorInvalidValue;  // no such instance is chosen
+  }
 }
 
 }  // namespace
 
-bool fwd_f16_supported(const FwdArgs& a) {
-  if (fwd_f16_wide_supported(a)) return true;
-  return a.d >= 1 && a.v_d >= 1 && a.d <= 128 && a.v_d <= 128 && a.b * ((a.rule.q.n + 127) / 128) < (1ll << 31);
+FwdF16Choice choose_fwd_f16(const FwdArgs& a) {
+#ifdef FA_DIAG
+  const int variant = diag_variant("FA_FWD_VARIANT");
+#else
+  constexpr int variant = -1;
+#endif
+  // only the band's conditions, for local windows, read the XCD count
+  return fwd_f16_choice(a, a.rule.policy == 2 ? device_xcds() : 0, variant);
 }
 
-hipError_t launch_fwd_f16(const FwdArgs& a, hipStream_t s) {
-  const int dm = max(a.d, a.v_d);
-  // 128 < max(d, v_d) <= 256, every rule and alignment: 256-channel MFMA tiles (fa_fwd_f16_wide.hip)
-  if (dm > 128) return launch_fwd_f16_wide(a, s);
+hipError_t launch_fwd_f16(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
+  switch (c.kernel) {
+    case FwdF16::kWide: return launch_fwd_f16_wide(a, c, s);
+    case FwdF16::kBand: return launch_fwd_f16_band(a, c, s);
+    case FwdF16::kPingpong: return launch_fwd_f16_pingpong(a, c, s);
+    case FwdF16::kGap128: return launch_fwd_f16_gap128(a, c, s);
+    case FwdF16::kFast: return launch_fwd_f16_fast(a, c, s);
+    case FwdF16::kGeneral: return launch_general(a, c, s);
 #ifdef FA_DIAG
-  // FA_FWD_VARIANT = <NW><F> below 1000 pins this general kernel (A/B runs), e.g. 408
-  const int v = diag_variant("FA_FWD_VARIANT");
-  if (v >= 0 && v < 1000 && dm <= 32) {  // d <= 32: 308 dot2c row sums (the round-3 default), 372 MFMA row sums
-    if (v == 308) return launch_t<32, 4, 8>(a, s);
-    if (v == 372) return launch_t<32, 4, 8 | kFMfmaSum>(a, s);
-    if (v == 808) return launch_t<32, 8, 8>(a, s);
-    if (v == 872) return launch_t<32, 8, 8 | kFMfmaSum>(a, s);
-  }
-  if (v >= 0 && v < 1000 && dm > 32 && dm <= 64) {
-    switch (v) {
-      case 400: return launch_t<64, 4, 0>(a, s);
-      case 408: return launch_t<64, 4, 8>(a, s);
-      case 424: return launch_t<64, 4, 24>(a, s);
-      case 456: return launch_t<64, 4, 56>(a, s);
-      case 800: return launch_t<64, 8, 0>(a, s);
-      case 808: return launch_t<64, 8, 8>(a, s);
-      case 840: return launch_t<64, 8, 40>(a, s);
-      default: break;
-    }
-  }
-  const bool pinned = v >= 0 && v < 1000;
-#else
-  constexpr bool pinned = false;
+    case FwdF16::kPp: return launch_fwd_f16_pp(a, c, s);
+    case FwdF16::kGap: return launch_fwd_f16_gap(a, c, s);
+    case FwdF16::kPingpong128: return launch_fwd_f16_pingpong128(a, c, s);
 #endif
-  if (!pinned && fwd_f16_fast_supported(a)) return launch_fwd_f16_fast(a, s);
-  if (dm <= 32) return launch_t<32, 4, 8>(a, s);
-  if (dm <= 64) {
-    // local bands: ~10 key tiles per block, so block prologue/epilogue matter;
-    // 4-wave blocks let two blocks per CU cover each other's (c4: 5.2 vs 5.9 ms)
-    if (a.rule.policy == 2) return launch_t<64, 4, 8>(a, s);
-    return launch_t<64, 8, 8>(a, s);
+    default: return hipErrorInvalidValue;  // kNone, or a study in the product library: never chosen
   }
-  return launch_t<128, 4, 8>(a, s);
 }
 
 }  // namespace fa

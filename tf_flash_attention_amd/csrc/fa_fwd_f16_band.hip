@@ -42,6 +42,7 @@
 // two positions ahead, LDS-DMA staging, packed edge-mask bounds, a hand-ordered softmax stream) and
 // the stamp / ablation builds were taken out in round 5; their numbers are in DESIGN.md §3.0c, §6.
 #include "fa_device.h"
+#include "fa_fwd_f16_choice.h"
 #include "fa_kernels.h"
 #include "fa_mfma.h"
 
@@ -854,43 +855,39 @@ int band_positions_stag(const FwdArgs& a) {
   return T;
 }
 
-bool fwd_f16_band_supported(const FwdArgs& a) {
+// What the band asks beyond the tuned kernels' common conditions (fwd_f16_tuned_operands, which the choice has
+// already put to these arguments): a 1d unit-stride window of few tiles a block, v_d = 64, vector Q reads
+int fwd_f16_band_positions(const FwdArgs& a, int xcds) {
   const Rule& r = a.rule;
   const int nq = r.q.n, nk = r.k.n;
   const int dm = max(a.d, a.v_d);
-  if (!(r.policy == 2 && r.seq_dims == 1 && r.ls == 0)) return false;
+  if (!(r.policy == 2 && r.seq_dims == 1 && r.ls == 0)) return 0;
   // v_d == 64: the epilogue's per-value buffer stores need no channel predicate (a predicated
   // form keeps 32 lane-dependent 64-bit offsets live across the stream: 116 spilled VGPRs)
-  if (!(a.v_d == kD && a.d > 32 && a.d <= kD && nk % 8 == 0 && nk > 0 && nq > 0)) return false;
-  if ((int64_t)dm * nk * 2 >= (1ll << 31) || (int64_t)dm * nq * 2 >= (1ll << 31)) return false;
-  if ((reinterpret_cast<uintptr_t>(a.K) % 16) || (reinterpret_cast<uintptr_t>(a.V) % 16) ||
-      (reinterpret_cast<uintptr_t>(a.Q) % 16) || nq % 8)
-    return false;
-  // a band: every block spans few tiles (else the per-launch kernels cover it at no loss)
-  if (band_positions_stag(a) > kMaxT) return false;
+  if (!(a.v_d == kD && a.d > 32 && a.d <= kD && nq > 0)) return 0;
+  if ((reinterpret_cast<uintptr_t>(a.Q) % 16) || nq % 8) return 0;
   // the per-slice table of first key tiles lives in LDS: kMaxTab query blocks (nq <= 1M)
-  if ((nq + kBM - 1) / kBM > kMaxTab) return false;
-  // one descriptor per tensor spans a workgroup's slices: below 2^31 bytes
+  if ((nq + kBM - 1) / kBM > kMaxTab) return 0;
+  // a band: every block spans few tiles (else the per-launch kernels cover it at no loss)
+  const int T = band_positions_stag(a);
+  if (T > kMaxT) return 0;
+  // one descriptor per tensor spans a workgroup's slices: below 2^31 bytes.  (The walk's item arithmetic is
+  // 32-bit: the common conditions hold the count of 128-query blocks below 2^31, and an item is two of them)
   const int64_t nqb = (nq + kBM - 1) / kBM, n_items = a.b * nqb, n_wg = band_workgroups(n_items);
-  if (n_items >= (1ll << 31)) return false;  // the walk's item arithmetic is 32-bit
-  const int xcds = device_xcds();
   const int64_t span =
       (band_interleaved(n_items, n_wg, xcds) ? (n_items + xcds - 1) / xcds : (n_items + n_wg - 1) / n_wg) / nqb + 2;
-  return span * 2 * (int64_t)dm * (nq > nk ? nq : nk) < (1ll << 31);
+  return span * 2 * (int64_t)dm * (nq > nk ? nq : nk) < (1ll << 31) ? T : 0;
 }
 
 template <int T>
 hipError_t launch_band_t(const BandArgs& ba, hipStream_t s) {
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(fwd_f16_band_kernel<T>), kSmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((fwd_f16_band_kernel<T>), dim3((unsigned)ba.n_wg), dim3(kNW * 64), kSmem, s, ba);
-  return hipGetLastError();
+  return launch_smem(fwd_f16_band_kernel<T>, (unsigned)ba.n_wg, kNW * 64, kSmem, s, ba);
 }
 
-hipError_t launch_fwd_f16_band(const FwdArgs& a, hipStream_t s) {
+hipError_t launch_fwd_f16_band(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
   BandArgs ba;
   ba.a = a;
-  ba.T = band_positions_stag(a);
+  ba.T = c.f;
   ba.n_items = a.b * (int64_t)((a.rule.q.n + kBM - 1) / kBM);
   ba.n_wg = (int)band_workgroups(ba.n_items);
   ba.n_xcd = device_xcds();
@@ -898,7 +895,7 @@ hipError_t launch_fwd_f16_band(const FwdArgs& a, hipStream_t s) {
 #ifdef FA_DIAG
   // FA_FWD_VARIANT=2402: the round-2 item order (contiguous runs of items per workgroup), for the
   // L2-traffic comparison of DESIGN.md §3.0c
-  if (diag_variant("FA_FWD_VARIANT") == 2402) ba.inter = 0;
+  if (c.variant == 2402) ba.inter = 0;
 #endif
   switch (ba.T) {
     case 9: return launch_band_t<9>(ba, s);

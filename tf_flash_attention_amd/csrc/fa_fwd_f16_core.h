@@ -41,6 +41,7 @@
 #define TF_FLASH_ATTENTION_AMD_FA_FWD_F16_CORE_H_
 
 #include "fa_device.h"
+#include "fa_fwd_f16_choice.h"
 #include "fa_kernels.h"
 #include "fa_mfma.h"
 
@@ -600,13 +601,15 @@ bool fast_staging(const FwdArgs& a, int row_keys, int chunk_bytes = 16) {
 
 // host: the <POL, FAST> instantiation these arguments take at channel tile D.  `launch(pol, fast)`
 // receives them as IC<POL> and IC<FAST> (types, so they can be template arguments).
-template <int D, class Launch>
-hipError_t with_pol_fast(const FwdArgs& a, Launch&& launch) {
-  const bool fast = fast_staging<D>(a, a.rule.k.n);
-  const int pol = a.rule.policy == 0 ? 0 : (rule_is_interval(a.rule) ? 1 : 2);
+template <class Launch>
+hipError_t with_pol_fast(int pol, bool fast, Launch&& launch) {
   return pol == 0 ? (fast ? launch(IC<0>{}, IC<1>{}) : launch(IC<0>{}, IC<0>{}))
        : pol == 1 ? (fast ? launch(IC<1>{}, IC<1>{}) : launch(IC<1>{}, IC<0>{}))
                   : (fast ? launch(IC<2>{}, IC<1>{}) : launch(IC<2>{}, IC<0>{}));
+}
+template <int D, class Launch>
+hipError_t with_pol_fast(const FwdArgs& a, Launch&& launch) {
+  return with_pol_fast(fwd_f16_pol(a.rule), fast_staging<D>(a, a.rule.k.n), launch);
 }
 
 }  // namespace f16core

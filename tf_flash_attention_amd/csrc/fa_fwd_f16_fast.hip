@@ -1,7 +1,10 @@
 // fa_fwd_f16_fast.hip — fp16 fused attention forward, streamlined main loop for
 // the common shapes (32 < max(d, v_d) <= 128, channels zero-padded to D ∈ {64, 128};
-// K/V rows 16-byte aligned, nk % 8 == 0) under the full policy and the interval
-// rules (causal, 1d unit-stride local).
+// K/V rows 16-byte aligned, nk % 8 == 0) under the interval rules (causal, 1d
+// unit-stride local) that no other tuned kernel takes: causal at d <= 64, local windows
+// the band kernel declines, local windows at 64 < d <= 128 (fa_fwd_f16_choice.h).  The
+// full policy goes to the ping-pong and gap-stream kernels; its POL = 0 form of this
+// kernel is built into the diagnostic library only.
 //
 // Same algorithm and operand layouts as fa_fwd_f16.hip (which remains the path
 // for every other shape and for strided / 2d local rules); what differs is how
@@ -23,6 +26,7 @@
 // shapes; numerics (fp32 accumulation, lazy log2-domain rescale, l relative to
 // the stored fp16 m) are identical to fa_fwd_f16.hip.
 #include "fa_device.h"
+#include "fa_fwd_f16_choice.h"
 #include "fa_kernels.h"
 #include "fa_mfma.h"
 
@@ -449,68 +453,28 @@ __global__ __launch_bounds__(NW * 64, fast_waves_per_eu(D)) void fwd_f16_fast_ke
   }
 }
 
+static_assert(kFastF1 == (kFPrio | kFLateV) && kFastF2 == (kFPrio | kFLateV | kFTpb2), "the choice's F values");
+
+// The full policy never comes here without a pin: it goes to the ping-pong kernel at d <= 64 and to the
+// gap-stream kernel above, so POL = 0 exists in the diagnostic library only (1814, 146)
 template <int D, int NW, int F>
-hipError_t launch_fast_t(const FwdArgs& a, hipStream_t s) {
+hipError_t launch_fast_t(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
   using S = FastSmem<D, NW, (F & kFTpb2) ? 2 : 1>;
   const int64_t nqb = (a.rule.q.n + S::kBM - 1) / S::kBM;
-  const int smem = S::kTotal;
-  auto kern = a.rule.policy == 0 ? fwd_f16_fast_kernel<D, NW, 0, F> : fwd_f16_fast_kernel<D, NW, 1, F>;
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), smem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * nqb)), dim3(NW * 64), smem, s, a);
-  return hipGetLastError();
+  auto kern = fwd_f16_fast_kernel<D, NW, 1, F>;
+#ifdef FA_DIAG
+  if (c.pol == 0) kern = fwd_f16_fast_kernel<D, NW, 0, F>;
+#else
+  if (c.pol == 0) return hipErrorInvalidValue;
+#endif
+  return launch_smem(kern, (unsigned)(a.b * nqb), NW * 64, S::kTotal, s, a);
 }
 
 }  // namespace
 
-bool fwd_f16_fast_supported(const FwdArgs& a) {
-  const int nk = a.rule.k.n;
-  const int dm = max(a.d, a.v_d);
-  return dm > 32 && dm <= 128 && (nk % 8 == 0) && nk > 0 &&
-         (int64_t)dm * nk * 2 < (1ll << 31) && (int64_t)dm * a.rule.q.n * 2 < (1ll << 31) &&
-         (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) && (reinterpret_cast<uintptr_t>(a.V) % 16 == 0) &&
-         rule_is_interval(a.rule) && a.b * ((a.rule.q.n + 127) / 128) < (1ll << 31);
-}
-
-hipError_t launch_fwd_f16_fast(const FwdArgs& a, hipStream_t s) {
-  const bool d64 = max(a.d, a.v_d) <= 64;
-#ifdef FA_DIAG
-  // FA_FWD_VARIANT forces one of the shipped structures onto a shape the dispatcher would send
-  // elsewhere (parity coverage of every rule each accepts): 1814 / 146 the 8-wave / 4-wave
-  // instances below, 2200 / 2301 the ping-pong kernels, 2000 the paired-block study (csrc/diag/)
-  const int v = diag_variant("FA_FWD_VARIANT");
-  if (fwd_f16_pp_supported(a) && v >= 2000 && v < 2200) return launch_fwd_f16_pp(a, s);  // 21xx: its ablations
-  if (fwd_f16_pingpong_supported(a) && v == 2200) return launch_fwd_f16_pingpong(a, s);
-  if (fwd_f16_gap_supported(a) && v >= 2600 && v < 2700) return launch_fwd_f16_gap(a, s);  // 26xx: its ablations
-  if (fwd_f16_gap128_supported(a) && v >= 2700 && v < 2800) return launch_fwd_f16_gap128(a, s);
-  if (fwd_f16_pingpong128_supported(a) && v == 2301) return launch_fwd_f16_pingpong128(a, s);
-  if (d64 && v == 1814) return launch_fast_t<64, 8, kFPrio | kFLateV | kFTpb2>(a, s);
-  if (v == 146) return d64 ? launch_fast_t<64, 4, kFPrio | kFLateV>(a, s) : launch_fast_t<128, 4, kFPrio | kFLateV>(a, s);
-  const bool tuned = v < 0;
-  if (v >= 2400 && v < 2500 && fwd_f16_band_supported(a)) return launch_fwd_f16_band(a, s);
-#else
-  constexpr bool tuned = true;
-#endif
-  // 1d local windows at d <= 64: the persistent band kernel (no per-block start / end cost)
-  if (tuned && fwd_f16_band_supported(a)) return launch_fwd_f16_band(a, s);
-  // ping-pong kernel (two wave groups alternating MFMA / softmax phases): the default for
-  // d <= 64 under the full policy (c2: 948 vs 904 TF/s for the 8-wave kernel below)
-  if (tuned && a.rule.policy == 0 && fwd_f16_pingpong_supported(a)) return launch_fwd_f16_pingpong(a, s);
-  // d in (64, 128], full and causal policies: the one-wave gap-stream kernel (c3 forward 2.29 against
-  // 2.40 ms for the ping-pong below, full policy at c3's shape 3.95 against 4.34: DESIGN.md §3.0b), then the
-  // ping-pong (c3 forward: 2.52 vs 3.16 ms for the 4-wave kernel below) where it does not fit; local windows
-  // keep the 4-wave blocks
-  if (tuned && a.rule.policy != 2 && fwd_f16_gap128_supported(a)) return launch_fwd_f16_gap128(a, s);
-  if (tuned && a.rule.policy != 2 && fwd_f16_pingpong128_supported(a)) return launch_fwd_f16_pingpong128(a, s);
-  if (d64) {
-    // tuned on MI355X: full-length key loops 8 waves x 32 queries, two key tiles per barrier;
-    // rule-bounded short loops (local windows, c4) 4-wave blocks with one tile per barrier
-    // (48 KB of LDS) so two blocks per CU cover each other's prologue / epilogue
-    if (a.rule.policy == 2) return launch_fast_t<64, 4, kFPrio | kFLateV>(a, s);
-    return launch_fast_t<64, 8, kFPrio | kFLateV | kFTpb2>(a, s);
-  }
-  // tuned (c3 forward, MI355X): 4 waves (one per SIMD), static priority, late V reads
-  return launch_fast_t<128, 4, kFPrio | kFLateV>(a, s);
+hipError_t launch_fwd_f16_fast(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
+  if (c.d == 128) return launch_fast_t<128, 4, kFastF1>(a, c, s);
+  return c.nw == 4 ? launch_fast_t<64, 4, kFastF1>(a, c, s) : launch_fast_t<64, 8, kFastF2>(a, c, s);
 }
 
 }  // namespace fa

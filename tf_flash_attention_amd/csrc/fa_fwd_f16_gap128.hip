@@ -7,7 +7,7 @@
 // channel quarters), so one P dword fills two gaps (one v_exp_f32 a gap: inside the <= 5 fillers / one
 // 8-cycle instruction a 32x32x16 gap hides, MI355X_MICROARCH.md 'one wave per SIMD'); and a wave's 64
 // queries read each K / V fragment once for two query blocks, half the LDS bytes per MFMA of the two-wave
-// ping-pong (fa_fwd_f16_pingpong128.hip), whose MFMA phase is LDS-bound.
+// ping-pong (diag/fa_fwd_f16_pingpong128.hip), whose MFMA phase is LDS-bound.
 //
 //   segment A of step i : Sᵀ A(i+1) (16 MFMAs), PV A(i) (16)  |  softmax B(i), row sums of P_B(i-1)
 //   segment B of step i : Sᵀ B(i+1) (16 MFMAs), PV B(i) (16)  |  softmax A(i+1), row sums of P_A(i)
@@ -30,11 +30,12 @@
 // K(i+4) / V(i+2) in the four lightest gaps of each segment (28-31).  One barrier a step.
 //
 // Rules: the full policy and interval rules (causal, 1d local), with the heavy / light block pairing of
-// fa_fwd_f16_pingpong128.hip.  Numerics as fa_fwd_f16_gap.hip.  Replaces the reference's ForwardImpl
+// diag/fa_fwd_f16_pingpong128.hip.  Numerics as fa_fwd_f16_gap.hip.  Replaces the reference's ForwardImpl
 // (flash_attention.cu:425-1077) for these shapes: the default for the full and causal policies at
 // 64 < max(d, v_d) <= 128 (config 3's forward; FA_FWD_VARIANT 2700 / 2701 force it / its other layout in the
 // diagnostic library).
 #include "fa_device.h"
+#include "fa_fwd_f16_choice.h"
 #include "fa_kernels.h"
 #include "fa_mfma.h"
 
@@ -671,26 +672,14 @@ __global__ __launch_bounds__(kNW * 64, 1) void fwd_f16_gap128_kernel(FwdArgs a) 
 
 }  // namespace
 
-bool fwd_f16_gap128_supported(const FwdArgs& a) {
-  const int nk = a.rule.k.n;
-  const int dm = max(a.d, a.v_d);
-  return dm > 64 && dm <= kD && (nk % 8 == 0) && nk > 0 && (int64_t)dm * nk * 2 < (1ll << 31) &&
-         (int64_t)dm * a.rule.q.n * 2 < (1ll << 31) && (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) &&
-         (reinterpret_cast<uintptr_t>(a.V) % 16 == 0) && (a.rule.policy == 0 || rule_is_interval(a.rule)) &&
-         a.b * ((a.rule.q.n + kBM - 1) / kBM) < (1ll << 31);
-}
-
-hipError_t launch_fwd_f16_gap128(const FwdArgs& a, hipStream_t s) {
+hipError_t launch_fwd_f16_gap128(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
   const int64_t nqb = (a.rule.q.n + kBM - 1) / kBM;
-  const int pol = a.rule.policy == 0 ? 0 : 1;
+  const int pol = c.pol;
   auto kern = pol == 0 ? fwd_f16_gap128_kernel<0> : fwd_f16_gap128_kernel<1>;
 #ifdef FA_DIAG
-  if (diag_variant("FA_FWD_VARIANT") == 2701) kern = pol == 0 ? fwd_f16_gap128_kernel<0, 1> : fwd_f16_gap128_kernel<1, 1>;
+  if (c.f == 1) kern = pol == 0 ? fwd_f16_gap128_kernel<0, 1> : fwd_f16_gap128_kernel<1, 1>;
 #endif
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), kSmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * gap128_groups(nqb, pol))), dim3(kNW * 64), kSmem, s, a);
-  return hipGetLastError();
+  return launch_smem(kern, (unsigned)(a.b * gap128_groups(nqb, pol)), kNW * 64, kSmem, s, a);
 }
 
 }  // namespace fa

@@ -40,6 +40,7 @@
 // interval-rule instance) and the stamp / ablation builds were taken out in round 5; their
 // measurements are in DESIGN.md §3.0 and §6.
 #include "fa_device.h"
+#include "fa_fwd_f16_choice.h"
 #include "fa_kernels.h"
 #include "fa_mfma.h"
 
@@ -476,26 +477,15 @@ __global__ __launch_bounds__(kNW * 64, 2) void fwd_f16_pingpong_kernel(FwdArgs a
 
 }  // namespace
 
-// the full policy only: every other rule goes to the band, pingpong128 or fast kernels
-bool fwd_f16_pingpong_supported(const FwdArgs& a) {
-  const int nk = a.rule.k.n;
-  const int dm = max(a.d, a.v_d);
-  return a.rule.policy == 0 && dm > 32 && dm <= kD && (nk % 8 == 0) && nk > 0 && (int64_t)dm * nk * 2 < (1ll << 31) &&
-         (int64_t)dm * a.rule.q.n * 2 < (1ll << 31) && (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) &&
-         (reinterpret_cast<uintptr_t>(a.V) % 16 == 0) && a.b * ((a.rule.q.n + kBM - 1) / kBM) < (1ll << 31);
-}
-
+// the full policy only: every other rule goes to the band, gap128 or fast kernels (fa_fwd_f16_choice.h)
 // tuned (c2, MI355X): MFMA phases at priority 1, fragment reads and staging
 // interleaved with the MFMAs (0.5526-0.5716 ms against 0.595 without), row sums in running
 // accumulators (0.5451 against 0.5552 ms), rebase check and m on the packed P (0.5395-0.5441
 // against 0.5512-0.5553 ms), the drain in place of the steps past the last tile (0.549-0.553 against
 // 0.557-0.569 ms)
-hipError_t launch_fwd_f16_pingpong(const FwdArgs& a, hipStream_t s) {
+hipError_t launch_fwd_f16_pingpong(const FwdArgs& a, const FwdF16Choice&, hipStream_t s) {
   const int64_t nqb = (a.rule.q.n + kBM - 1) / kBM;
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(fwd_f16_pingpong_kernel), kSmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fwd_f16_pingpong_kernel, dim3((unsigned)(a.b * nqb)), dim3(kNW * 64), kSmem, s, a);
-  return hipGetLastError();
+  return launch_smem(fwd_f16_pingpong_kernel, (unsigned)(a.b * nqb), kNW * 64, kSmem, s, a);
 }
 
 }  // namespace fa

@@ -17,13 +17,14 @@
 //   staging: K(i+1) loaded at the head of Sᵀ(i), stored after it; V(i+1) loaded at the head of
 //   softmax(i), stored after PV(i); one barrier per tile publishes both
 //
-// Layouts and numerics follow fa_fwd_f16_pingpong128.hip (the K image with 64-B halves swapped on
+// Layouts and numerics follow diag/fa_fwd_f16_pingpong128.hip (the K image with 64-B halves swapped on
 // rows with c & 2 read by transposed reads whose key columns are σ-permuted, V rows with XOR-swizzled
 // 16-B chunks read as b128, scores relative to 0 out of the MFMA, exact fp32 row max, log2-domain
 // lazy rebase at 8, l relative to the stored fp16 m).  Replaces the reference's ForwardImpl
 // (flash_attention.cu:425-1077), whose channel count is bounded only by shared memory
 // (flash_attention.cu:1977-2067), for these shapes; before round 4 they ran on the SIMT kernel.
 #include "fa_device.h"
+#include "fa_fwd_f16_choice.h"
 #include "fa_kernels.h"
 #include "fa_mfma.h"
 
@@ -349,25 +350,14 @@ __global__ __launch_bounds__(kNW * 64, 1) void fwd_f16_wide_kernel(FwdArgs a) {
 
 }  // namespace
 
-bool fwd_f16_wide_supported(const FwdArgs& a) {
-  const int nk = a.rule.k.n;
-  const int dm = max(a.d, a.v_d);
-  // (32-bit buffer offsets: a slice's rows stay below 2^31 bytes, the element-wise gather included)
-  return dm > 128 && dm <= kD && nk > 0 && (int64_t)dm * (nk + 8) * 2 < (1ll << 31) &&
-         (int64_t)dm * a.rule.q.n * 2 < (1ll << 31) && a.b * ((a.rule.q.n + kBM - 1) / kBM) < (1ll << 31);
-}
+static_assert(kD == 256 && kBM == 128, "the extents of the choice's wide question");
 
-hipError_t launch_fwd_f16_wide(const FwdArgs& a, hipStream_t s) {
+hipError_t launch_fwd_f16_wide(const FwdArgs& a, const FwdF16Choice& c, hipStream_t s) {
   const int64_t nqb = (a.rule.q.n + kBM - 1) / kBM;
-  const bool aln = (a.rule.k.n % 8 == 0) && (reinterpret_cast<uintptr_t>(a.K) % 16 == 0) &&
-                   (reinterpret_cast<uintptr_t>(a.V) % 16 == 0);
-  const int pol = a.rule.policy == 0 ? 0 : rule_is_interval(a.rule) ? 1 : 2;
-  auto kern = aln ? (pol == 0 ? fwd_f16_wide_kernel<0, true> : pol == 1 ? fwd_f16_wide_kernel<1, true> : fwd_f16_wide_kernel<2, true>)
-                  : (pol == 0 ? fwd_f16_wide_kernel<0, false> : pol == 1 ? fwd_f16_wide_kernel<1, false> : fwd_f16_wide_kernel<2, false>);
-  hipError_t e = set_smem_once(reinterpret_cast<const void*>(kern), kSmem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(a.b * nqb)), dim3(kNW * 64), kSmem, s, a);
-  return hipGetLastError();
+  const int pol = c.pol;
+  auto kern = c.aligned ? (pol == 0 ? fwd_f16_wide_kernel<0, true> : pol == 1 ? fwd_f16_wide_kernel<1, true> : fwd_f16_wide_kernel<2, true>)
+                        : (pol == 0 ? fwd_f16_wide_kernel<0, false> : pol == 1 ? fwd_f16_wide_kernel<1, false> : fwd_f16_wide_kernel<2, false>);
+  return launch_smem(kern, (unsigned)(a.b * nqb), kNW * 64, kSmem, s, a);
 }
 
 }  // namespace fa

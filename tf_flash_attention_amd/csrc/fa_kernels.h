@@ -199,36 +199,7 @@ bool bwd_generic_supported(int dtype, const BwdArgs& a);
 hipError_t launch_bwd_generic(int dtype, const BwdArgs& a, hipStream_t s);
 
 // The MFMA paths: where a *_supported predicate fails, the caller falls back to the generic path.
-// fp16 MFMA forward — fa_fwd_f16.hip (dispatch over the kernels below)
-bool fwd_f16_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16(const FwdArgs& a, hipStream_t s);
-// streamlined fp16 forward for d == v_d in {64, 128} under full / interval rules — fa_fwd_f16_fast.hip
-bool fwd_f16_fast_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16_fast(const FwdArgs& a, hipStream_t s);
-// paired-block fp16 forward for 32 < max(d, v_d) <= 64 (one wave per SIMD) — fa_fwd_f16_pp.hip
-bool fwd_f16_pp_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16_pp(const FwdArgs& a, hipStream_t s);
-// ping-pong fp16 forward (8 waves, two groups alternating MFMA / softmax phases) — fa_fwd_f16_pingpong.hip
-bool fwd_f16_pingpong_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16_pingpong(const FwdArgs& a, hipStream_t s);
-// one-wave-per-SIMD fp16 forward with a hand-placed gap stream, full policy, 32 < max(d, v_d) <= 64 —
-// diag/fa_fwd_f16_gap.hip (diagnostic library only: FA_FWD_VARIANT 26xx)
-bool fwd_f16_gap_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16_gap(const FwdArgs& a, hipStream_t s);
-// one-wave gap-stream fp16 forward for 64 < max(d, v_d) <= 128 (full / causal default) — fa_fwd_f16_gap128.hip
-bool fwd_f16_gap128_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16_gap128(const FwdArgs& a, hipStream_t s);
-// ping-pong fp16 forward for 64 < max(d, v_d) <= 128 — fa_fwd_f16_pingpong128.hip
-bool fwd_f16_pingpong128_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16_pingpong128(const FwdArgs& a, hipStream_t s);
-// fp16 forward on MFMA for 128 < max(d, v_d) <= 256: every rule (interval rules by key ranges, strided /
-// 2d windows by per-element masks) and any alignment or length (element-wise staging where K / V are not
-// 16-B aligned) — fa_fwd_f16_wide.hip
-bool fwd_f16_wide_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16_wide(const FwdArgs& a, hipStream_t s);
-// persistent band forward for 1d unit-stride local windows, 32 < max(d, v_d) <= 64 — fa_fwd_f16_band.hip
-bool fwd_f16_band_supported(const FwdArgs& a);
-hipError_t launch_fwd_f16_band(const FwdArgs& a, hipStream_t s);
+// The fp16 MFMA forward's kernels, the choice among them and their launchers: fa_fwd_f16_choice.h.
 // The few-query fp16 forwards: a partial kernel per (slice, key chunk), which runs the general kernel's key
 // loop (fa_fwd_f16_core.h) over its chunk, and a merge kernel (the pair: fa_fwd_f16_fewq.h).  At most
 // fwd_f16_fewq_max_batch() slices per call (grid limits), rows_out the (head, query) rows a slice's merge writes.

@@ -61,8 +61,54 @@ SHAPES_F16W = [
 SHAPES_SIMT = [("causal", 1, 40, (33,), (70,), 1, 0, False, False)]
 
 
+def choice_rows(dev):
+    """One fa_forward per row of the CPU choice table (tests/test_fwd_choice.py, imported, in table order) whose
+    operands take at most 1 GiB; prints each row with the kernel the table expects and, where the library has
+    fa_forward_kernel, the one it names for the real pointers (asserted equal)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_fwd_choice as T
+    from tf_flash_attention_amd import _lib
+    L = _lib.lib()
+    for name, kw, want in T.TABLE:
+        p, off = T.problem(**kw), kw.get("off", (0, 0, 0))
+        nq, nk = p.q_seq[0] * p.q_seq[1], p.k_seq[0] * p.k_seq[1]
+        elt = {_lib.F16: 2, _lib.F32: 4, _lib.F64: 8}[p.dtype]
+        sizes = [p.b * n * elt for n in (p.d * nq, p.d * nk, p.v_d * nk, p.v_d * nq)] + [p.b * nq * 8] * 2
+        if want == "none" or sum(sizes) > 1 << 30:
+            continue
+        bufs = [torch.zeros(n + 16, dtype=torch.uint8, device=dev) for n in sizes]
+        ptrs = [t.data_ptr() + o for t, o in zip(bufs, off + (0, 0, 0))]
+        assert all(t.data_ptr() % 16 == 0 for t in bufs)
+        named = "-"
+        if hasattr(L, "fa_forward_kernel"):
+            named = L.fa_forward_kernel(p, *ptrs[:3]).decode()
+            assert named == want, (name, named, want)
+        st = L.fa_forward(torch.cuda.current_stream().cuda_stream, p, *ptrs)
+        torch.cuda.synchronize()
+        assert st == 0, (name, _lib.last_error())
+        print(f"row {name} {want} | {named}", flush=True)
+    print("choice rows done")
+
+
+def choice_check(rows_file, *ordered_files):
+    """The ordered kernel lists (tools/trace_summary.py RUN_DIR --ordered) of runs of `choice` are equal, and row by
+    row the kernel each row of `rows_file` (a run's output) names."""
+    rows = [ln.split(" | ")[0].split(" ", 2)[2] for ln in open(rows_file) if ln.startswith("row ")]
+    lists = [[ln.strip() for ln in open(f) if ln.strip()] for f in ordered_files]
+    assert all(x == lists[0] for x in lists), "the runs launched different kernels"
+    assert len(rows) == len(lists[0]), (len(rows), len(lists[0]))
+    for want, got in zip(rows, lists[0]):
+        family = want in ("fwd_f32", "fwd_f64", "fwd_generic")  # (named by family: any kernel of it)
+        assert f"::{want}_" in got if family else f"::{want}(" in got, (want, got)
+    print(f"{len(ordered_files)} traces of {len(rows)} launches: equal, and each the kernel its row names")
+
+
 def main():
+    if sys.argv[1:2] == ["choice-check"]:
+        return choice_check(*sys.argv[2:])
     dev = torch.device("cuda:0")
+    if sys.argv[1:2] == ["choice"]:
+        return choice_rows(dev)
     g = torch.Generator(device=dev).manual_seed(0)
     mode = sys.argv[1] if len(sys.argv) > 1 else ""
     shapes = {"f64": SHAPES_F64, "f16w": SHAPES_F16W, "simt": SHAPES_SIMT}.get(mode, SHAPES)
