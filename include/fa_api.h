@@ -405,6 +405,71 @@ int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_g
                                  void* O, void* l, void* m,
                                  void* workspace, size_t workspace_bytes);
 
+/* Tree-masked draft attention (speculative decoding that verifies a TREE of candidates in one step): the four
+ * un-windowed, un-blocked forwards above with a DEVICE bit mask in the place of tail_causal.  The nq queries are
+ * the draft tokens, held in the last nq positions of each sequence; each sees the committed context and, of the
+ * draft tokens, those its mask row names (itself and its ancestors, for a tree).  Layouts, k_lens, kv_per_len,
+ * block_table, the scales, the clamping and the empty rows are fa_forward_ragged's / fa_forward_paged's and their
+ * _fp8 forms'.
+ *   draft_mask: DEVICE uint32 [sequences][nq][W], W = ceil(nq / 32), sequences = (b / kv_group) / kv_per_len; shared
+ *     by all K/V heads and query heads of a sequence.  Bit j & 31 of word j >> 5 of row i says whether query i sees
+ *     draft slot j.  The array needs 4-byte alignment only.
+ *   Rule: with L the clamped length of the slice and base = L - nq, draft slot j is key position base + j, and query
+ *     i sees key k iff 0 <= k < L and (k < base or bit(i, k - base)).  There is no other case: slots whose position
+ *     is negative (L < nq) name no key, and bits at or past nq in a row's last word are ignored, whatever they hold.
+ *     A row that sees no key is the empty row: O = 0, l = 0, every byte of m 0xFA.  The lower-triangular mask (bit j
+ *     of row i set iff j <= i) is the twin's tail_causal = 1 call.
+ * The host never reads the mask: no host synchronisation, and it may be overwritten in place between replays of a
+ * captured graph, like k_lens, block_table and the scales.
+ *
+ * Envelope: the twins': fp16, 1d sequences, FA_FULL, max(d, v_d) <= 128, kv_group * P <= 128 (so nq <= 128 and
+ *   W <= 4), and page % 64 == 0 in the paged forms.  There is no windowed and no query-blocked tree form.  Outside
+ *   it FA_ERR_UNSUPPORTED with nothing written.
+ * FA_ERR_INVALID_ARGUMENT with text in fa_last_error(): the twins' argument errors, and with b > 0 a null
+ *   draft_mask.  b == 0 and FA_ERR_WORKSPACE_TOO_SMALL with nothing written are the twins'.
+ * The plan and the workspace do not depend on the mask: fa_forward_ragged_tree_plan /
+ *   fa_forward_ragged_tree_workspace_bytes and the paged pair return fa_forward_ragged_plan's / ..._workspace_bytes's
+ *   and fa_forward_paged_plan's / ..._workspace_bytes's values; the FP8 forms share them.
+ *
+ * Never read: keys at or past L, whatever they hold; in the paged forms the table entries of pages without a key
+ *   below L.  Loaded entries and lengths are clamped as in the twins.
+ * Finite keys: a draft key that is masked for a query is the sequence's own key below L.  It is loaded and masked,
+ *   not zeroed, so it must be finite: a NaN or Inf in V there would survive a probability of 0 (the window forms'
+ *   clause).
+ * Bitwise: a slice's bits do not depend on b, on the other slices' lengths or on the other sequences' masks; the
+ *   paged bits are the ragged ones on the gathered cache; the FP8 bits with null or unit scales are the fp16 ones on
+ *   the converted cache; with the lower-triangular mask (O, l, m) are the bits of the twin called with
+ *   tail_causal = 1 (masking is a select to -inf in front of the same max, exp and sum chains, and a tile the twin
+ *   skips adds exact zeros when it is masked instead). */
+int fa_forward_ragged_tree_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]);
+int fa_forward_paged_tree_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]);
+size_t fa_forward_ragged_tree_workspace_bytes(const fa_problem* p, int32_t kv_group);
+size_t fa_forward_paged_tree_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page);
+int fa_forward_ragged_tree(void* stream, const fa_problem* p, int32_t kv_group,
+                           const void* Q, const void* K, const void* V,
+                           const int32_t* k_lens, int32_t kv_per_len, const uint32_t* draft_mask,
+                           void* O, void* l, void* m,
+                           void* workspace, size_t workspace_bytes);
+int fa_forward_paged_tree(void* stream, const fa_problem* p, int32_t kv_group,
+                          const void* Q, const void* K_pool, const void* V_pool,
+                          const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                          const int32_t* k_lens, int32_t kv_per_len, const uint32_t* draft_mask,
+                          void* O, void* l, void* m,
+                          void* workspace, size_t workspace_bytes);
+int fa_forward_ragged_tree_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                               const void* Q, const void* K8, const void* V8,
+                               const float* k_scale, const float* v_scale,
+                               const int32_t* k_lens, int32_t kv_per_len, const uint32_t* draft_mask,
+                               void* O, void* l, void* m,
+                               void* workspace, size_t workspace_bytes);
+int fa_forward_paged_tree_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                              const void* Q, const void* K_pool8, const void* V_pool8,
+                              const float* k_scale, const float* v_scale,
+                              const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                              const int32_t* k_lens, int32_t kv_per_len, const uint32_t* draft_mask,
+                              void* O, void* l, void* m,
+                              void* workspace, size_t workspace_bytes);
+
 /* Fused K/V append: the write side of the four caches above.  New tokens' keys and values are stored IN PLACE into a
  * ragged cache or into page pools, fp16 or FP8, by one kernel launch enqueued on `stream`: a forward enqueued after it
  * on that stream sees the tokens.  Every control value is device data; the host reads nothing and does not

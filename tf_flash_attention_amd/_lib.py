@@ -60,6 +60,14 @@ EXPORTED_SYMBOLS = (
     "fa_forward_paged_prefill",
     "fa_forward_ragged_prefill_fp8",
     "fa_forward_paged_prefill_fp8",
+    "fa_forward_ragged_tree_plan",
+    "fa_forward_paged_tree_plan",
+    "fa_forward_ragged_tree_workspace_bytes",
+    "fa_forward_paged_tree_workspace_bytes",
+    "fa_forward_ragged_tree",
+    "fa_forward_paged_tree",
+    "fa_forward_ragged_tree_fp8",
+    "fa_forward_paged_tree_fp8",
     "fa_append_ragged",
     "fa_append_paged",
     "fa_append_ragged_fp8",
@@ -84,7 +92,7 @@ EXPORTED_SYMBOLS = (
 
 
 DECODE_CACHES = ("ragged", "paged")
-DECODE_FORMS = ("plain", "window", "prefill")
+DECODE_FORMS = ("plain", "window", "prefill", "tree")
 
 
 def decode_entry_points(cache, form, fp8):
@@ -188,8 +196,8 @@ def _declare(lib):
     # The decode forwards (include/fa_api.h): a cache times a form times the cache's precision, every argument
     # list made of the same pieces.  A paged cache adds (page) to the plan functions and (block_table, max_pages,
     # page, num_pages) to the forward, an FP8 cache (k_scale, v_scale) to the forward, a window `window` after the
-    # plan functions' own arguments and where the forward's tail_causal stands.  (Each is absent from a library
-    # built before its feature, as above.)
+    # plan functions' own arguments and where the forward's tail_causal stands, a tree the device mask's pointer
+    # there.  (Each is absent from a library built before its feature, as above.)
     i32, i64 = ctypes.c_int32, ctypes.c_int64
     for cache in DECODE_CACHES:
         for form in DECODE_FORMS:
@@ -204,7 +212,8 @@ def _declare(lib):
                 getattr(lib, ws_bytes).restype = ctypes.c_size_t
                 getattr(lib, forward).argtypes = ([vp, P, i32, vp, vp, vp] + ([vp, vp] if fp8 else [])
                                                   + ([vp, i32, i32, i64] if cache == "paged" else [])
-                                                  + [vp, i32, i32, vp, vp, vp, vp, ctypes.c_size_t])
+                                                  + [vp, i32, vp if form == "tree" else i32]
+                                                  + [vp, vp, vp, vp, ctypes.c_size_t])
                 getattr(lib, forward).restype = ctypes.c_int
     # The fused K/V appends (include/fa_api.h): the same pieces again, the caches written instead of read; (k_scale,
     # v_scale) after an FP8 cache, (block_table, max_pages, page, num_pages) after a paged one.  (Absent as above.)

@@ -806,8 +806,8 @@ int fa_forward_grouped(void* stream, const fa_problem* p, int32_t kv_group, cons
                     [&](int64_t) { return fa::launch_fwd_f16_gqa(ga, s); });
 }
 
-// ---- the decode forwards (include/fa_api.h): a K/V cache times a form.  The cache is
-// ragged or paged, fp16 or FP8; the form plain, sliding-window or query-blocked.  What a call is:
+// ---- the decode forwards (include/fa_api.h): a K/V cache times a form.  The cache
+// is ragged or paged, fp16 or FP8; the form plain, sliding-window, query-blocked or tree-masked.  What a call is:
 struct PagedPart {  // the block table of a paged cache
   const int32_t* block_table;
   int32_t max_pages, page;
@@ -821,7 +821,12 @@ struct DecodeKind {
   const Kv8* kv8;          // null: an fp16 cache
   const int32_t* window;   // null: no window
   bool prefill;            // the query-blocked form
+  bool tree;               // the tree-masked draft form, with
+  const uint32_t* mask;    //   its device mask [sequences][nq][ceil(nq / 32)] (checked where k_lens is)
 };
+
+// the words of one sequence's draft mask: nq rows of ceil(nq / 32)
+static int64_t tree_mask_words(int64_t nq) { return nq * ((nq + 31) / 32); }
 
 // the checks and the un-windowed, un-blocked plan of a cache; `page` null: ragged
 static int check_cache(const fa_problem* p, int32_t kv_group, const int32_t* page) {
@@ -861,7 +866,8 @@ static size_t decode_workspace_bytes(const fa_problem* p, int32_t kv_group, cons
 // Every decode forward: the same checks, plan, workspace and launches.  K and V are the cache or the pools.  With
 // a window the sliding-window form: the tail form itself where the window reaches the capacity, else the window's
 // plan and kernels.  With `prefill` the query-blocked form: the twin itself where one block holds the queries, else
-// the blocked plan and kernels.
+// the blocked plan and kernels.  With `tree` the tree-masked draft form: the plain plan and workspace, the tree
+// kernels, and `tail_causal` unread (the draft slots' positions are the tail's).
 static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
                           const DecodeKind& c, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
                           void* l, void* m, void* workspace, size_t workspace_bytes) {
@@ -902,6 +908,7 @@ static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, c
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
   if (pg && !pg->block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null block_table");
   if (pg && (!K || !V)) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null K_pool or V_pool");
+  if (c.tree && !c.mask) return set_error(FA_ERR_INVALID_ARGUMENT, name + " tree forward: null draft_mask");
   fa::PagedFp8Args all = {};  // the widest cache's arguments: a narrower cache sends the part it has
   fa::PagedArgs& pa = all.p;
   fa::RaggedArgs& ra = pa.r;
@@ -920,6 +927,8 @@ static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, c
     using Args = std::decay_t<decltype(args)>;
     if (win) return fa::launch_fwd_f16_window<Args>({args, *c.window}, s);
     if (blocked) return fa::launch_fwd_f16_prefill<Args>({args, pp.nqb}, s);
+    // (the mask advances by sequences with the slab, as len0 does: the kernel counts from the launch's first)
+    if (c.tree) return fa::launch_fwd_f16_tree<Args>({args, c.mask + ra.len0 * tree_mask_words(p->q_seq[0])}, s);
     return fa::launch_fwd_f16_decode(args, s);
   };
   return fewq_slabs(p, ptrs, kv_group, gp.rows, &ra.g.s, [&](int64_t b0) {
@@ -1063,6 +1072,53 @@ int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_g
   const PagedPart pg = {block_table, max_pages, page, num_pages};
   const Kv8 kv8 = {k_scale, v_scale};
   return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, nullptr, true}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
+}
+
+// the tree-masked draft forms: the plain twins' plan and workspace (the mask changes neither), and the twins'
+// signatures with the device mask in the place of tail_causal
+int fa_forward_ragged_tree_plan(const fa_problem* p, int32_t kv_group, int32_t out[6]) {
+  return decode_plan(p, kv_group, nullptr, nullptr, false, out);
+}
+size_t fa_forward_ragged_tree_workspace_bytes(const fa_problem* p, int32_t kv_group) {
+  return decode_workspace_bytes(p, kv_group, nullptr, nullptr, false);
+}
+int fa_forward_paged_tree_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]) {
+  return decode_plan(p, kv_group, &page, nullptr, false, out);
+}
+size_t fa_forward_paged_tree_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page) {
+  return decode_workspace_bytes(p, kv_group, &page, nullptr, false);
+}
+
+int fa_forward_ragged_tree(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K,
+                           const void* V, const int32_t* k_lens, int32_t kv_per_len, const uint32_t* draft_mask, void* O,
+                           void* l, void* m, void* workspace, size_t workspace_bytes) {
+  return forward_decode(stream, p, kv_group, Q, K, V, {nullptr, nullptr, nullptr, false, true, draft_mask}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_ragged_tree_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K8,
+                               const void* V8, const float* k_scale, const float* v_scale, const int32_t* k_lens,
+                               int32_t kv_per_len, const uint32_t* draft_mask, void* O, void* l, void* m, void* workspace,
+                               size_t workspace_bytes) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_decode(stream, p, kv_group, Q, K8, V8, {nullptr, &kv8, nullptr, false, true, draft_mask}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_paged_tree(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
+                          const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page,
+                          int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, const uint32_t* draft_mask, void* O,
+                          void* l, void* m, void* workspace, size_t workspace_bytes) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  return forward_decode(stream, p, kv_group, Q, K_pool, V_pool, {&pg, nullptr, nullptr, false, true, draft_mask}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_paged_tree_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool8,
+                              const void* V_pool8, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                              int32_t max_pages, int32_t page, int64_t num_pages, const int32_t* k_lens,
+                              int32_t kv_per_len, const uint32_t* draft_mask, void* O, void* l, void* m, void* workspace,
+                              size_t workspace_bytes) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, nullptr, false, true, draft_mask}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
 }
 
 // ---- the fused K/V append of the same four caches (include/fa_api.h): every check on the host
@@ -1424,7 +1480,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill, tree-masked draft decode), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
 }
 
 }  // extern "C"

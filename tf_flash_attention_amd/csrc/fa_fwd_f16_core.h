@@ -18,7 +18,9 @@
 //     (RaggedCache8, PagedCache8: KvOf below);
 //   * window_partial_kernel and prefill_partial_kernel (fa_fwd_f16_window.h / .hip, fa_fwd_f16_prefill.h / .hip):
 //     the same four caches again, with a lower interval end, and over one block of a longer query axis (a map
-//     with kQBlock below).
+//     with kQBlock below);
+//   * tree_partial_kernel (fa_fwd_f16_tree.h / .hip): the four caches once more, the last nq keys seen through a
+//     device bit mask (a map with kTree: HasTree below).
 // The partial kernels share what surrounds the core, and their merge, in fa_fwd_f16_fewq.h.
 // The structure:
 //   * Sᵀ = Kᵀ·Q and Oᵀ = V·Pᵀ on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
@@ -125,6 +127,20 @@ __device__ __forceinline__ u32x4 chunk_f16(u32x2 v, float mul) {
                                                : __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(v[i >> 1], mul, false));
   return o;
 }
+
+// Whether the map's rule is a device bit mask over the last nq keys (fa_fwd_f16_tree.h: a map with kTree), which no
+// index interval expresses.  Such a map runs at POL 0 and is asked three more things: load_mask(qi), once per lane
+// before the key loop, for the row of the lane's query; its `base`, below which every key is seen (the tile class);
+// and allowed(k0), the 64 keys of a class-1 tile that the lane's query sees, as bits.  The other maps compile as
+// they did without it.
+template <class Map, class = void>
+struct HasTree {
+  static constexpr bool on = false;
+};
+template <class Map>
+struct HasTree<Map, typename std::enable_if<Map::kTree>::type> {
+  static constexpr bool on = true;
+};
 
 // The loop's register arrays.  The KERNEL declares them (and the WaveState below) and hands them
 // in: the compiler optimises fwd_f16_core as a function of its own before it inlines it, without
@@ -372,6 +388,7 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   const int wq1 = min(wq0 + 31, nq - 1);
   const bool wave_active = map.wave_active(wq0, w, nq);
   const int qi = map.lane_q(wq0, w, r);
+  if constexpr (HasTree<Map>::on) map.load_mask(min(qi, nq - 1));  // (padding rows take query nq-1's, as below)
   // (a folded block's padding rows take the rule state of query nq-1, here and in key_interval below)
   const int qo = (POL == 2 && (Map::kFolded || qi < nq)) ? seq_order(a.rule.q, a.rule, Map::kFolded ? min(qi, nq - 1) : qi) : 0;
   // POL 1 (interval rules): this lane's allowed keys [klo, klo + kspan) and the wave's
@@ -391,6 +408,7 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   auto tcls = [&](int k0) -> int {
     const int k1 = k0 + kBN - 1;
     if (!wave_active) return 0;
+    if constexpr (HasTree<Map>::on) return k1 < map.base ? 2 : 1;  // (a tile with a draft slot or the key nkl)
     if (POL == 0) return k1 < nkl ? 2 : 1;
     if (POL == 1) {
       if (wlo_min > k1 || whi_max < k0) return 0;
@@ -442,7 +460,18 @@ __device__ __forceinline__ void fwd_f16_core(const FwdArgs& a, lds_char_t* smem,
   // this, exp2(st) are the tile's probabilities relative to m_run).
   auto prepare = [&](int it, int cls, floatx16 (&st)[2], floatx16 (&nxt)[2], bool has_next) {
     const int k0 = kt0 + it * kBN;
-    if (cls == 1) {  // mixed / tail tile: per-element mask
+    if constexpr (HasTree<Map>::on) {
+      if (cls == 1) {  // a tile with draft slots: one bit of the lane's allowed word per element
+        const uint64_t allow = map.allowed(k0) >> (4 * h);
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int off = 32 * t + (i & 3) + 8 * (i >> 2);
+            st[t][i] = (allow >> off) & 1 ? st[t][i] : kNegInf;
+          }
+      }
+    } else if (cls == 1) {  // mixed / tail tile: per-element mask
       const int base = k0 + 4 * h - klo;
 #pragma unroll
       for (int t = 0; t < 2; ++t)

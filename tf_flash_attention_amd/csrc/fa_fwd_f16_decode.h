@@ -3,10 +3,10 @@
 // A decode forward is a cache times a form.  The cache says where the keys lie and how they are staged: ragged
 // (a padded K/V with per-sequence lengths) or paged (page pools behind a device block table), fp16 or FP8.  The
 // form says which keys a workgroup works: plain (fa_fwd_f16_decode.hip), under a sliding window
-// (fa_fwd_f16_window.h, .hip) or over query blocks (fa_fwd_f16_prefill.h, .hip).  Each form is ONE kernel template
-// over `class Cache`; a cache supplies
-//   Args         its argument struct (fa_kernels.h), which a form wraps in WindowOf<> / PrefillOf<>
-//   Rows         its row map (fa_fwd_f16_fewq.h), which a form wraps in WindowRowsOf<> / BlockRowsOf<>
+// (fa_fwd_f16_window.h, .hip), over query blocks (fa_fwd_f16_prefill.h, .hip) or with the last nq keys behind a
+// device bit mask (fa_fwd_f16_tree.h, .hip).  Each form is ONE kernel template over `class Cache`; a cache supplies
+//   Args         its argument struct (fa_kernels.h), which a form wraps in WindowOf<> / PrefillOf<> / TreeOf<>
+//   Rows         its row map (fa_fwd_f16_fewq.h), which a form wraps in WindowRowsOf<> / BlockRowsOf<> / TreeRowsOf<>
 //   ragged(a)    the RaggedArgs inside a: the plan, the lengths, what the merge reads
 //   row_keys(a)  host: the keys between two channel rows of K / V (the capacity, or the page)
 //   kChunkBytes  the bytes of 8 keys: with_fewq_tail's alignment unit

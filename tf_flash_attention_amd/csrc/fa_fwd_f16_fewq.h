@@ -1,7 +1,8 @@
 // fa_fwd_f16_fewq.h — the partial + merge pair of the few-query fp16 forwards (gfx950 MFMA).
 //
 // Few queries against many keys leave the GPU empty when one workgroup walks a slice's whole key range, so the
-// split-key, grouped and decode forwards (fa_fwd_f16_splitk.hip, _gqa.hip, _decode.hip, _window.hip, _prefill.hip) cut
+// split-key, grouped and decode forwards (fa_fwd_f16_splitk.hip, _gqa.hip, _decode.hip, _window.hip, _prefill.hip,
+// _tree.hip) cut
 // the key range into the chunks of a plan (fa_api.hip) and run two kernels:
 //   * a partial kernel, one workgroup of 4 waves per (slice, chunk), runs fwd_f16_core (fa_fwd_f16_core.h) over
 //     its chunk only and writes the UNNORMALISED fp32 accumulator of its live rows with their statistics to the

@@ -124,6 +124,14 @@ struct PrefillOf {
   int32_t nqb;  // query blocks: ceil(nq / P), >= 2
 };
 
+// the tree-masked draft forms of the same four forwards (fa_fwd_f16_tree.h): `a` with the capacity's plan, as the
+// plain form takes it; a's tail_causal is not read: the draft slots' positions are the tail's.
+template <class Args>
+struct TreeOf {
+  Args a;
+  const uint32_t* mask;  // device: [sequences][nq][ceil(nq / 32)] words from this LAUNCH's first sequence on (a.len0)
+};
+
 // the write side of the four caches (fa_cache_append.hip): new tokens' K and V stored in place.  Sequence s holds
 // L = clamp(k_lens[s], 0, nk) keys AFTER the append, of which the last n = min(clamp(new_lens[s], 0, n_new), L)
 // (new_lens null: min(n_new, L)) are new: slot n_new - n + t of K_new / V_new goes to key position L - n + t.
@@ -215,13 +223,16 @@ hipError_t launch_fwd_f16_gqa(const GqaArgs& ga, hipStream_t s);
 // for these four.  The form: plain (a chunk at or past its slice's length returns at once, and the merge folds only
 // the chunks below it) — fa_fwd_f16_decode.hip; with a sliding window (work for the window's chunks only) —
 // fa_fwd_f16_window.hip; for any number of queries (one workgroup per (K/V slice, query block, key chunk)) —
-// fa_fwd_f16_prefill.hip.
+// fa_fwd_f16_prefill.hip; with a device bit mask over the last nq keys (the plain form's chunks and merge) —
+// fa_fwd_f16_tree.hip.
 template <class Args>
 hipError_t launch_fwd_f16_decode(const Args& args, hipStream_t s);
 template <class Args>
 hipError_t launch_fwd_f16_window(const WindowOf<Args>& wa, hipStream_t s);
 template <class Args>
 hipError_t launch_fwd_f16_prefill(const PrefillOf<Args>& pf, hipStream_t s);
+template <class Args>
+hipError_t launch_fwd_f16_tree(const TreeOf<Args>& ta, hipStream_t s);
 // The fused K/V append of the same four caches (paged: behind a block table; fp8: e4m3fn bytes with per-head scales):
 // one launch of `blocks` = sequences * kv_heads * a.slice_blocks workgroups, which the caller has checked to fit a
 // grid — fa_cache_append.hip

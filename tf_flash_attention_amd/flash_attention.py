@@ -720,9 +720,9 @@ def _scale_ptrs(fp8, k_scale, v_scale):
 decode_entry_points = _lib.decode_entry_points
 
 
-def _decode_form(prefill, window):
-    """The form of a decode call: query-blocked, under a window (an int), or plain."""
-    return "prefill" if prefill else "plain" if window is None else "window"
+def _decode_form(prefill, window, mask=None):
+    """The form of a decode call: query-blocked, under a window (an int), tree-masked (a tensor), or plain."""
+    return "prefill" if prefill else "tree" if mask is not None else "plain" if window is None else "window"
 
 
 def _decode_window(what, window_size, tail_causal, nq):
@@ -740,7 +740,55 @@ def _decode_window(what, window_size, tail_causal, nq):
     return min(window_size, 2 ** 31 - 1)  # (any window at or above the capacity is the tail rule)
 
 
-def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=None, v_scale=None, window_size=None):
+def _decode_mask(what, draft_mask, tail_causal, window_size, Q, batch, nq):
+    """The mask of a tree-masked ``ragged_1d`` / ``paged_1d`` call as a contiguous int32 tensor, or None without one."""
+    if draft_mask is None:
+        return None
+    if not isinstance(draft_mask, torch.Tensor) or draft_mask.dtype != torch.int32:
+        raise TypeError("draft_mask must be an int32 tensor or None, got "
+                        f"{getattr(draft_mask, 'dtype', type(draft_mask).__name__)}")
+    want = tuple(batch) + (nq, (nq + 31) // 32)
+    if tuple(draft_mask.shape) != want:
+        raise InvalidArgumentError("The shape of draft_mask should be the batch shape without the heads plus "
+                                   "(Nq, ceil(Nq / 32)), but draft_mask_shape = " + _shape_str(draft_mask.shape)
+                                   + ", expected " + _shape_str(want) + " were received")
+    if draft_mask.device != Q.device:
+        raise InvalidArgumentError("draft_mask must be on the device of Q")
+    if not tail_causal:
+        raise InvalidArgumentError(f"{what}: draft slot j is the key at position k_lens - Nq + j, which is the tail "
+                                   "rule's placement, so draft_mask requires tail_causal=True")
+    if window_size is not None:
+        raise InvalidArgumentError(f"{what}: there is no windowed tree form; give draft_mask or window_size, not both")
+    return draft_mask.contiguous()
+
+
+def draft_mask_from_parents(parents):
+    """The ``draft_mask`` of a forest of draft tokens: ``parents`` is an integer tensor ``batch + (Nq,)`` with
+    ``parents[..., i] < i`` the parent of node i, or -1 for a child of the committed context.  Returns the int32
+    tensor ``batch + (Nq, ceil(Nq / 32))`` in which node i sees itself and its ancestors, built on the device of
+    ``parents`` without a host read: ancestors come before their descendants, so one pass in node order completes
+    every row from its parent's."""
+    if not isinstance(parents, torch.Tensor) or parents.dtype.is_floating_point or parents.dtype == torch.bool:
+        raise TypeError(f"parents must be an integer tensor, got {getattr(parents, 'dtype', type(parents).__name__)}")
+    if parents.dim() < 1 or parents.shape[-1] < 1:
+        raise InvalidArgumentError("parents should be batch + (Nq,) with Nq >= 1, but parents_shape = "
+                                   + _shape_str(parents.shape) + " was received")
+    nq = int(parents.shape[-1])
+    words = (nq + 31) // 32
+    par = parents.to(torch.int64)
+    sees = torch.zeros(tuple(parents.shape) + (32 * words,), dtype=torch.bool, device=parents.device)
+    for i in range(nq):
+        p = par[..., i]
+        up = torch.gather(sees, -2, p.clamp(0, nq - 1)[..., None, None].expand(p.shape + (1, 32 * words)))[..., 0, :]
+        sees[..., i, :] = up & ((p >= 0) & (p < i))[..., None]
+        sees[..., i, i] = True
+    weights = torch.ones(32, dtype=torch.int64, device=parents.device) << torch.arange(32, device=parents.device)
+    packed = (sees.view(tuple(parents.shape) + (words, 32)).to(torch.int64) * weights).sum(-1)
+    return (packed - ((packed >> 31) << 32)).to(torch.int32)  # (bit 31 is the int32's sign)
+
+
+def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=None, v_scale=None, window_size=None,
+              draft_mask=None):
     """Attention of a few queries over a padded K/V cache: Q ``batch + (Hq, C, Nq)``, K ``batch + (Hk, C, cap)``,
     V ``batch + (Hk, Cv, cap)`` with Hq = g * Hk read from the shapes (query head h attends K/V head h // g), and
     ``k_lens`` an int32 tensor of shape ``batch`` on the same device (0-d without a leading batch axis): sequence
@@ -764,9 +812,21 @@ def ragged_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=N
     not the capacity; ``W >= cap`` is the tail-causal call itself, bit for bit.  With
     ``lo = max(0, k_lens[s] - Nq - W + 1)``, keys below ``lo // 64 * 64`` are never read.  The at most 63 keys
     between that and ``lo`` are read and masked, so they must be finite (they are the sequence's own earlier keys).
+
+    A tree of draft tokens (speculative decoding that verifies several candidates in one step): ``draft_mask`` is an
+    int32 tensor ``batch + (Nq, ceil(Nq / 32))`` on the device of Q, taken as raw bits and shared by all heads of a
+    sequence.  The Nq queries are the draft tokens at the last Nq positions (``tail_causal=True`` is required, and
+    ``window_size`` must be None): draft slot j is the key at ``base + j``, ``base = k_lens[s] - Nq``, and query i
+    sees the keys below ``base`` and the slots j with bit ``j & 31`` of ``draft_mask[s, i, j >> 5]`` set; slots at
+    negative positions name no key, and bits at or past Nq are ignored.  ``draft_mask_from_parents`` builds the mask
+    of a forest (each token sees itself and its ancestors); the lower triangle is the ``tail_causal`` call, bit for
+    bit.  The kernels read the mask, never the host, so it too may be overwritten in place between replays.  Draft
+    keys that a query does not see are read and masked: they must be finite.
+
     More queries than the envelope's g * next_pow2(Nq) <= 128 (chunked prefill, a long speculative draft):
     ``ragged_prefill_1d``.  Returns ``O`` or ``(O, l, m)``."""
-    return _ragged_forward("ragged_1d", False, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, window_size)
+    return _ragged_forward("ragged_1d", False, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, window_size,
+                           draft_mask)
 
 
 def ragged_prefill_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k_scale=None, v_scale=None):
@@ -789,7 +849,8 @@ _PREFILL_ENVELOPE = ("float16, 1d sequences, at most 128 channels, Nq >= 1, capa
                      "1 <= g <= 128 with g = Hq / Hk")
 
 
-def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, window_size):
+def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, window_size,
+                    draft_mask=None):
     """``ragged_1d`` (``prefill`` False) and ``ragged_prefill_1d``: one validation, the entry points differ."""
     Qb, Qs, Q_ch, Kb, Ks, V_ch, g = verify_grouped_shapes(1, Q.shape, K.shape, V.shape)
     dt = _dtype_id(Q, True)
@@ -808,9 +869,10 @@ def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, 
         raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
                            "detach its inputs")
     window = _decode_window(what, window_size, tail_causal, int(Qs[0]))
+    mask = _decode_mask(what, draft_mask, tail_causal, window_size, Q, batch, int(Qs[0]))
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(Qb), Qs, Ks, Q_ch, V_ch)
     L = _lib.lib()
-    plan_name, ws_name, forward_name = decode_entry_points("ragged", _decode_form(prefill, window), fp8)
+    plan_name, ws_name, forward_name = decode_entry_points("ragged", _decode_form(prefill, window, mask), fp8)
     own = (prob, g) + (() if window is None else (window,))  # the plan functions' own arguments
     plan = (ctypes.c_int32 * 8)()
     st = getattr(L, plan_name)(*own, plan)
@@ -831,7 +893,8 @@ def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, 
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
         st = getattr(L, forward_name)(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
                                       *_scale_ptrs(fp8, k_scale, v_scale), k_lens.data_ptr(), kv_per_len,
-                                      int(bool(tail_causal)) if window is None else window, O.data_ptr(),
+                                      mask.data_ptr() if mask is not None else int(bool(tail_causal)) if window is None
+                                      else window, O.data_ptr(),
                                       l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
@@ -846,7 +909,7 @@ _PAGE_CONDITION = "the page size (the last axis of K_pool and V_pool) must be a 
 
 
 def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False, k_scale=None,
-             v_scale=None, window_size=None):
+             v_scale=None, window_size=None, draft_mask=None):
     """``ragged_1d`` over a paged K/V cache: Q ``batch + (Hq, C, Nq)``, ``K_pool`` ``[num_pages, Hk, C, page]``,
     ``V_pool`` ``[num_pages, Hk, Cv, page]`` with Hq = g * Hk read from the shapes, ``block_table`` an int32 tensor
     ``batch + (max_pages,)`` and ``k_lens`` an int32 tensor of shape ``batch``, both on the device of Q.  A page
@@ -888,11 +951,17 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
 
     (exact where the two key sets are disjoint: S <= k_lens - Nq - W + 1).
 
+    A tree of draft tokens: ``draft_mask``, an int32 tensor ``batch + (Nq, ceil(Nq / 32))`` of raw bits on the device
+    of Q, with ``ragged_1d``'s rule (``tail_causal=True`` required, no ``window_size``): query i sees the keys below
+    ``k_lens[s] - Nq`` and the draft slots its row names.  One call replaces a context call, a gather of the draft
+    keys out of the pages, a masked attention over them and ``merge_partials``; the mask may be overwritten in place
+    between replays like ``k_lens`` and ``block_table``.  ``draft_mask_from_parents`` builds it from a forest.
+
     Inference only (no gradient); float16 only; the page size must be a multiple of 64; outside the envelope the
     call raises NotImplementedError (there is no gather fallback).  More queries than the envelope's
     g * next_pow2(Nq) <= 128: ``paged_prefill_1d``.  Returns ``O`` or ``(O, l, m)``."""
     return _paged_forward("paged_1d", False, Q, K_pool, V_pool, block_table, k_lens, tail_causal, returning_l_m, k_scale,
-                          v_scale, window_size)
+                          v_scale, window_size, draft_mask)
 
 
 def paged_prefill_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False, k_scale=None,
@@ -917,7 +986,7 @@ def paged_prefill_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, 
 
 
 def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_causal, returning_l_m, k_scale, v_scale,
-                   window_size):
+                   window_size, draft_mask=None):
     """``paged_1d`` (``prefill`` False) and ``paged_prefill_1d``: one validation, the entry points differ."""
     if len(K_pool.shape) != 4 or len(V_pool.shape) != 4:
         raise InvalidArgumentError("K_pool and V_pool should be [num_pages, Hk, channels, page], but K_pool_shape = "
@@ -966,9 +1035,10 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
     if cap > 2 ** 30:
         raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
     window = _decode_window(what, window_size, tail_causal, nq)
+    mask = _decode_mask(what, draft_mask, tail_causal, window_size, Q, batch, nq)
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_ch)
     L = _lib.lib()
-    plan_name, ws_name, forward_name = decode_entry_points("paged", _decode_form(prefill, window), fp8)
+    plan_name, ws_name, forward_name = decode_entry_points("paged", _decode_form(prefill, window, mask), fp8)
     own = (prob, g, page) + (() if window is None else (window,))  # the plan functions' own arguments
     plan = (ctypes.c_int32 * 8)()
     st = getattr(L, plan_name)(*own, plan)
@@ -991,7 +1061,8 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
         st = getattr(L, forward_name)(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
                                       V_pool.data_ptr(), *_scale_ptrs(fp8, k_scale, v_scale), block_table.data_ptr(),
                                       max_pages, page, num_pages, k_lens.data_ptr(), hk,
-                                      int(bool(tail_causal)) if window is None else window, O.data_ptr(),
+                                      mask.data_ptr() if mask is not None else int(bool(tail_causal)) if window is None
+                                      else window, O.data_ptr(),
                                       l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
