@@ -470,7 +470,82 @@ int fa_forward_paged_tree_fp8(void* stream, const fa_problem* p, int32_t kv_grou
                               void* O, void* l, void* m,
                               void* workspace, size_t workspace_bytes);
 
-/* Fused K/V append: the write side of the four caches above.  New tokens' keys and values are stored IN PLACE into a
+/* Sliding-window forwards over query blocks (chunked prefill of local-attention layers): the sliding-window
+ * forwards above for ANY nq >= 1, with the same layouts, arguments and rule.  The nq queries are the last nq
+ * positions of a sequence of L = clamp(k_lens, 0, nk) live keys (the tail rule is implied): query i sits at
+ * pos = L - nq + i and sees the keys max(0, pos - window + 1) <= j <= pos; a query before position 0 gets the empty
+ * row (O = 0, l = 0, every byte of m 0xFA).  A batch that mixes prefill with decode right-aligns each sequence's real
+ * queries in the nq slots, as in the query-blocked forwards.
+ *
+ * Envelope: the query-blocked forwards': fp16, 1d sequences, FA_FULL, max(d, v_d) <= 128, 1 <= kv_group <= 128,
+ * nq >= 1, nk >= 1, and page % 64 == 0 in the paged forms.  Outside it FA_ERR_UNSUPPORTED with nothing written.
+ * window < 1 is FA_ERR_INVALID_ARGUMENT; the other argument errors, b == 0 and FA_ERR_WORKSPACE_TOO_SMALL with
+ * nothing written are the twins'; so are: no host synchronisation, no host read of k_lens, block_table or the
+ * scales, replayable from a captured graph.
+ *
+ * Block shape: the query-blocked forwards' P_b, rows and nqb.  Delegation, each bit for bit the parent with the
+ * parent's plan and workspace bytes:
+ *   window >= nk: the call IS fa_forward_*_prefill with tail_causal = 1 (delegated = 1);
+ *   otherwise nqb == 1 (kv_group * next_pow2(nq) <= 128): the call IS fa_forward_*_window (delegated = 2).
+ * Otherwise block qb holds nq_b queries and sees the keys [lo_b, L_b), L_b as in the query-blocked forwards and
+ *   lo_b = max(0, L_b - nq_b - window + 1): at most span_w = min(nk, window + P_b - 1) keys.  With
+ *     kmax = max(1, 64 / nqb), min_chunk = 512 where rows <= 64, else 1024,
+ *     chunk = max(min_chunk, ceil(ceil(span_w / kmax) / 64) * 64), cap_chunks = ceil(nk / chunk),
+ *     launched = min(cap_chunks, (span_w + chunk - 2) / chunk + 1)
+ *   one workgroup per (K/V slice, query block, launched chunk) and a merge: chunk boundaries are absolute multiples
+ *   of `chunk` from key 0, and launched chunk c of a block is absolute chunk lo_b / chunk + c.  The workspace is
+ *   b / kv_group * nqb * launched records of rows * (v_d + 3) floats, rounded up to 256 bytes.
+ * The plan functions (host-only; pure functions of the problem WITHOUT b, the lengths or the table) write
+ *   out[0] launched chunks per block (0 outside the envelope; then all of out[] is 0)
+ *   out[1] keys per chunk          out[4] P_b
+ *   out[2] span_w                  out[5] rows
+ *   out[3] cap_chunks              out[6] nqb
+ *   out[7] delegated: 0, 1 or 2 as above; out[0] .. out[3] are then the parent's plan (out[2] = min(nk, window +
+ *          P_b - 1) and out[3] = out[0] for 1; the windowed twin's span_w and cap_chunks for 2)
+ * The FP8 forms use the fp16 plan and workspace functions, as their twins do.
+ *
+ * Never read: for each block, key tiles wholly below floor(lo_b / 64) * 64 and keys at or past L_b; so for the call,
+ *   key tiles wholly below its lowest window start lo = max(0, L - nq - window + 1) rounded down to 64, and keys at
+ *   or past L.  In the paged forms the table entries of pages wholly below that key and of pages past the last live
+ *   page are never loaded: the serving stack may free and reuse those pages.  Loaded entries and lengths are clamped
+ *   as in the twins.  No unwritten workspace word reaches a result.
+ * Finite keys: the keys of a block's first staged tile that lie below lo_b (at most 63) are loaded and masked, not
+ *   zeroed.  For every block but the first they are keys that an earlier block sees anyway; for the call, the up to
+ *   63 keys below lo must be finite.
+ * A slice's bits do not depend on b or on the other slices' lengths; the paged bits are the ragged ones on the
+ *   gathered cache; the FP8 bits with null or unit scales are the fp16 ones on the converted cache; a full block's
+ *   bits are fa_forward_*_window's on a contiguous copy of its queries with the length L_b, where both plans give the
+ *   same chunk. */
+int fa_forward_ragged_window_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t window, int32_t out[8]);
+int fa_forward_paged_window_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window, int32_t out[8]);
+size_t fa_forward_ragged_window_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t window);
+size_t fa_forward_paged_window_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window);
+int fa_forward_ragged_window_prefill(void* stream, const fa_problem* p, int32_t kv_group,
+                                     const void* Q, const void* K, const void* V,
+                                     const int32_t* k_lens, int32_t kv_per_len, int32_t window,
+                                     void* O, void* l, void* m,
+                                     void* workspace, size_t workspace_bytes);
+int fa_forward_paged_window_prefill(void* stream, const fa_problem* p, int32_t kv_group,
+                                    const void* Q, const void* K_pool, const void* V_pool,
+                                    const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                                    const int32_t* k_lens, int32_t kv_per_len, int32_t window,
+                                    void* O, void* l, void* m,
+                                    void* workspace, size_t workspace_bytes);
+int fa_forward_ragged_window_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                                         const void* Q, const void* K8, const void* V8,
+                                         const float* k_scale, const float* v_scale,
+                                         const int32_t* k_lens, int32_t kv_per_len, int32_t window,
+                                         void* O, void* l, void* m,
+                                         void* workspace, size_t workspace_bytes);
+int fa_forward_paged_window_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group,
+                                        const void* Q, const void* K_pool8, const void* V_pool8,
+                                        const float* k_scale, const float* v_scale,
+                                        const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                                        const int32_t* k_lens, int32_t kv_per_len, int32_t window,
+                                        void* O, void* l, void* m,
+                                        void* workspace, size_t workspace_bytes);
+
+/* Fused K/V append: the write side of the four caches above. New tokens' keys and values are stored IN PLACE into a
  * ragged cache or into page pools, fp16 or FP8, by one kernel launch enqueued on `stream`: a forward enqueued after it
  * on that stream sees the tokens.  Every control value is device data; the host reads nothing and does not
  * synchronise, so the call may be captured in a graph and replayed after any of them was overwritten in place.

@@ -68,6 +68,14 @@ EXPORTED_SYMBOLS = (
     "fa_forward_paged_tree",
     "fa_forward_ragged_tree_fp8",
     "fa_forward_paged_tree_fp8",
+    "fa_forward_ragged_window_prefill_plan",
+    "fa_forward_paged_window_prefill_plan",
+    "fa_forward_ragged_window_prefill_workspace_bytes",
+    "fa_forward_paged_window_prefill_workspace_bytes",
+    "fa_forward_ragged_window_prefill",
+    "fa_forward_paged_window_prefill",
+    "fa_forward_ragged_window_prefill_fp8",
+    "fa_forward_paged_window_prefill_fp8",
     "fa_append_ragged",
     "fa_append_paged",
     "fa_append_ragged_fp8",
@@ -92,7 +100,7 @@ EXPORTED_SYMBOLS = (
 
 
 DECODE_CACHES = ("ragged", "paged")
-DECODE_FORMS = ("plain", "window", "prefill", "tree")
+DECODE_FORMS = ("plain", "window", "prefill", "tree", "window_prefill")
 
 
 def decode_entry_points(cache, form, fp8):
@@ -201,7 +209,7 @@ def _declare(lib):
     i32, i64 = ctypes.c_int32, ctypes.c_int64
     for cache in DECODE_CACHES:
         for form in DECODE_FORMS:
-            own = [P, i32] + ([i32] if cache == "paged" else []) + ([i32] if form == "window" else [])
+            own = [P, i32] + ([i32] if cache == "paged" else []) + ([i32] if form in ("window", "window_prefill") else [])
             for fp8 in (False, True):
                 plan, ws_bytes, forward = decode_entry_points(cache, form, fp8)
                 if not hasattr(lib, forward):

@@ -403,6 +403,65 @@ void write_prefill_plan(int32_t out[8], const PrefillPlan& w) {
   out[6] = out[7] = 0;
 }
 
+// Sliding-window forms over query blocks: the product of the two plans above.  `base` is the
+// un-windowed, un-blocked twin's plan.  A window that reaches the capacity cuts nothing: the call is the
+// query-blocked form's tail call with its plan (delegated = 1).  Below it, where one block holds the queries, the
+// call is the windowed twin's with its plan (delegated = 2).  Otherwise block qb sees at most
+// span_w = min(nk, W + pb - 1) keys somewhere in the capacity: prefill_plan's chunk formula over span_w (at most
+// kmax = max(1, 64 / nqb) chunks of at least the twins' min_chunk keys), chunk boundaries at absolute multiples of
+// the chunk, and as many launched chunks per block as an interval of span_w keys can touch.  A pure function of the
+// problem without b, the lengths or the table.
+struct WindowPrefillPlan {
+  PrefillPlan pp;  // pp.g.nchunks: the launched chunks per (K/V slice, query block); pp.delegated: the parent's own
+  int32_t span_w, cap_chunks, delegated;
+};
+
+WindowPrefillPlan window_prefill_plan(const fa_problem* p, int32_t kv_group, const GroupedPlan& base, int32_t page_keys,
+                                      int32_t window) {
+  WindowPrefillPlan w = {prefill_plan(p, kv_group, base, page_keys), 0, 0, 0};
+  if (w.pp.g.nchunks == 0) return w;  // outside the envelope (inside it: 1d, nq >= 1, nk >= 1)
+  const int64_t nk = p->k_seq[0];
+  w.cap_chunks = w.pp.g.nchunks;
+  w.span_w = (int32_t)(nk < (int64_t)window + w.pp.pb - 1 ? nk : (int64_t)window + w.pp.pb - 1);
+  if (window >= nk) {
+    w.delegated = 1;
+    return w;
+  }
+  if (w.pp.delegated) {  // one block: the windowed twin
+    const WindowPlan t = window_plan(p, base, window);
+    w.pp.g = t.g;
+    w.span_w = t.span_w;
+    w.cap_chunks = t.cap_chunks;
+    w.delegated = 2;
+    return w;
+  }
+  const int32_t kmax = kSplitMaxChunks / w.pp.nqb > 1 ? kSplitMaxChunks / w.pp.nqb : 1;
+  const int32_t min_chunk = w.pp.rows <= 64 ? 512 : 1024;
+  const int32_t capped = ((w.span_w + kmax - 1) / kmax + kSplitTile - 1) / kSplitTile * kSplitTile;
+  w.pp.g.chunk = capped > min_chunk ? capped : min_chunk;
+  w.cap_chunks = (int32_t)((nk + w.pp.g.chunk - 1) / w.pp.g.chunk);
+  const int32_t touched = (w.span_w + w.pp.g.chunk - 2) / w.pp.g.chunk + 1;
+  w.pp.g.nchunks = touched < w.cap_chunks ? touched : w.cap_chunks;
+  return w;
+}
+
+// (delegated = 2: the windowed twin's records; otherwise the query-blocked form's, its own delegation included)
+size_t window_prefill_ws_bytes(const fa_problem* p, int32_t kv_group, const WindowPrefillPlan& w) {
+  return w.delegated == 2 ? grouped_ws_bytes(p, kv_group, w.pp.g) : prefill_ws_bytes(p, kv_group, w.pp);
+}
+
+void write_window_prefill_plan(int32_t out[8], const WindowPrefillPlan& w) {
+  const bool in = w.pp.g.nchunks != 0;
+  out[0] = w.pp.g.nchunks;
+  out[1] = in ? w.pp.g.chunk : 0;
+  out[2] = in ? w.span_w : 0;
+  out[3] = in ? w.cap_chunks : 0;
+  out[4] = in ? w.pp.pb : 0;
+  out[5] = in ? w.pp.rows : 0;
+  out[6] = in ? w.pp.nqb : 0;
+  out[7] = in ? w.delegated : 0;
+}
+
 // Split-key routing of the fp16 backward's dQ pass: the forward's plan, where the
 // dQ kernel's 32-bit buffer offsets reach a slice's K / V channel rows (the b-free part of
 // bwd_f16_fast_supported).  Also a pure function of the problem WITHOUT b, and a subset of the
@@ -845,7 +904,8 @@ static int decode_plan(const fa_problem* p, int32_t kv_group, const int32_t* pag
   if (wst != FA_OK) return wst;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
   const GroupedPlan base = cache_plan(p, kv_group, page);
-  if (window) write_window_plan(out, window_plan(p, base, *window));
+  if (window && prefill) write_window_prefill_plan(out, window_prefill_plan(p, kv_group, base, page ? *page : 0, *window));
+  else if (window) write_window_plan(out, window_plan(p, base, *window));
   else if (prefill) write_prefill_plan(out, prefill_plan(p, kv_group, base, page ? *page : 0));
   else write_plan(out, base);
   return FA_OK;
@@ -855,6 +915,10 @@ static size_t decode_workspace_bytes(const fa_problem* p, int32_t kv_group, cons
                                      bool prefill) {
   if (check_cache(p, kv_group, page) != FA_OK || (window && check_window(*window) != FA_OK)) return 0;
   const GroupedPlan base = cache_plan(p, kv_group, page);
+  if (window && prefill) {
+    const WindowPrefillPlan w = window_prefill_plan(p, kv_group, base, page ? *page : 0, *window);
+    return w.pp.g.nchunks ? window_prefill_ws_bytes(p, kv_group, w) : 0;
+  }
   if (prefill) {
     const PrefillPlan w = prefill_plan(p, kv_group, base, page ? *page : 0);
     return w.g.nchunks ? prefill_ws_bytes(p, kv_group, w) : 0;
@@ -866,7 +930,10 @@ static size_t decode_workspace_bytes(const fa_problem* p, int32_t kv_group, cons
 // Every decode forward: the same checks, plan, workspace and launches.  K and V are the cache or the pools.  With
 // a window the sliding-window form: the tail form itself where the window reaches the capacity, else the window's
 // plan and kernels.  With `prefill` the query-blocked form: the twin itself where one block holds the queries, else
-// the blocked plan and kernels.  With `tree` the tree-masked draft form: the plain plan and workspace, the tree
+// the blocked plan and kernels.  With both the sliding-window form over query blocks: the query-blocked tail call
+// itself where the window reaches the capacity, else the windowed twin itself where one block holds the queries
+// (either is the parent's own call: its checks, plan, workspace size and bits), else the product's plan and
+// kernels.  With `tree` the tree-masked draft form: the plain plan and workspace, the tree
 // kernels, and `tail_causal` unread (the draft slots' positions are the tail's).
 static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K, const void* V,
                           const DecodeKind& c, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, void* O,
@@ -888,21 +955,28 @@ static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, c
                            " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
     if (pg->num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: num_pages must be >= 1");
   }
-  const WindowPlan wp = window_plan(p, cache_plan(p, kv_group, page), c.window ? *c.window : 0x7fffffff);
-  const PrefillPlan pp = c.prefill ? prefill_plan(p, kv_group, wp.g, pg ? pg->page : 0) : PrefillPlan{};
+  const GroupedPlan base = cache_plan(p, kv_group, page);
+  const bool both = c.window && c.prefill;
+  const WindowPrefillPlan wpp = both ? window_prefill_plan(p, kv_group, base, pg ? pg->page : 0, *c.window) : WindowPrefillPlan{};
+  if (wpp.delegated == 1)
+    return forward_decode(stream, p, kv_group, Q, K, V, {c.paged, c.kv8, nullptr, true}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
+  if (wpp.delegated == 2)
+    return forward_decode(stream, p, kv_group, Q, K, V, {c.paged, c.kv8, c.window}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
+  const WindowPlan wp = both ? WindowPlan{} : window_plan(p, base, c.window ? *c.window : 0x7fffffff);
+  const PrefillPlan pp = both ? wpp.pp : c.prefill ? prefill_plan(p, kv_group, wp.g, pg ? pg->page : 0) : PrefillPlan{};
   const bool blocked = c.prefill && !pp.delegated;
-  const GroupedPlan& gp = blocked ? pp.g : wp.g;
-  const bool win = c.window && !wp.delegated;
+  const GroupedPlan& gp = blocked || both ? pp.g : wp.g;
+  const bool win = c.window && !both && !wp.delegated;
   if (gp.nchunks == 0)
     return set_error(FA_ERR_UNSUPPORTED,
-                     name + (c.prefill ? " prefill forward: outside the envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
+                     name + (both ? " windowed" : "") + (c.prefill ? " prefill forward: outside the envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
                                          "1 <= kv_group <= 128, nq >= 1, nk >= 1"
                                        : " forward: outside the fused envelope (fp16, 1d sequences, max(d, v_d) <= 128, "
                                          "kv_group * pitch <= 128, nq >= 1, nk >= 1") +
                          (pg ? ", page % 64 == 0)" : ")"));
   if (!workspace || workspace_bytes < (blocked ? prefill_ws_bytes(p, kv_group, pp) : grouped_ws_bytes(p, kv_group, gp)))
     return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "forward workspace is smaller than fa_forward_" + name +
-                                                     (c.prefill ? "_prefill" : "") + "_workspace_bytes()");
+                                                     (both ? "_window" : "") + (c.prefill ? "_prefill" : "") + "_workspace_bytes()");
   FA_DIAG_COUNT(0);
   if (p->b == 0) return FA_OK;
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
@@ -925,6 +999,7 @@ static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, c
   // the form picks the launcher, the argument struct its instance
   auto launch = [&](const auto& args) {
     using Args = std::decay_t<decltype(args)>;
+    if (both) return fa::launch_fwd_f16_window_prefill<Args>({args, *c.window, pp.nqb}, s);
     if (win) return fa::launch_fwd_f16_window<Args>({args, *c.window}, s);
     if (blocked) return fa::launch_fwd_f16_prefill<Args>({args, pp.nqb}, s);
     // (the mask advances by sequences with the slab, as len0 does: the kernel counts from the launch's first)
@@ -1072,6 +1147,52 @@ int fa_forward_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_g
   const PagedPart pg = {block_table, max_pages, page, num_pages};
   const Kv8 kv8 = {k_scale, v_scale};
   return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, nullptr, true}, k_lens, kv_per_len, tail_causal, O, l, m, workspace, workspace_bytes);
+}
+
+// the sliding-window forms over query blocks: the `_window` signatures with the prefill forms' envelope
+int fa_forward_ragged_window_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t window, int32_t out[8]) {
+  return decode_plan(p, kv_group, nullptr, &window, true, out);
+}
+size_t fa_forward_ragged_window_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t window) {
+  return decode_workspace_bytes(p, kv_group, nullptr, &window, true);
+}
+int fa_forward_paged_window_prefill_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window, int32_t out[8]) {
+  return decode_plan(p, kv_group, &page, &window, true, out);
+}
+size_t fa_forward_paged_window_prefill_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page, int32_t window) {
+  return decode_workspace_bytes(p, kv_group, &page, &window, true);
+}
+
+int fa_forward_ragged_window_prefill(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K,
+                                     const void* V, const int32_t* k_lens, int32_t kv_per_len, int32_t window, void* O,
+                                     void* l, void* m, void* workspace, size_t workspace_bytes) {
+  return forward_decode(stream, p, kv_group, Q, K, V, {nullptr, nullptr, &window, true}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_ragged_window_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K8,
+                                         const void* V8, const float* k_scale, const float* v_scale, const int32_t* k_lens,
+                                         int32_t kv_per_len, int32_t window, void* O, void* l, void* m, void* workspace,
+                                         size_t workspace_bytes) {
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_decode(stream, p, kv_group, Q, K8, V8, {nullptr, &kv8, &window, true}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_paged_window_prefill(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
+                                    const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page,
+                                    int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t window, void* O,
+                                    void* l, void* m, void* workspace, size_t workspace_bytes) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  return forward_decode(stream, p, kv_group, Q, K_pool, V_pool, {&pg, nullptr, &window, true}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_paged_window_prefill_fp8(void* stream, const fa_problem* p, int32_t kv_group, const void* Q,
+                                        const void* K_pool8, const void* V_pool8, const float* k_scale, const float* v_scale,
+                                        const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                                        const int32_t* k_lens, int32_t kv_per_len, int32_t window, void* O, void* l, void* m,
+                                        void* workspace, size_t workspace_bytes) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  const Kv8 kv8 = {k_scale, v_scale};
+  return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, &window, true}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
 }
 
 // the tree-masked draft forms: the plain twins' plan and workspace (the mask changes neither), and the twins'
@@ -1480,7 +1601,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill, tree-masked draft decode), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill, tree-masked draft decode, sliding-window prefill), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
 }
 
 }  // extern "C"

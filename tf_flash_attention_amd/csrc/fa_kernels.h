@@ -124,6 +124,17 @@ struct PrefillOf {
   int32_t nqb;  // query blocks: ceil(nq / P), >= 2
 };
 
+// the sliding-window forms over query blocks of the same four forwards (fa_fwd_f16_window_prefill.h): `a` as
+// PrefillOf takes it, with the window's plan as WindowOf takes it: a's SplitArgs holds nchunks = the launched chunks
+// per (K/V slice, query block), relative to the chunk that holds the first key of the block's window, and the
+// records [b_kv][nqb][nchunks] of stride g * P; its tail_causal is not read.
+template <class Args>
+struct WindowPrefillOf {
+  Args a;
+  int32_t window;  // W, as in WindowOf; 1 <= W < nk
+  int32_t nqb;     // query blocks, as in PrefillOf; >= 2
+};
+
 // the tree-masked draft forms of the same four forwards (fa_fwd_f16_tree.h): `a` with the capacity's plan, as the
 // plain form takes it; a's tail_causal is not read: the draft slots' positions are the tail's.
 template <class Args>
@@ -224,9 +235,12 @@ hipError_t launch_fwd_f16_gqa(const GqaArgs& ga, hipStream_t s);
 // the chunks below it) — fa_fwd_f16_decode.hip; with a sliding window (work for the window's chunks only) —
 // fa_fwd_f16_window.hip; for any number of queries (one workgroup per (K/V slice, query block, key chunk)) —
 // fa_fwd_f16_prefill.hip; with a device bit mask over the last nq keys (the plain form's chunks and merge) —
-// fa_fwd_f16_tree.hip.
+// fa_fwd_f16_tree.hip; with a sliding window over query blocks (the product of the second and the third) —
+// fa_fwd_f16_window_prefill.hip.
 template <class Args>
 hipError_t launch_fwd_f16_decode(const Args& args, hipStream_t s);
+template <class Args>
+hipError_t launch_fwd_f16_window_prefill(const WindowPrefillOf<Args>& wp, hipStream_t s);
 template <class Args>
 hipError_t launch_fwd_f16_window(const WindowOf<Args>& wa, hipStream_t s);
 template <class Args>

@@ -65,7 +65,7 @@ __all__ = [
     "Part", "combined_1d", "combined_2d", "merge_partials",
     "grouped_1d", "grouped_2d", "attention_forward_grouped",
     "ragged_1d", "paged_1d", "ragged_prefill_1d", "paged_prefill_1d", "quantize_kv_fp8",
-    "ragged_append_1d", "paged_append_1d",
+    "ragged_append_1d", "paged_append_1d", "ragged_window_prefill_1d", "paged_window_prefill_1d",
 ]
 
 
@@ -721,7 +721,10 @@ decode_entry_points = _lib.decode_entry_points
 
 
 def _decode_form(prefill, window, mask=None):
-    """The form of a decode call: query-blocked, under a window (an int), tree-masked (a tensor), or plain."""
+    """The form of a decode call: query-blocked (under a window or not), under a window (an int), tree-masked (a
+    tensor), or plain."""
+    if prefill and window is not None:
+        return "window_prefill"
     return "prefill" if prefill else "tree" if mask is not None else "plain" if window is None else "window"
 
 
@@ -833,7 +836,8 @@ def ragged_prefill_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k
     """``ragged_1d`` for any number of queries (chunked prefill, long speculative drafts): the same tensors, layouts,
     ``tail_causal`` rule, empty rows, FP8 cache and scales, with Nq >= 1 unbounded and 1 <= g <= 128.  The queries are
     worked in blocks of P = the largest power of two with g * P <= 128; where one block holds them all the call is
-    ``ragged_1d`` itself, bit for bit.  There is no ``window_size``.
+    ``ragged_1d`` itself, bit for bit.  There is no ``window_size``.  (Under a sliding window:
+    ``ragged_window_prefill_1d``.)
 
     A batch that mixes prefill with decode right-aligns each sequence's real queries in the Nq slots (with
     ``tail_causal`` the last slot is the sequence's last position).  The padding queries in front compute earlier
@@ -843,6 +847,36 @@ def ragged_prefill_1d(Q, K, V, k_lens, tail_causal=False, returning_l_m=False, k
     the envelope (more than 128 channels, g > 128) the call raises NotImplementedError.  Returns ``O`` or
     ``(O, l, m)``."""
     return _ragged_forward("ragged_prefill_1d", True, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, None)
+
+
+def ragged_window_prefill_1d(Q, K, V, k_lens, window_size, returning_l_m=False, k_scale=None, v_scale=None):
+    """``ragged_1d`` under a sliding window for any number of queries (chunked prefill of local-attention layers): the
+    same tensors, layouts, empty rows, FP8 cache and scales, with Nq >= 1 unbounded and 1 <= g <= 128.
+    ``window_size`` = W is a required int >= 1 (clamped to 2^31 - 1).  The Nq queries are the last Nq positions of the
+    sequence (the tail rule is implied): query i at position ``pos = k_lens[s] - Nq + i`` sees the W keys
+    ``max(0, pos - W + 1) <= j <= pos``; a query before position 0 gets the empty row.  The queries are worked in
+    blocks of P = the largest power of two with g * P <= 128, and each block launches work for the W + P - 1 keys it
+    can see, not for the prefix.  ``W >= cap`` is ``ragged_prefill_1d(..., tail_causal=True)`` itself and one block is
+    ``ragged_1d(..., tail_causal=True, window_size=W)`` itself, bit for bit.
+
+    ``k_lens`` and the scales are read on the device, never on the host: no synchronisation, and the call may be
+    replayed from a captured graph after they were overwritten in place.  A batch that mixes prefill with decode
+    right-aligns each sequence's real queries in the Nq slots; the padding queries in front compute earlier
+    positions' rows, or empty rows.  With ``lo = max(0, k_lens[s] - Nq - W + 1)``, the call's lowest window start,
+    keys below ``lo // 64 * 64`` are never read; the up to 63 keys between that and ``lo`` are read and masked, so
+    they must be finite.  Attention sinks compose from a second call and ``merge_partials``, as in ``ragged_1d``.
+
+    Inference only; float16 only; outside the envelope (more than 128 channels, g > 128) the call raises
+    NotImplementedError.  Returns ``O`` or ``(O, l, m)``."""
+    return _ragged_forward("ragged_window_prefill_1d", True, Q, K, V, k_lens, True, returning_l_m, k_scale, v_scale,
+                           _required_window(window_size))
+
+
+def _required_window(window_size):
+    """``window_size`` of a call that has no form without one."""
+    if window_size is None:
+        raise TypeError("window_size must be an int, got None")
+    return window_size
 
 
 _PREFILL_ENVELOPE = ("float16, 1d sequences, at most 128 channels, Nq >= 1, capacity >= 1 and "
@@ -970,9 +1004,9 @@ def paged_prefill_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, 
     the same pools, block table, lengths, ``tail_causal`` rule, empty rows, FP8 pools and scales, with Nq >= 1
     unbounded and 1 <= g <= 128.  The queries are worked in blocks of P = the largest power of two with
     g * P <= 128; where one block holds them all the call is ``paged_1d`` itself, bit for bit.  There is no
-    ``window_size``.  The new tokens' keys are appended to the pools first (``paged_1d`` shows how), so that
-    ``k_lens`` counts them; ``paged_append_1d`` does it in one call, with this function's ``k_lens`` and the real
-    tokens right-aligned as the queries are.
+    ``window_size``.  (Under a sliding window: ``paged_window_prefill_1d``.)  The new tokens' keys are appended to
+    the pools first (``paged_1d`` shows how), so that ``k_lens`` counts them; ``paged_append_1d`` does it in one
+    call, with this function's ``k_lens`` and the real tokens right-aligned as the queries are.
 
     A batch that mixes prefill with decode right-aligns each sequence's real queries in the Nq slots (with
     ``tail_causal`` the last slot is the sequence's last position).  The padding queries in front compute earlier
@@ -983,6 +1017,30 @@ def paged_prefill_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, 
     raises NotImplementedError.  Returns ``O`` or ``(O, l, m)``."""
     return _paged_forward("paged_prefill_1d", True, Q, K_pool, V_pool, block_table, k_lens, tail_causal, returning_l_m,
                           k_scale, v_scale, None)
+
+
+def paged_window_prefill_1d(Q, K_pool, V_pool, block_table, k_lens, window_size, returning_l_m=False, k_scale=None,
+                            v_scale=None):
+    """``paged_1d`` under a sliding window for any number of queries (chunked prefill of local-attention layers
+    against the paged cache): the same pools, block table, lengths, empty rows, FP8 pools and scales, with Nq >= 1
+    unbounded and 1 <= g <= 128.  ``window_size`` = W is a required int >= 1 (clamped to 2^31 - 1), and the rule,
+    the blocks and the two bit-for-bit delegations (``W >= cap``: ``paged_prefill_1d(..., tail_causal=True)``; one
+    block: ``paged_1d(..., tail_causal=True, window_size=W)``) are ``ragged_window_prefill_1d``'s.  The new tokens'
+    keys are appended first (``paged_append_1d``), so that ``k_lens`` counts them.
+
+    Lengths, table and scales are read on the device, never on the host: no synchronisation, and the call may be
+    replayed from a captured graph after any of them was overwritten in place.  Queries of a mixed batch are
+    right-aligned in the Nq slots.  With ``lo = max(0, k_lens[s] - Nq - W + 1)``, the call's lowest window start:
+    keys below ``lo // 64 * 64`` are never read, and the table entries of pages wholly below that key are never
+    loaded, like those past the last live page, so such pages may be freed and reused and their entries may hold
+    anything; loaded entries are clamped.  The up to 63 keys between ``lo // 64 * 64`` and ``lo`` are read and
+    masked, so they must be finite.  Attention sinks compose from a second call and ``merge_partials``, as in
+    ``paged_1d``.
+
+    Inference only; float16 only; the page size must be a multiple of 64; outside the envelope the call raises
+    NotImplementedError.  Returns ``O`` or ``(O, l, m)``."""
+    return _paged_forward("paged_window_prefill_1d", True, Q, K_pool, V_pool, block_table, k_lens, True, returning_l_m,
+                          k_scale, v_scale, _required_window(window_size))
 
 
 def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_causal, returning_l_m, k_scale, v_scale,
