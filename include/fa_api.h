@@ -545,6 +545,55 @@ int fa_forward_paged_window_prefill_fp8(void* stream, const fa_problem* p, int32
                                         void* O, void* l, void* m,
                                         void* workspace, size_t workspace_bytes);
 
+/* MLA decode (multi-head latent attention in absorbed form) over a PAGED LATENT cache: `heads` query heads of a
+ * sequence attend ONE K/V head whose keys are the cached latent vectors (d channels, e.g. 576 = 512 latent + 64
+ * rotary) and whose VALUES are the first v_d channels of the same vectors.  There is one pool and no V pool.
+ *   p: dtype FA_F16, seq_dims 1, policy FA_FULL; d = the score channels C, v_d = the value channels,
+ *     b = sequences * heads, q_seq[0] = nq, k_seq[0] = nk = max_pages * page, the CAPACITY.
+ *   Q [sequences][heads][d][nq], O [sequences][heads][v_d][nq] fp16; l [sequences][heads][nq] fp32, m the same fp16.
+ *   KV_pool [num_pages][d][page] fp16, the key axis contiguous, 16-byte aligned: a page holds `page` consecutive
+ *     positions of one sequence.  The value of key j is channels [0, v_d) of its vector.
+ *   block_table (DEVICE int32 [sequences][max_pages]), k_lens (DEVICE int32 [sequences]), tail_causal and the empty
+ *     rows: fa_forward_paged's contract with kv_per_len = 1.  A length is clamped to [0, nk]; only the table entries
+ *     of pages that hold a live key are loaded, one tile ahead of their use, and each is clamped to
+ *     [0, num_pages - 1] before it forms an address (page bases are 64-bit: a pool may pass 4 GB); sequences may
+ *     share pages; the host reads neither array, and either may be overwritten in place between replays of a
+ *     captured graph.  Whatever the pool holds past a length (NaN and Inf included) does not reach a result.
+ *   softmax_scale: a host float that multiplies the scores (MLA: 1 / sqrt(192), not 1 / sqrt(d)); it is folded into
+ *     the fp32 pre-scale of Q.  A launch argument: fixed in a captured graph.  l and m are in the units of the
+ *     SCALED scores, as fa_forward's are, so (O, l, m) compose with fa_merge_partials.
+ *
+ * Envelope: fp16, seq_dims == 1, d % 64 == 0, 64 <= d <= 576, v_d % 64 == 0, 64 <= v_d <= min(d, 512),
+ *   page % 64 == 0, 1 <= heads <= 128, nq >= 1, nk >= 1, R = heads * P <= 512 with P the smallest power of two
+ *   >= nq (row rho of the fold is query rho % P of head rho / P), and launch grids below 2^31 workgroups.  A
+ *   well-formed problem outside it: FA_ERR_UNSUPPORTED, nothing written; there is no gather fallback.
+ * FA_ERR_INVALID_ARGUMENT with text in fa_last_error(): fa_validate's errors, heads < 1, b % heads != 0,
+ *   policy != FA_FULL, page < 1, nk % page != 0, max_pages < 1, max_pages * page != nk, num_pages < 1, a
+ *   softmax_scale that is not positive and finite, and with b > 0 a null pointer or a KV_pool that is not 16-byte
+ *   aligned.
+ *
+ * fa_forward_mla_paged_plan (host-only): out = {key chunks (0 outside the envelope), keys per chunk, P, R, blocks of
+ *   64 rows}.  The chunks follow fa_forward_ragged_plan's formula over the capacity: chunk = max(ceil(nk / 64)
+ *   rounded up to 64 keys, 512 for R <= 64 or 1024 above), chunks = ceil(nk / chunk).  A pure function of the
+ *   problem WITHOUT b, the lengths or the table: a short sequence in a large cache launches the capacity's chunks,
+ *   and those at or past its length return at once.
+ * fa_forward_mla_paged_workspace_bytes (host-only): (b / heads) * blocks * chunks * 64 * (v_d + 3) floats rounded
+ *   up to 256 bytes (linear in b / heads and otherwise a function of the plan alone); 0 outside the envelope.
+ * fa_forward_mla_paged: one partial workgroup per (sequence, row block, chunk) writes fp32 partials, a merge folds
+ *   a row's live chunks in chunk order without atomics: a sequence's bits do not depend on b, on the other
+ *   sequences' lengths or on where the table puts its pages.  A smaller workspace returns
+ *   FA_ERR_WORKSPACE_TOO_SMALL with nothing written; b == 0 returns FA_OK with nothing launched.
+ * Not here: a fused append for the single pool (store KV_pool[block_table[s][pos / page]][:][pos % page]), FP8
+ *   latent pools, sliding windows, tree masks, query blocking beyond R <= 512 and a ragged (unpaged) twin. */
+int fa_forward_mla_paged_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[5]);
+size_t fa_forward_mla_paged_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page);
+int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads,
+                         const void* Q, const void* KV_pool,
+                         const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                         const int32_t* k_lens, int32_t tail_causal, float softmax_scale,
+                         void* O, void* l, void* m,
+                         void* workspace, size_t workspace_bytes);
+
 /* Fused K/V append: the write side of the four caches above. New tokens' keys and values are stored IN PLACE into a
  * ragged cache or into page pools, fp16 or FP8, by one kernel launch enqueued on `stream`: a forward enqueued after it
  * on that stream sees the tokens.  Every control value is device data; the host reads nothing and does not

@@ -76,6 +76,9 @@ EXPORTED_SYMBOLS = (
     "fa_forward_paged_window_prefill",
     "fa_forward_ragged_window_prefill_fp8",
     "fa_forward_paged_window_prefill_fp8",
+    "fa_forward_mla_paged_plan",
+    "fa_forward_mla_paged_workspace_bytes",
+    "fa_forward_mla_paged",
     "fa_append_ragged",
     "fa_append_paged",
     "fa_append_ragged_fp8",
@@ -223,6 +226,16 @@ def _declare(lib):
                                                   + [vp, i32, vp if form == "tree" else i32]
                                                   + [vp, vp, vp, vp, ctypes.c_size_t])
                 getattr(lib, forward).restype = ctypes.c_int
+    # MLA decode over a paged latent cache: (heads, page) are the plan functions' own arguments; the forward takes
+    # one pool, the table's pieces, the lengths, tail_causal and softmax_scale.  (Absent as above.)
+    if hasattr(lib, "fa_forward_mla_paged"):
+        lib.fa_forward_mla_paged_plan.argtypes = [P, i32, i32, ctypes.POINTER(i32)]
+        lib.fa_forward_mla_paged_plan.restype = ctypes.c_int
+        lib.fa_forward_mla_paged_workspace_bytes.argtypes = [P, i32, i32]
+        lib.fa_forward_mla_paged_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_forward_mla_paged.argtypes = [vp, P, i32, vp, vp, vp, i32, i32, i64, vp, i32, ctypes.c_float,
+                                             vp, vp, vp, vp, ctypes.c_size_t]
+        lib.fa_forward_mla_paged.restype = ctypes.c_int
     # The fused K/V appends (include/fa_api.h): the same pieces again, the caches written instead of read; (k_scale,
     # v_scale) after an FP8 cache, (block_table, max_pages, page, num_pages) after a paged one.  (Absent as above.)
     for cache in DECODE_CACHES:

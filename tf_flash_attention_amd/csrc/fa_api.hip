@@ -1242,6 +1242,123 @@ int fa_forward_paged_tree_fp8(void* stream, const fa_problem* p, int32_t kv_grou
   return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, nullptr, false, true, draft_mask}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
 }
 
+// ---- MLA decode over a paged latent cache (include/fa_api.h; fa_fwd_f16_mla.hip): `heads` query
+// heads against one K/V head whose values are the first v_d channels of its keys.  The plan: the heads' P query
+// slots folded into R = heads * P rows, blocks of 64 rows, and ragged_plan's chunk formula over the capacity (a
+// 512-key minimum up to 64 rows, 1024 above; at most 64 chunks).  A pure function of the problem without b.
+constexpr int32_t kMlaMaxC = 576, kMlaMaxV = 512, kMlaMaxHeads = 128, kMlaMaxRows = 512, kMlaBlockRows = 64;
+
+struct MlaPlan {
+  int32_t nchunks, chunk, pitch, rows, nrb;
+};
+
+static int check_mla(const fa_problem* p, int32_t heads, int32_t page) {
+  const int st = fa_validate(p);
+  if (st != FA_OK) return st;
+  if (heads < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: heads must be >= 1");
+  if (p->b % heads != 0)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: the batch size b = " + std::to_string(p->b) +
+                                                  " is not a multiple of heads = " + std::to_string(heads));
+  if (p->policy != FA_FULL)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: the policy must be FA_FULL (the lengths and tail_causal are the mask)");
+  if (page < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: page must be >= 1");
+  if (p->seq_dims == 1 && p->k_seq[0] % page != 0)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: the capacity k_seq[0] = " + std::to_string(p->k_seq[0]) +
+                                                  " is not a multiple of page = " + std::to_string(page));
+  return FA_OK;
+}
+
+// (after check_mla)
+static MlaPlan mla_plan(const fa_problem* p, int32_t heads, int32_t page) {
+  MlaPlan s = {};
+  const int64_t nq = p->q_seq[0];
+  if (p->seq_dims == 1 && nq >= 1) {
+    s.pitch = next_pow2((int32_t)nq);
+    s.rows = (int64_t)heads * s.pitch <= 0x7fffffff ? heads * s.pitch : 0x7fffffff;
+    s.nrb = (int32_t)(((int64_t)s.rows + kMlaBlockRows - 1) / kMlaBlockRows);
+  }
+  const int32_t nk = p->k_seq[0];
+  const bool inside = p->dtype == FA_F16 && p->seq_dims == 1 && p->d % 64 == 0 && p->d >= 64 && p->d <= kMlaMaxC &&
+                      p->v_d % 64 == 0 && p->v_d >= 64 && p->v_d <= kMlaMaxV && p->v_d <= p->d && page % kSplitTile == 0 &&
+                      heads <= kMlaMaxHeads && nq >= 1 && (int64_t)heads * s.pitch <= kMlaMaxRows && nk >= 1;
+  if (!inside) return s;
+  const int32_t min_chunk = s.rows <= 64 ? 512 : 1024;
+  const int32_t capped = ((nk + kSplitMaxChunks - 1) / kSplitMaxChunks + kSplitTile - 1) / kSplitTile * kSplitTile;
+  s.chunk = capped > min_chunk ? capped : min_chunk;
+  s.nchunks = (nk + s.chunk - 1) / s.chunk;
+  return s;
+}
+
+static size_t mla_ws_bytes(const fa_problem* p, int32_t heads, const MlaPlan& s) {
+  return align_up((size_t)(p->b / heads) * (size_t)s.nrb * (size_t)s.nchunks *
+                  (size_t)fa::fewq_record_floats(p->v_d, kMlaBlockRows) * sizeof(float));
+}
+
+int fa_forward_mla_paged_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[5]) {
+  const int st = check_mla(p, heads, page);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const MlaPlan s = mla_plan(p, heads, page);
+  out[0] = s.nchunks; out[1] = s.chunk; out[2] = s.pitch; out[3] = s.rows; out[4] = s.nrb;
+  return FA_OK;
+}
+
+size_t fa_forward_mla_paged_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page) {
+  if (check_mla(p, heads, page) != FA_OK) return 0;
+  const MlaPlan s = mla_plan(p, heads, page);
+  return s.nchunks ? mla_ws_bytes(p, heads, s) : 0;
+}
+
+int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
+                         const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                         const int32_t* k_lens, int32_t tail_causal, float softmax_scale, void* O, void* l, void* m,
+                         void* workspace, size_t workspace_bytes) {
+  const int st = check_mla(p, heads, page);
+  if (st != FA_OK) return st;
+  if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: max_pages must be >= 1");
+  if (p->seq_dims == 1 && (int64_t)max_pages * page != p->k_seq[0])
+    return set_error(FA_ERR_INVALID_ARGUMENT,
+                     "MLA paged forward: max_pages * page = " + std::to_string((int64_t)max_pages * page) +
+                         " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
+  if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: num_pages must be >= 1");
+  if (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale))
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: softmax_scale must be positive and finite");
+  const MlaPlan mp = mla_plan(p, heads, page);
+  if (mp.nchunks == 0)
+    return set_error(FA_ERR_UNSUPPORTED,
+                     "MLA paged forward: outside the envelope (fp16, 1d sequences, d % 64 == 0, 64 <= d <= 576, "
+                     "v_d % 64 == 0, 64 <= v_d <= min(d, 512), page % 64 == 0, 1 <= heads <= 128, nq >= 1, "
+                     "heads * pitch <= 512, nk >= 1)");
+  const int64_t seqs = p->b / heads, nq = p->q_seq[0];
+  if (seqs * mp.nrb * mp.nchunks > 0x7fffffff || (seqs * p->v_d * heads * nq + 255) / 256 > 0x7fffffff)
+    return set_error(FA_ERR_UNSUPPORTED, "MLA paged forward: b = " + std::to_string(p->b) + " needs a launch grid of 2^31 workgroups or more");
+  if (!workspace || workspace_bytes < mla_ws_bytes(p, heads, mp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "forward workspace is smaller than fa_forward_mla_paged_workspace_bytes()");
+  FA_DIAG_COUNT(0);
+  if (p->b == 0) return FA_OK;
+  if (!Q || !O || !l || !m) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null Q, O, l or m");
+  if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
+  if (!block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null block_table");
+  if (!KV_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null KV_pool");
+  if (reinterpret_cast<uintptr_t>(KV_pool) & 15)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: KV_pool must be 16-byte aligned");
+  fa::MlaArgs ma = {};
+  fill_split(p, {mp.nchunks, mp.chunk, 0, p->k_seq[0], 0}, &ma.s);
+  fa::FwdArgs& a = ma.s.f;
+  a.Q = Q; a.K = KV_pool; a.V = nullptr; a.O = O; a.l = l; a.m = m;
+  a.b = seqs;
+  a.scale = (double)softmax_scale;
+  ma.s.ws = static_cast<float*>(workspace);
+  ma.block_table = block_table; ma.k_lens = k_lens;
+  ma.heads = heads; ma.pitch = mp.pitch; ma.log2_pitch = ilog2(mp.pitch); ma.nrb = mp.nrb;
+  ma.max_pages = max_pages; ma.page = page;
+  ma.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
+  ma.tail_causal = tail_causal != 0;
+  const hipError_t e = fa::launch_fwd_f16_mla(ma, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+  return FA_OK;
+}
+
 // ---- the fused K/V append of the same four caches (include/fa_api.h): every check on the host
 // before any device call, then one launch of fa_cache_append.hip's kernel.  No workspace, no plan.
 static int cache_append(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new,
@@ -1601,7 +1718,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill, tree-masked draft decode, sliding-window prefill), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill, tree-masked draft decode, sliding-window prefill, MLA paged latent decode), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
 }
 
 }  // extern "C"

@@ -162,6 +162,25 @@ struct AppendArgs {
   int32_t slice_blocks;        // 256-thread blocks per (sequence, head): ceil((d + v_d) * chunks / 256)
 };
 
+// MLA decode over a paged latent cache (fa_fwd_f16_mla.hip): `heads` query heads against ONE K/V head whose keys
+// are the pool's vectors and whose values are their first v_d channels.  s.f: Q [sequences][heads][d][nq], K the
+// POOL [num_pages][d][page] halfs (V is not read), O / l / m of sequences * heads slices, b = SEQUENCES, scale =
+// softmax_scale, rule.q.n = nq and rule.k.n = the capacity max_pages * page.  s.ws: the records
+// [sequences][nrb][nchunks] of stride 64; s.nchunks / s.chunk the plan; s.k_first = 0, s.k_end = the capacity.
+struct MlaArgs {
+  SplitArgs s;
+  const int32_t* block_table;  // device: [sequences][max_pages], loaded entries clamped to [0, last_page]
+  const int32_t* k_lens;       // device: [sequences], clamped to [0, capacity]
+  int32_t heads;               // Hq, 1 .. 128
+  int32_t pitch, log2_pitch;   // rows per head: the smallest power of two >= nq; row rho = head * pitch + query
+  int32_t nrb;                 // blocks of 64 folded rows: ceil(heads * pitch / 64), <= 8
+  int32_t max_pages, page, last_page;
+  int32_t tail_causal;         // != 0: query i sees keys j <= len - nq + i
+};
+// one partial workgroup per (sequence, row block, key chunk) and one merge thread per output element; the caller
+// has checked that both grids fit
+hipError_t launch_fwd_f16_mla(const MlaArgs& ma, hipStream_t s);
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;

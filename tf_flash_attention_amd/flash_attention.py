@@ -33,6 +33,12 @@ that says which page holds which keys of which sequence (also read by the kernel
 
     paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False)
 
+and MLA decode (multi-head latent attention in absorbed form: 16 to 128 query heads against one K/V head of up to
+576 channels whose values are its first ``v_channels`` channels) over a paged latent cache ``[num_pages, C, page]``::
+
+    mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False, softmax_scale=None,
+                 returning_l_m=False)
+
 Tensors are ``torch`` tensors on a ROCm device in the reference's channel-first
 layout ``batch_shape + (C, *seq_shape)``.  Each call returns ``O`` or
 ``(O, l, m)``; autograd flows through ``O`` only (gradients of ``l``/``m`` are
@@ -66,6 +72,7 @@ __all__ = [
     "grouped_1d", "grouped_2d", "attention_forward_grouped",
     "ragged_1d", "paged_1d", "ragged_prefill_1d", "paged_prefill_1d", "quantize_kv_fp8",
     "ragged_append_1d", "paged_append_1d", "ragged_window_prefill_1d", "paged_window_prefill_1d",
+    "mla_paged_1d",
 ]
 
 
@@ -1122,6 +1129,125 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
                                       mask.data_ptr() if mask is not None else int(bool(tail_causal)) if window is None
                                       else window, O.data_ptr(),
                                       l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    return (O, l, m) if returning_l_m else O
+
+
+# ----------------------------------------------------------------------------
+# MLA decode over a paged latent cache
+
+_MLA_PAGE_CONDITION = "the page size (the last axis of KV_pool) must be a multiple of 64 keys"
+_MLA_ENVELOPE = ("float16, C % 64 == 0 and 64 <= C <= 576, v_channels % 64 == 0 and 64 <= v_channels <= min(C, 512), "
+                 "1 <= Hq <= 128, Nq >= 1, Hq * next_pow2(Nq) <= 512")
+
+
+def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False, softmax_scale=None,
+                 returning_l_m=False):
+    """Decode of multi-head latent attention (MLA: DeepSeek-V2/V3 style stacks) in absorbed form over a paged
+    LATENT cache: Q ``batch + (Hq, C, Nq)``, ``KV_pool`` ``[num_pages, C, page]`` (one K/V head, the key axis
+    contiguous, a page holding ``page`` consecutive positions of one sequence), ``block_table`` int32
+    ``batch + (max_pages,)`` and ``k_lens`` int32 of shape ``batch``, both on the device of Q.  The key of position j
+    is its cached vector (C channels, e.g. 576 = 512 latent + 64 rotary); its VALUE is channels ``[0, v_channels)``
+    of the same vector, so there is no V pool, and a tile of the pool is read from memory once for both roles.
+
+    ``block_table`` and ``k_lens`` follow ``paged_1d``'s contract: the host never reads them; a length is clamped
+    to ``[0, max_pages * page]``; table entries of pages without a live key are never loaded, loaded ones are
+    clamped to ``[0, num_pages - 1]``; sequences may share pages; a captured graph may be replayed after either
+    tensor was overwritten in place.  Whatever the pool holds past a length (NaN, Inf) does not reach a result.
+    ``tail_causal`` is ``ragged_1d``'s rule: the Nq queries are the sequence's last Nq positions and query i sees
+    keys ``j <= len - Nq + i`` (multi-token prediction, speculative decode).  Rows that see no key give O = 0,
+    l = 0 and every byte of m 0xFA.
+
+    ``softmax_scale`` is a host float that multiplies the scores; ``None`` means ``1 / sqrt(C)``.  MLA's own scale
+    is ``1 / sqrt(192)`` (the un-absorbed head width), not ``1 / sqrt(576)``.  It is a launch argument and therefore
+    FIXED in a captured graph.  ``l`` (float32) and ``m`` (float16) are in the units of the scaled scores, so
+    ``(O, l, m)`` compose with ``merge_partials``.
+
+    A new token's latent vector is appended on the device before the call, so that ``k_lens`` counts it::
+
+        KV_pool[block_table[s, pos // page], :, pos % page] = new        # new: [C], pos = k_lens[s] - 1
+
+    Envelope: float16, C % 64 == 0 and 64 <= C <= 576, v_channels % 64 == 0 and 64 <= v_channels <= min(C, 512),
+    1 <= Hq <= 128, Nq >= 1, Hq * next_pow2(Nq) <= 512, page % 64 == 0, capacity <= 2^30 keys; outside it ``NotImplementedError``
+    names the condition: there is no fallback that would read the lengths on the host.  Inference only.  Not here: a
+    fused append for the single pool, FP8 latent pools, sliding windows, tree masks, query blocking for more rows and
+    a ragged twin.  Returns ``O`` ``batch + (Hq, v_channels, Nq)`` or ``(O, l, m)``."""
+    what = "mla_paged_1d"
+    if len(KV_pool.shape) != 3:
+        raise InvalidArgumentError("KV_pool should be [num_pages, channels, page], but KV_pool_shape = "
+                                   + _shape_str(KV_pool.shape) + " was received")
+    num_pages, k_ch, page = (int(x) for x in KV_pool.shape)
+    if len(Q.shape) < 3:
+        raise InvalidArgumentError("Q should be batch + (Hq, C, Nq), but Q_shape = " + _shape_str(Q.shape)
+                                   + " was received")
+    batch, hq, q_ch, nq = tuple(Q.shape[:-3]), int(Q.shape[-3]), int(Q.shape[-2]), int(Q.shape[-1])
+    if q_ch != k_ch:
+        raise InvalidArgumentError("The channels of Q and KV_pool should be the same, but Q_shape = "
+                                   + _shape_str(Q.shape) + ", KV_pool_shape = " + _shape_str(KV_pool.shape)
+                                   + " were received")
+    if num_pages < 1 or hq < 1:
+        raise InvalidArgumentError("Q should have a head and the pool should hold a page, but Q_shape = "
+                                   + _shape_str(Q.shape) + ", KV_pool_shape = " + _shape_str(KV_pool.shape)
+                                   + " were received")
+    if isinstance(v_channels, bool) or not isinstance(v_channels, int) or v_channels < 1:
+        raise InvalidArgumentError(f"v_channels must be a positive int, got {v_channels!r}")
+    dt = _dtype_id(Q, True)
+    if KV_pool.dtype != Q.dtype:
+        raise TypeError(f"Q and KV_pool must share one dtype, got {Q.dtype} and {KV_pool.dtype}")
+    for name, t in (("block_table", block_table), ("k_lens", k_lens)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if tuple(block_table.shape[:-1]) != batch or len(block_table.shape) != len(batch) + 1 or block_table.shape[-1] < 1:
+        raise InvalidArgumentError("The shape of block_table should be the batch shape without the heads plus "
+                                   "(max_pages,), but block_table_shape = " + _shape_str(block_table.shape)
+                                   + ", batch_shape = " + _shape_str(batch) + " were received")
+    if tuple(k_lens.shape) != batch:
+        raise InvalidArgumentError("The shape of k_lens should be the batch shape without the heads, but k_lens_shape = "
+                                   + _shape_str(k_lens.shape) + ", batch_shape = " + _shape_str(batch)
+                                   + " were received")
+    if block_table.device != Q.device or k_lens.device != Q.device:
+        raise InvalidArgumentError("block_table and k_lens must be on the device of Q and KV_pool")
+    if softmax_scale is None:
+        softmax_scale = 1.0 / float(q_ch) ** 0.5
+    softmax_scale = float(softmax_scale)
+    if not (softmax_scale > 0.0 and softmax_scale != float("inf")):
+        raise InvalidArgumentError(f"softmax_scale must be positive and finite, got {softmax_scale!r}")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, KV_pool)):
+        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
+                           "detach its inputs")
+    if page < 1 or page % 64 != 0:
+        raise NotImplementedError(what + ": " + _MLA_PAGE_CONDITION + ", got page = " + str(page))
+    if v_channels > q_ch:
+        raise NotImplementedError(what + ": the values are channels of the cached vectors, v_channels <= C, got "
+                                  f"v_channels = {v_channels}, C = {q_ch}")
+    max_pages = int(block_table.shape[-1])
+    cap = max_pages * page
+    if cap > 2 ** 30:
+        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_channels)
+    L = _lib.lib()
+    plan = (ctypes.c_int32 * 5)()
+    st = L.fa_forward_mla_paged_plan(prob, hq, page, plan)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    if plan[0] == 0:
+        raise NotImplementedError(what + ": outside the envelope (" + _MLA_ENVELOPE + "; and " + _MLA_PAGE_CONDITION
+                                  + "), got Q_shape = " + _shape_str(Q.shape) + ", KV_pool_shape = "
+                                  + _shape_str(KV_pool.shape) + ", v_channels = " + str(v_channels))
+    _check_device_tensors(Q, KV_pool)
+    Q, KV_pool = Q.contiguous(), KV_pool.contiguous()
+    block_table, k_lens = block_table.contiguous(), k_lens.contiguous()
+    O = torch.empty(batch + (hq, v_channels, nq), dtype=Q.dtype, device=Q.device)
+    l = torch.empty(batch + (hq, nq), dtype=torch.float32, device=Q.device)
+    m = torch.empty(batch + (hq, nq), dtype=Q.dtype, device=Q.device)
+    ws_bytes = int(L.fa_forward_mla_paged_workspace_bytes(prob, hq, page))
+    with torch.cuda.device(Q.device):
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
+        st = L.fa_forward_mla_paged(_stream_handle(Q.device), prob, hq, Q.data_ptr(), KV_pool.data_ptr(),
+                                    block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(),
+                                    int(bool(tail_causal)), softmax_scale, O.data_ptr(), l.data_ptr(), m.data_ptr(),
+                                    ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
