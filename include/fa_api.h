@@ -583,8 +583,19 @@ int fa_forward_paged_window_prefill_fp8(void* stream, const fa_problem* p, int32
  *   a row's live chunks in chunk order without atomics: a sequence's bits do not depend on b, on the other
  *   sequences' lengths or on where the table puts its pages.  A smaller workspace returns
  *   FA_ERR_WORKSPACE_TOO_SMALL with nothing written; b == 0 returns FA_OK with nothing launched.
- * Not here: a fused append for the single pool (store KV_pool[block_table[s][pos / page]][:][pos % page]), FP8
- *   latent pools, sliding windows, tree masks, query blocking beyond R <= 512 and a ragged (unpaged) twin. */
+ * fa_forward_mla_paged_fp8: the same over an FP8 latent pool.  KV_pool8 is [num_pages][d][page] OCP e4m3fn bytes,
+ *   16-byte aligned; kv_scale is a DEVICE pointer to one fp32 value (null: 1.0), and the true cached vector is
+ *   kv_scale * decode(byte).  The plan, the workspace size, the envelope and every refusal are fa_forward_mla_paged's:
+ *   call fa_forward_mla_paged_plan and _workspace_bytes.  Only the kernel reads the scale, so a captured graph may be
+ *   replayed after it was overwritten in place.  In the tile that holds a length the bytes at or past it are cleared
+ *   to 0x00 before they are converted, so the NaN codes 0x7F / 0xFF past a length reach no result.  The bytes are
+ *   converted exactly to the fp16 image the fp16 kernel builds, with the power of two 2^e nearest kv_scale
+ *   (-8 <= e <= 7) inside the conversion; the remainder kv_scale / 2^e multiplies the fp32 Q pre-scale and the fp32
+ *   accumulator.  With kv_scale null, 1.0 or any 2^e inside the clamp the results are BITWISE fa_forward_mla_paged's
+ *   on the fp16 pool of the values 2^e * decode(byte).  A kv_scale that is zero, negative, Inf or NaN gives NaN in O,
+ *   as the FP8 caches above do.
+ * Not here: per-block or per-channel-group scales, an fp16 rotary tail beside FP8 latents, sliding windows, tree
+ *   masks, query blocking beyond R <= 512 and a ragged (unpaged) twin.  The write side: fa_append_mla_paged below. */
 int fa_forward_mla_paged_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[5]);
 size_t fa_forward_mla_paged_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page);
 int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads,
@@ -593,6 +604,12 @@ int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads,
                          const int32_t* k_lens, int32_t tail_causal, float softmax_scale,
                          void* O, void* l, void* m,
                          void* workspace, size_t workspace_bytes);
+int fa_forward_mla_paged_fp8(void* stream, const fa_problem* p, int32_t heads,
+                             const void* Q, const void* KV_pool8,
+                             const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                             const int32_t* k_lens, int32_t tail_causal, float softmax_scale, const float* kv_scale,
+                             void* O, void* l, void* m,
+                             void* workspace, size_t workspace_bytes);
 
 /* Fused K/V append: the write side of the four caches above. New tokens' keys and values are stored IN PLACE into a
  * ragged cache or into page pools, fp16 or FP8, by one kernel launch enqueued on `stream`: a forward enqueued after it
@@ -651,6 +668,21 @@ int fa_append_paged_fp8(void* stream, int64_t sequences,
                         const float* k_scale, const float* v_scale,
                         const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
                         const int32_t* k_lens, const int32_t* new_lens);
+
+/* The same for the latent pool of fa_forward_mla_paged (fp16) and fa_forward_mla_paged_fp8: KV_new
+ * [sequences][d][n_new] fp16, KV_pool [num_pages][d][page].  It is fa_append_paged's contract and kernel with
+ * kv_heads = 1 and no V rows: k_lens after the append, new_lens right-aligned, only the new positions written, only
+ * the entries of pages that receive one loaded and each clamped, every control value read on the device.  _fp8 stores
+ * e4m3fn(fp32(x) / kv_scale[0]) as above; kv_scale is a DEVICE pointer to one fp32 value, null means 1.0.  The errors
+ * are fa_append_paged's under the name "MLA paged append" (d or nk < 1; a null KV_new or pool where there is work). */
+int fa_append_mla_paged(void* stream, int64_t sequences, int32_t d, int32_t n_new, int32_t nk,
+                        const void* KV_new, void* KV_pool,
+                        const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                        const int32_t* k_lens, const int32_t* new_lens);
+int fa_append_mla_paged_fp8(void* stream, int64_t sequences, int32_t d, int32_t n_new, int32_t nk,
+                            const void* KV_new, void* KV_pool8, const float* kv_scale,
+                            const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                            const int32_t* k_lens, const int32_t* new_lens);
 
 /* Bytes of device scratch fa_backward needs (replaces the Br_occupancy temp,
  * flash_attention_backward.cc:274-283): the D = rowsum(dO * O) rows and the lse rows,

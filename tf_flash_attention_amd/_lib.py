@@ -79,10 +79,13 @@ EXPORTED_SYMBOLS = (
     "fa_forward_mla_paged_plan",
     "fa_forward_mla_paged_workspace_bytes",
     "fa_forward_mla_paged",
+    "fa_forward_mla_paged_fp8",
     "fa_append_ragged",
     "fa_append_paged",
     "fa_append_ragged_fp8",
     "fa_append_paged_fp8",
+    "fa_append_mla_paged",
+    "fa_append_mla_paged_fp8",
     "fa_backward_workspace_bytes",
     "fa_backward",
     "fa_backward_split_plan",
@@ -236,6 +239,16 @@ def _declare(lib):
         lib.fa_forward_mla_paged.argtypes = [vp, P, i32, vp, vp, vp, i32, i32, i64, vp, i32, ctypes.c_float,
                                              vp, vp, vp, vp, ctypes.c_size_t]
         lib.fa_forward_mla_paged.restype = ctypes.c_int
+    # its FP8 latent pool (kv_scale after softmax_scale) and the appends into the single pool, fp16 and FP8 (kv_scale
+    # after the pool): the plan and the workspace are the fp16 forward's.  (Absent as above.)
+    if hasattr(lib, "fa_forward_mla_paged_fp8"):
+        lib.fa_forward_mla_paged_fp8.argtypes = [vp, P, i32, vp, vp, vp, i32, i32, i64, vp, i32, ctypes.c_float, vp,
+                                                 vp, vp, vp, vp, ctypes.c_size_t]
+        lib.fa_forward_mla_paged_fp8.restype = ctypes.c_int
+        for fp8 in (False, True):
+            append = getattr(lib, "fa_append_mla_paged" + ("_fp8" if fp8 else ""))
+            append.argtypes = [vp, i64, i32, i32, i32, vp, vp] + ([vp] if fp8 else []) + [vp, i32, i32, i64, vp, vp]
+            append.restype = ctypes.c_int
     # The fused K/V appends (include/fa_api.h): the same pieces again, the caches written instead of read; (k_scale,
     # v_scale) after an FP8 cache, (block_table, max_pages, page, num_pages) after a paged one.  (Absent as above.)
     for cache in DECODE_CACHES:

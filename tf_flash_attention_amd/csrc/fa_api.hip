@@ -1309,10 +1309,12 @@ size_t fa_forward_mla_paged_workspace_bytes(const fa_problem* p, int32_t heads, 
   return s.nchunks ? mla_ws_bytes(p, heads, s) : 0;
 }
 
-int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
-                         const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
-                         const int32_t* k_lens, int32_t tail_causal, float softmax_scale, void* O, void* l, void* m,
-                         void* workspace, size_t workspace_bytes) {
+// both pool encodings: every check is the fp16 entry point's (the plan does not know the encoding); `fp8` takes
+// the pool as e4m3fn bytes with the device scale `kv_scale` (null: 1.0), which only the kernel reads
+static int forward_mla(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool, bool fp8,
+                       const float* kv_scale, const int32_t* block_table, int32_t max_pages, int32_t page,
+                       int64_t num_pages, const int32_t* k_lens, int32_t tail_causal, float softmax_scale, void* O,
+                       void* l, void* m, void* workspace, size_t workspace_bytes) {
   const int st = check_mla(p, heads, page);
   if (st != FA_OK) return st;
   if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: max_pages must be >= 1");
@@ -1354,21 +1356,40 @@ int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads, const
   ma.max_pages = max_pages; ma.page = page;
   ma.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
   ma.tail_causal = tail_causal != 0;
-  const hipError_t e = fa::launch_fwd_f16_mla(ma, static_cast<hipStream_t>(stream));
+  const hipError_t e = fp8 ? fa::launch_fwd_f16_mla_fp8(fa::MlaFp8Args{ma, kv_scale}, static_cast<hipStream_t>(stream))
+                          : fa::launch_fwd_f16_mla(ma, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
   return FA_OK;
+}
+
+int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
+                         const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                         const int32_t* k_lens, int32_t tail_causal, float softmax_scale, void* O, void* l, void* m,
+                         void* workspace, size_t workspace_bytes) {
+  return forward_mla(stream, p, heads, Q, KV_pool, false, nullptr, block_table, max_pages, page, num_pages, k_lens,
+                     tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_mla_paged_fp8(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool8,
+                             const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                             const int32_t* k_lens, int32_t tail_causal, float softmax_scale, const float* kv_scale,
+                             void* O, void* l, void* m, void* workspace, size_t workspace_bytes) {
+  return forward_mla(stream, p, heads, Q, KV_pool8, true, kv_scale, block_table, max_pages, page, num_pages, k_lens,
+                     tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
 }
 
 // ---- the fused K/V append of the same four caches (include/fa_api.h): every check on the host
 // before any device call, then one launch of fa_cache_append.hip's kernel.  No workspace, no plan.
 static int cache_append(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new,
                         int32_t nk, const void* K_new, const void* V_new, void* K, void* V, const Kv8* kv8,
-                        const PagedPart* pg, const int32_t* k_lens, const int32_t* new_lens) {
-  const std::string name = pg ? "paged append" : "ragged append";
+                        const PagedPart* pg, const int32_t* k_lens, const int32_t* new_lens, bool latent = false) {
+  // (latent: the single pool of the MLA forward, [num_pages][d][page] = one head and no V rows; its entry points pass
+  // the pool and the new vectors as K and as V, and the kernel, which has d + v_d = d rows, touches them as K only)
+  const std::string name = latent ? "MLA paged append" : pg ? "paged append" : "ragged append";
   if (sequences < 0 || n_new < 0)
     return set_error(FA_ERR_INVALID_ARGUMENT, name + ": sequences = " + std::to_string(sequences) + " and n_new = " +
                                                   std::to_string(n_new) + " must not be negative");
-  if (kv_heads < 1 || d < 1 || v_d < 1 || nk < 1)
+  if (kv_heads < 1 || d < 1 || v_d < (latent ? 0 : 1) || nk < 1)
     return set_error(FA_ERR_INVALID_ARGUMENT, name + ": kv_heads = " + std::to_string(kv_heads) + ", d = " + std::to_string(d) +
                                                   ", v_d = " + std::to_string(v_d) + " and nk = " + std::to_string(nk) +
                                                   " must be >= 1");
@@ -1384,8 +1405,9 @@ static int cache_append(void* stream, int64_t sequences, int32_t kv_heads, int32
       return set_error(FA_ERR_UNSUPPORTED, name + ": outside the envelope (page % 64 == 0), got page = " + std::to_string(pg->page));
   }
   if (sequences == 0 || n_new == 0) return FA_OK;
-  if (!K_new || !V_new) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": null K_new or V_new");
-  if (!K || !V) return set_error(FA_ERR_INVALID_ARGUMENT, name + (pg ? ": null K_pool or V_pool" : ": null K or V"));
+  if (!K_new || !V_new) return set_error(FA_ERR_INVALID_ARGUMENT, name + (latent ? ": null KV_new" : ": null K_new or V_new"));
+  if (!K || !V)
+    return set_error(FA_ERR_INVALID_ARGUMENT, name + (latent ? ": null KV_pool" : pg ? ": null K_pool or V_pool" : ": null K or V"));
   if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": null k_lens");
   if (pg && !pg->block_table) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": null block_table");
   // one thread per (channel row, 8-key chunk), 256 to a block, the blocks of a (sequence, head) together: a grid
@@ -1439,6 +1461,21 @@ int fa_append_paged_fp8(void* stream, int64_t sequences, int32_t kv_heads, int32
   const PagedPart pg = {block_table, max_pages, page, num_pages};
   const Kv8 kv8 = {k_scale, v_scale};
   return cache_append(stream, sequences, kv_heads, d, v_d, n_new, nk, K_new, V_new, K_pool8, V_pool8, &kv8, &pg, k_lens, new_lens);
+}
+
+int fa_append_mla_paged(void* stream, int64_t sequences, int32_t d, int32_t n_new, int32_t nk, const void* KV_new,
+                        void* KV_pool, const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                        const int32_t* k_lens, const int32_t* new_lens) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  return cache_append(stream, sequences, 1, d, 0, n_new, nk, KV_new, KV_new, KV_pool, KV_pool, nullptr, &pg, k_lens, new_lens, true);
+}
+
+int fa_append_mla_paged_fp8(void* stream, int64_t sequences, int32_t d, int32_t n_new, int32_t nk, const void* KV_new,
+                            void* KV_pool8, const float* kv_scale, const int32_t* block_table, int32_t max_pages,
+                            int32_t page, int64_t num_pages, const int32_t* k_lens, const int32_t* new_lens) {
+  const PagedPart pg = {block_table, max_pages, page, num_pages};
+  const Kv8 kv8 = {kv_scale, nullptr};
+  return cache_append(stream, sequences, 1, d, 0, n_new, nk, KV_new, KV_new, KV_pool8, KV_pool8, &kv8, &pg, k_lens, new_lens, true);
 }
 
 size_t fa_backward_workspace_bytes(const fa_problem* p) {

@@ -41,6 +41,15 @@
 // result; pages without a live key are never looked up, and every entry that is loaded is clamped to
 // [0, num_pages - 1] before it forms an address.  C and v_d below (576, 512) are uniform loop bounds over 64-channel
 // groups of this one instance.
+//
+// The pool's encoding is a compile-time parameter: over MlaFp8Args the pool holds OCP e4m3fn bytes,
+// [num_pages][C][page], and only the staging differs.  A thread stages 16 keys of a channel row as ONE 16-byte load
+// (9 loads and 36 registers a tile instead of 18 and 72), clears the bytes at or past the length as integers (so the
+// NaN codes 0x7F / 0xFF never reach the conversion), converts with v_cvt_scalef32_pk_f16_fp8 (exact, with the power
+// of two 2^e of kv_scale riding in it) and stores the two 16-byte chunks of the SAME swizzled fp16 image; everything
+// after the publish barrier is the text above.  K and V are one image, so 2^e multiplies both; the remainder
+// r = kv_scale / 2^e goes twice: into the fp32 Q pre-scale (for K) and into the accumulator where the record is
+// written (for V).  An invalid scale makes the second factor NaN.
 #include "fa_device.h"
 #include "fa_fwd_f16_fewq.h"
 #include "fa_kernels.h"
@@ -51,6 +60,18 @@ namespace {
 
 using namespace mf;
 using f16core::FewqRecord;
+
+// the pool encoding of a kernel argument type: fp16 halfs (MlaArgs) or e4m3fn bytes with one device scale (MlaFp8Args)
+template <class Args>
+struct PoolOf {
+  static constexpr bool k8 = false;
+  static __device__ __forceinline__ const MlaArgs& mla(const Args& a) { return a; }
+};
+template <>
+struct PoolOf<MlaFp8Args> {
+  static constexpr bool k8 = true;
+  static __device__ __forceinline__ const MlaArgs& mla(const MlaFp8Args& a) { return a.m; }
+};
 
 constexpr int kC = 576;                     // most score channels
 constexpr int kVd = 512;                    // most value channels
@@ -63,6 +84,8 @@ constexpr int kXWave = 64 * 16 * 4;         // 16 fp32 scores a lane
 constexpr int kSmem = kOffX + kNW * kXWave; // 160 KB
 constexpr int kCPT = kC * 8 / (kNW * 64);   // 16-byte chunks of a full tile per thread: 18
 constexpr int kRowStep = kNW * 64 / 8;      // channel rows between two chunks of a thread: 32
+constexpr int kCPT8 = kC * 4 / (kNW * 64);  // FP8: 16-byte loads (16 keys) of a full tile per thread: 9
+constexpr int kRowStep8 = kNW * 64 / 4;     // FP8: channel rows between two loads of a thread: 64
 static_assert(kCPT % 2 == 0, "staged in two halves");
 static_assert(kSmem == 160 * 1024, "the whole LDS of a gfx950 CU");
 static_assert(kRows == 64 && kVd % 128 == 0 && kC % 64 == 0, "two 32-row halves; channel groups dealt to two waves");
@@ -70,7 +93,10 @@ static_assert(kRows == 64 && kVd % 128 == 0 && kC % 64 == 0, "two 32-row halves;
 // the chunk swizzle of channel row c (see above)
 __device__ __forceinline__ int swz(int c) { return (((c >> 1) & 1) << 2) | ((c >> 2) & 3); }
 
-__global__ __launch_bounds__(kNW * 64, 1) void mla_partial_kernel(MlaArgs ma) {
+template <class Args>
+__global__ __launch_bounds__(kNW * 64, 1) void mla_partial_kernel(Args args) {
+  constexpr bool k8 = PoolOf<Args>::k8;
+  const MlaArgs& ma = PoolOf<Args>::mla(args);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   lds_char_t* smem = (lds_char_t*)smem_raw;
   constexpr float kNegInf = -__builtin_huge_valf();
@@ -104,9 +130,17 @@ __global__ __launch_bounds__(kNW * 64, 1) void mla_partial_kernel(MlaArgs ma) {
   const int hi = ma.tail_causal ? min(len - nq + qi, len - 1) : len - 1;
 
   // ---- Q * softmax_scale * log2(e) as the B operand of S^T = K^T.Q: lane (r, h) holds channels 16 s + 8 h + e
+  // (FP8: kv_scale = kmul * rmul, kmul = 2^e in the conversion of the one image, rmul here and in the record)
+  float kmul = 1.f, rmul = 1.f, omul = 1.f;
+  if constexpr (k8) {
+    const f16core::Kv8Mul sc = f16core::kv8_mul(args.kv_scale, nullptr, 0);  // (vmul: 1.0, or NaN for an invalid scale)
+    kmul = sc.kmul;
+    rmul = sc.qmul;
+    omul = __float_as_uint(sc.vmul) == 0x3f800000u ? sc.qmul : sc.vmul;  // r, not kv_scale: 2^e came with the image
+  }
   half8 qf[kC / 16];
   {
-    const float c2 = (float)a.scale * kLog2e;
+    const float c2 = k8 ? (float)a.scale * kLog2e * rmul : (float)a.scale * kLog2e;
     const __half* Qr = static_cast<const __half*>(a.Q) + (((int64_t)seq * ma.heads + head) * C) * nq + qi;
     const bool qvec = nq == 1 && (reinterpret_cast<uintptr_t>(a.Q) & 15) == 0;  // a row's channels are contiguous
 #pragma unroll
@@ -178,6 +212,56 @@ __global__ __launch_bounds__(kNW * 64, 1) void mla_partial_kernel(MlaArgs ma) {
     return trow[min((int)((uint32_t)k / (uint32_t)page), last_live)];
   };
 
+  // ---- FP8 staging: load j of this thread is the 16 keys 16 cm8 .. 16 cm8 + 15 of channel row crow8 + 64 j, the
+  // 16 rows of a wave with bits 1 and 2 of the row number swapped: the four rows of 16 consecutive lanes are then
+  // r, r + 1, r + 4, r + 5, whose chunk positions (2 cm8 + b) ^ f(c) for one b are 8 different ones x 2 row parities.
+  // (Generic lambdas: the fp16 instance holds none of this, and its machine code is what it was.)
+  u32x4 stg8[k8 ? kCPT8 : 1];
+  auto lane8 = [&](auto) __attribute__((always_inline)) {
+    struct { int cm, crow, nj; } t;
+    const int q8 = tid >> 2;
+    t.cm = tid & 3;
+    t.crow = (q8 & ~6) | ((q8 & 2) << 1) | ((q8 & 4) >> 1);
+    t.nj = C >> 6;
+    return t;
+  };
+  auto issue8 = [&](auto tag, int k0, int e_raw) __attribute__((always_inline)) {
+    const auto t = lane8(tag);
+    const int entry = __builtin_amdgcn_readfirstlane(min(max(e_raw, 0), ma.last_page));
+    const int p = (int)((uint32_t)k0 / (uint32_t)page);
+    const uint8_t* src = static_cast<const uint8_t*>(a.K) + ((int64_t)entry * C + t.crow) * page + (k0 - p * page) + 16 * t.cm;
+    const int64_t step = (int64_t)kRowStep8 * page;
+#pragma unroll
+    for (int j = 0; j < kCPT8; ++j) {
+      if (j < t.nj) stg8[j] = *reinterpret_cast<const u32x4*>(src);
+      src += step;
+    }
+  };
+  // in the tile that holds the length the BYTES at or past it become 0x00 (+0.0) before anything converts them
+  auto store8 = [&](auto tag, int slot, int k0) __attribute__((always_inline)) {
+    const auto t = lane8(tag);
+    if (k0 + kBN > len) {
+      const int nv = len - k0 - 16 * t.cm;  // this thread's live keys, of 16
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int k = nv - 4 * x;  // live bytes of word x
+        const uint32_t keep = k >= 4 ? 0xffffffffu : k <= 0 ? 0u : (1u << (8 * (k & 3))) - 1u;
+#pragma unroll
+        for (int j = 0; j < kCPT8; ++j)
+          if (j < t.nj) stg8[j][x] &= keep;
+      }
+    }
+    lds_char_t* row = smem + slot * kTile + t.crow * 128;  // (64 j leaves the swizzle's bits alone)
+    const int x0 = 16 * ((2 * t.cm) ^ swz(t.crow)), x1 = 16 * ((2 * t.cm + 1) ^ swz(t.crow));
+#pragma unroll
+    for (int j = 0; j < kCPT8; ++j)
+      if (j < t.nj) {
+        *reinterpret_cast<lds_u32x4_t*>(row + x0) = f16core::chunk_f16(u32x2{stg8[j][0], stg8[j][1]}, kmul);
+        *reinterpret_cast<lds_u32x4_t*>(row + x1) = f16core::chunk_f16(u32x2{stg8[j][2], stg8[j][3]}, kmul);
+        row += kRowStep8 * 128;
+      }
+  };
+
   // ---- fragment read bases (lane constants)
   // K, transposed: rows 16 s + 8 h + 4 e + tq, the 8 bytes of keys 32 cw + 16 (g & 1) + 4 sig .. + 3, so that
   // register i of S^T holds key 32 cw + 16 (i >> 3) + 8 h + (i & 7): P is the B operand of PV as it stands
@@ -206,10 +290,15 @@ __global__ __launch_bounds__(kNW * 64, 1) void mla_partial_kernel(MlaArgs ma) {
 
   // ---- prologue: tile 0 into slot 0
   int e_next = entry_of(kt0);
-  issue(IC<0>{}, kt0, e_next);
-  store(IC<0>{}, 0, kt0);
-  issue(IC<1>{}, kt0, e_next);
-  store(IC<1>{}, 0, kt0);
+  if constexpr (k8) {
+    issue8(IC<0>{}, kt0, e_next);
+    store8(IC<0>{}, 0, kt0);
+  } else {
+    issue(IC<0>{}, kt0, e_next);
+    store(IC<0>{}, 0, kt0);
+    issue(IC<1>{}, kt0, e_next);
+    store(IC<1>{}, 0, kt0);
+  }
   e_next = entry_of(kt0 + kBN);
   __syncthreads();
 
@@ -220,8 +309,12 @@ __global__ __launch_bounds__(kNW * 64, 1) void mla_partial_kernel(MlaArgs ma) {
     const int k0 = kt0 + it * kBN, slot = it & 1;
     const bool more = it + 1 < ntiles;
     if (more) {  // the whole next tile in flight for the whole of this one
-      issue(IC<0>{}, k0 + kBN, e_next);
-      issue(IC<1>{}, k0 + kBN, e_next);
+      if constexpr (k8) {
+        issue8(IC<0>{}, k0 + kBN, e_next);
+      } else {
+        issue(IC<0>{}, k0 + kBN, e_next);
+        issue(IC<1>{}, k0 + kBN, e_next);
+      }
       e_next = entry_of(k0 + 2 * kBN);
     }
 
@@ -332,8 +425,12 @@ __global__ __launch_bounds__(kNW * 64, 1) void mla_partial_kernel(MlaArgs ma) {
     }
 
     if (more) {
-      store(IC<0>{}, slot ^ 1, k0 + kBN);
-      store(IC<1>{}, slot ^ 1, k0 + kBN);
+      if constexpr (k8) {
+        store8(IC<0>{}, slot ^ 1, k0 + kBN);
+      } else {
+        store(IC<0>{}, slot ^ 1, k0 + kBN);
+        store(IC<1>{}, slot ^ 1, k0 + kBN);
+      }
     }
     __syncthreads();
   }
@@ -351,7 +448,7 @@ __global__ __launch_bounds__(kNW * 64, 1) void mla_partial_kernel(MlaArgs ma) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int v = 64 * (2 * gi + cw) + 32 * uu + 8 * (i >> 2) + 4 * h + (i & 3);
-          rec[rc.chan(v, row)] = o[2 * gi + uu][i];
+          rec[rc.chan(v, row)] = k8 ? o[2 * gi + uu][i] * omul : o[2 * gi + uu][i];
         }
     }
   if (cw == 0 && h == 0) {  // (the two waves of a row pair hold the same statistics)
@@ -381,13 +478,18 @@ __global__ __launch_bounds__(256) void mla_merge_kernel(MlaArgs ma) {
 
 }  // namespace
 
-hipError_t launch_fwd_f16_mla(const MlaArgs& ma, hipStream_t s) {
+// the partial kernel of the pool's encoding over `args`, then the merge over its MlaArgs
+template <class Args>
+static hipError_t launch_mla(const Args& args, const MlaArgs& ma, hipStream_t s) {
   const FwdArgs& a = ma.s.f;
-  const hipError_t e = launch_smem(mla_partial_kernel, (unsigned)(a.b * ma.nrb * ma.s.nchunks), kNW * 64, kSmem, s, ma);
+  const hipError_t e = launch_smem(mla_partial_kernel<Args>, (unsigned)(a.b * ma.nrb * ma.s.nchunks), kNW * 64, kSmem, s, args);
   if (e != hipSuccess) return e;
   const int64_t threads = a.b * (int64_t)a.v_d * ma.heads * a.rule.q.n;
   hipLaunchKernelGGL(mla_merge_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ma);
   return hipGetLastError();
 }
+
+hipError_t launch_fwd_f16_mla(const MlaArgs& ma, hipStream_t s) { return launch_mla(ma, ma, s); }
+hipError_t launch_fwd_f16_mla_fp8(const MlaFp8Args& ma8, hipStream_t s) { return launch_mla(ma8, ma8.m, s); }
 
 }  // namespace fa

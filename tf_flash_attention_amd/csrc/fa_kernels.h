@@ -181,6 +181,14 @@ struct MlaArgs {
 // has checked that both grids fit
 hipError_t launch_fwd_f16_mla(const MlaArgs& ma, hipStream_t s);
 
+// the same over an FP8 latent pool: m.s.f.K is the pool [num_pages][d][page] in OCP e4m3fn bytes, and the true
+// cached vector is kv_scale[0] * decode(byte); only the kernel reads the scale (null: 1.0)
+struct MlaFp8Args {
+  MlaArgs m;
+  const float* kv_scale;
+};
+hipError_t launch_fwd_f16_mla_fp8(const MlaFp8Args& ma8, hipStream_t s);
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;

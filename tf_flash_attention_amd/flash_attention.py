@@ -34,10 +34,12 @@ that says which page holds which keys of which sequence (also read by the kernel
     paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False)
 
 and MLA decode (multi-head latent attention in absorbed form: 16 to 128 query heads against one K/V head of up to
-576 channels whose values are its first ``v_channels`` channels) over a paged latent cache ``[num_pages, C, page]``::
+576 channels whose values are its first ``v_channels`` channels) over a paged latent cache ``[num_pages, C, page]``,
+float16 or FP8 (e4m3fn bytes with one device scale), with its fused append::
 
     mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False, softmax_scale=None,
-                 returning_l_m=False)
+                 returning_l_m=False, kv_scale=None)
+    mla_paged_append_1d(KV_pool, KV_new, block_table, k_lens, new_lens=None, kv_scale=None)
 
 Tensors are ``torch`` tensors on a ROCm device in the reference's channel-first
 layout ``batch_shape + (C, *seq_shape)``.  Each call returns ``O`` or
@@ -73,6 +75,7 @@ __all__ = [
     "ragged_1d", "paged_1d", "ragged_prefill_1d", "paged_prefill_1d", "quantize_kv_fp8",
     "ragged_append_1d", "paged_append_1d", "ragged_window_prefill_1d", "paged_window_prefill_1d",
     "mla_paged_1d",
+    "mla_paged_append_1d",
 ]
 
 
@@ -1143,7 +1146,7 @@ _MLA_ENVELOPE = ("float16, C % 64 == 0 and 64 <= C <= 576, v_channels % 64 == 0 
 
 
 def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False, softmax_scale=None,
-                 returning_l_m=False):
+                 returning_l_m=False, kv_scale=None):
     """Decode of multi-head latent attention (MLA: DeepSeek-V2/V3 style stacks) in absorbed form over a paged
     LATENT cache: Q ``batch + (Hq, C, Nq)``, ``KV_pool`` ``[num_pages, C, page]`` (one K/V head, the key axis
     contiguous, a page holding ``page`` consecutive positions of one sequence), ``block_table`` int32
@@ -1164,15 +1167,23 @@ def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False,
     FIXED in a captured graph.  ``l`` (float32) and ``m`` (float16) are in the units of the scaled scores, so
     ``(O, l, m)`` compose with ``merge_partials``.
 
-    A new token's latent vector is appended on the device before the call, so that ``k_lens`` counts it::
+    An FP8 latent pool: ``KV_pool`` may be ``torch.float8_e4m3fn`` or the same bytes as ``torch.uint8`` (Q stays
+    float16), with ``kv_scale`` a one-element float32 tensor on the device of Q, or None for 1.0: the true cached
+    vector is ``kv_scale * decode(byte)``.  Only the kernel reads the scale, so a captured graph may be replayed after
+    it was overwritten in place; a scale that is zero, negative, Inf or NaN gives NaN in O.  The bytes are converted
+    exactly, half the cache bytes cross memory, and with ``kv_scale`` None, 1.0 or a power of two in
+    ``[2^-8, 2^7]`` the result is bitwise the float16 call's on the dequantized pool.  A float16 pool takes no scale.
+
+    A new token's latent vector is appended on the device before the call, so that ``k_lens`` counts it, by
+    ``mla_paged_append_1d`` (one kernel for a whole batch, float16 or FP8); for one token of one sequence it does::
 
         KV_pool[block_table[s, pos // page], :, pos % page] = new        # new: [C], pos = k_lens[s] - 1
 
     Envelope: float16, C % 64 == 0 and 64 <= C <= 576, v_channels % 64 == 0 and 64 <= v_channels <= min(C, 512),
     1 <= Hq <= 128, Nq >= 1, Hq * next_pow2(Nq) <= 512, page % 64 == 0, capacity <= 2^30 keys; outside it ``NotImplementedError``
-    names the condition: there is no fallback that would read the lengths on the host.  Inference only.  Not here: a
-    fused append for the single pool, FP8 latent pools, sliding windows, tree masks, query blocking for more rows and
-    a ragged twin.  Returns ``O`` ``batch + (Hq, v_channels, Nq)`` or ``(O, l, m)``."""
+    names the condition: there is no fallback that would read the lengths on the host.  Inference only.  Not here:
+    per-block or per-channel-group scales, sliding windows, tree masks, query blocking for more rows and a ragged
+    twin.  Returns ``O`` ``batch + (Hq, v_channels, Nq)`` or ``(O, l, m)``."""
     what = "mla_paged_1d"
     if len(KV_pool.shape) != 3:
         raise InvalidArgumentError("KV_pool should be [num_pages, channels, page], but KV_pool_shape = "
@@ -1193,8 +1204,10 @@ def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False,
     if isinstance(v_channels, bool) or not isinstance(v_channels, int) or v_channels < 1:
         raise InvalidArgumentError(f"v_channels must be a positive int, got {v_channels!r}")
     dt = _dtype_id(Q, True)
-    if KV_pool.dtype != Q.dtype:
+    fp8 = KV_pool.dtype in _FP8_CACHE_DTYPES
+    if not fp8 and KV_pool.dtype != Q.dtype:
         raise TypeError(f"Q and KV_pool must share one dtype, got {Q.dtype} and {KV_pool.dtype}")
+    _mla_kv_scale(fp8, kv_scale, Q.device, "Q")
     for name, t in (("block_table", block_table), ("k_lens", k_lens)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
             raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
@@ -1244,13 +1257,105 @@ def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False,
     ws_bytes = int(L.fa_forward_mla_paged_workspace_bytes(prob, hq, page))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        st = L.fa_forward_mla_paged(_stream_handle(Q.device), prob, hq, Q.data_ptr(), KV_pool.data_ptr(),
-                                    block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(),
-                                    int(bool(tail_causal)), softmax_scale, O.data_ptr(), l.data_ptr(), m.data_ptr(),
-                                    ws.data_ptr(), ws_bytes)
+        head = (_stream_handle(Q.device), prob, hq, Q.data_ptr(), KV_pool.data_ptr(), block_table.data_ptr(),
+                max_pages, page, num_pages, k_lens.data_ptr(), int(bool(tail_causal)), softmax_scale)
+        tail = (O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+        if fp8:
+            st = L.fa_forward_mla_paged_fp8(*head, kv_scale.data_ptr() if kv_scale is not None else None, *tail)
+        else:
+            st = L.fa_forward_mla_paged(*head, *tail)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
+
+
+def _mla_kv_scale(fp8, kv_scale, device, q):
+    """The checks of the one scale of an FP8 latent pool: a one-element float32 tensor on ``device`` (the device of
+    the float16 tensor that ``q`` names), or None for 1.0; a float16 pool takes none."""
+    if kv_scale is None:
+        return
+    if not fp8:
+        raise InvalidArgumentError("kv_scale was given, but KV_pool is not an FP8 pool (float8_e4m3fn or uint8): "
+                                   "a float16 pool takes no scale")
+    if not isinstance(kv_scale, torch.Tensor) or kv_scale.dtype != torch.float32:
+        raise TypeError(f"kv_scale must be a float32 tensor, got {getattr(kv_scale, 'dtype', type(kv_scale).__name__)}")
+    if kv_scale.numel() != 1:
+        raise InvalidArgumentError("kv_scale should hold one element, but kv_scale_shape = " + _shape_str(kv_scale.shape)
+                                   + " was received")
+    if kv_scale.device != device:
+        raise InvalidArgumentError(f"kv_scale must be on the device of {q}")
+
+
+def mla_paged_append_1d(KV_pool, KV_new, block_table, k_lens, new_lens=None, kv_scale=None):
+    """``paged_append_1d`` into the latent pool of ``mla_paged_1d``, in place, with one kernel: ``KV_pool``
+    ``[num_pages, C, page]`` float16 or FP8 (``float8_e4m3fn`` or ``uint8``), ``KV_new`` ``batch + (C, Nnew)``
+    float16 (made contiguous if it is not), ``block_table`` int32 ``batch + (max_pages,)``, ``k_lens`` and
+    ``new_lens`` int32 of shape ``batch``.  Position ``pos`` of sequence s goes to
+    ``KV_pool[block_table[s, pos // page], :, pos % page]``.
+
+    The contract is ``paged_append_1d``'s with one head and no V: ``k_lens[s]`` is the length AFTER the append (the
+    tensor this step's ``mla_paged_1d`` takes), ``new_lens`` right-aligns the real tokens in the Nnew slots, only the
+    new positions are written, only the table entries of pages that receive one are loaded and each is clamped to
+    ``[0, num_pages - 1]``, and nothing is read on the host: a captured graph may be replayed after any of the
+    tensors was overwritten in place.  An FP8 pool stores the bytes of ``quantize_kv_fp8(x, scale=kv_scale)``;
+    ``kv_scale`` is a one-element float32 tensor on the device or None for 1.0, and a float16 pool takes none.  The
+    pool must be contiguous (a copy would silently take the write) and its page a multiple of 64.  Inference only.
+    Returns None."""
+    what = "mla_paged_append_1d"
+    if len(KV_pool.shape) != 3:
+        raise InvalidArgumentError("KV_pool should be [num_pages, channels, page], but KV_pool_shape = "
+                                   + _shape_str(KV_pool.shape) + " was received")
+    num_pages, k_ch, page = (int(x) for x in KV_pool.shape)
+    if num_pages < 1:
+        raise InvalidArgumentError("The pool should hold a page, but KV_pool_shape = " + _shape_str(KV_pool.shape)
+                                   + " was received")
+    if not isinstance(KV_new, torch.Tensor) or KV_new.dtype != torch.float16:
+        raise TypeError(f"KV_new must be a float16 tensor, got {getattr(KV_new, 'dtype', type(KV_new).__name__)}")
+    if len(KV_new.shape) < 2 or int(KV_new.shape[-2]) != k_ch:
+        raise InvalidArgumentError("KV_new should be batch + (C, Nnew) with C = " + str(k_ch) + ", but KV_new_shape = "
+                                   + _shape_str(KV_new.shape) + " was received")
+    batch, n_new = tuple(KV_new.shape[:-2]), int(KV_new.shape[-1])
+    fp8 = KV_pool.dtype in _FP8_CACHE_DTYPES
+    if not fp8 and KV_pool.dtype != KV_new.dtype:
+        raise TypeError("KV_pool must be float16 or an FP8 pool (float8_e4m3fn or uint8), got " + str(KV_pool.dtype))
+    _mla_kv_scale(fp8, kv_scale, KV_pool.device, "KV_pool")
+    ints = (("block_table", block_table), ("k_lens", k_lens)) + ((("new_lens", new_lens),) if new_lens is not None else ())
+    for name, t in ints:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if tuple(block_table.shape[:-1]) != batch or len(block_table.shape) != len(batch) + 1 or block_table.shape[-1] < 1:
+        raise InvalidArgumentError("The shape of block_table should be the batch shape plus (max_pages,), but "
+                                   "block_table_shape = " + _shape_str(block_table.shape) + ", batch_shape = "
+                                   + _shape_str(batch) + " were received")
+    for name, t in ints[1:]:
+        if tuple(t.shape) != batch:
+            raise InvalidArgumentError(f"The shape of {name} should be the batch shape, but {name}_shape = "
+                                       + _shape_str(t.shape) + ", batch_shape = " + _shape_str(batch) + " were received")
+    if KV_new.device != KV_pool.device or any(t.device != KV_pool.device for _, t in ints):
+        raise InvalidArgumentError(", ".join(n for n, _ in ints) + " and KV_new must be on the device of KV_pool")
+    if torch.is_grad_enabled() and (KV_pool.requires_grad or KV_new.requires_grad):
+        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
+                           "detach its inputs")
+    if not KV_pool.is_contiguous():
+        raise InvalidArgumentError(what + ": KV_pool must be contiguous: the append writes in place, and a contiguous "
+                                   "copy would silently take the write")
+    if page < 1 or page % 64 != 0:
+        raise NotImplementedError(what + ": " + _MLA_PAGE_CONDITION + ", got page = " + str(page))
+    max_pages = int(block_table.shape[-1])
+    cap = max_pages * page
+    if cap > 2 ** 30:
+        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    _check_device_tensors(KV_pool, KV_new)
+    KV_new, block_table, k_lens = KV_new.contiguous(), block_table.contiguous(), k_lens.contiguous()
+    new_lens = new_lens.contiguous() if new_lens is not None else None
+    scale = ((kv_scale.data_ptr() if kv_scale is not None else None),) if fp8 else ()
+    with torch.cuda.device(KV_pool.device):
+        st = getattr(_lib.lib(), "fa_append_mla_paged" + ("_fp8" if fp8 else ""))(
+            _stream_handle(KV_pool.device), _prod(batch), k_ch, n_new, cap, KV_new.data_ptr(), KV_pool.data_ptr(), *scale,
+            block_table.data_ptr(), max_pages, page, num_pages, k_lens.data_ptr(),
+            new_lens.data_ptr() if new_lens is not None else None)
+    if st != _lib.FA_OK:
+        _raise_status(st, "append")
 
 
 # ----------------------------------------------------------------------------
