@@ -594,8 +594,9 @@ int fa_forward_paged_window_prefill_fp8(void* stream, const fa_problem* p, int32
  *   accumulator.  With kv_scale null, 1.0 or any 2^e inside the clamp the results are BITWISE fa_forward_mla_paged's
  *   on the fp16 pool of the values 2^e * decode(byte).  A kv_scale that is zero, negative, Inf or NaN gives NaN in O,
  *   as the FP8 caches above do.
- * Not here: per-block or per-channel-group scales, an fp16 rotary tail beside FP8 latents, sliding windows, tree
- *   masks, query blocking beyond R <= 512 and a ragged (unpaged) twin.  The write side: fa_append_mla_paged below. */
+ * Not here: per-block or per-channel-group scales, an fp16 rotary tail beside FP8 latents, sliding windows and a
+ *   ragged (unpaged) twin.  More rows than R <= 512 and tree masks: fa_forward_mla_paged_prefill below.  The write
+ *   side: fa_append_mla_paged below. */
 int fa_forward_mla_paged_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[5]);
 size_t fa_forward_mla_paged_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page);
 int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads,
@@ -610,6 +611,53 @@ int fa_forward_mla_paged_fp8(void* stream, const fa_problem* p, int32_t heads,
                              const int32_t* k_lens, int32_t tail_causal, float softmax_scale, const float* kv_scale,
                              void* O, void* l, void* m,
                              void* workspace, size_t workspace_bytes);
+
+/* Query-blocked and tree-masked MLA attention over the same paged latent cache: ANY nq >= 1 (a draft tree, a long
+ * draft chain, a chunk of a prompt against its own latent prefix).  The arguments, the contract of block_table,
+ * k_lens, softmax_scale and kv_scale, and the INVALID_ARGUMENT refusals are fa_forward_mla_paged's (_fp8's); the
+ * queries are the sequence's last nq positions, under tail_causal query i sees keys j <= len - nq + i, and a row
+ * before position 0, or one that sees no key, is the empty row (O = 0, l = 0, m bytes 0xFA).
+ *   draft_mask (nullable): DEVICE int32 [sequences][nq][ceil(nq / 32)], shared by the heads: fa_forward_paged_tree's
+ *     mask.  With base = len - nq, query i sees every key below base and draft slot j (key base + j) iff bit j & 31
+ *     of word [i][j >> 5] is set; bits at or past nq are ignored and slots at negative positions name no key.  It
+ *     requires tail_causal != 0 and nq <= 128 (else FA_ERR_INVALID_ARGUMENT).  Only the kernel reads it: a captured
+ *     graph may be replayed after it was overwritten in place.  Draft keys that a row does not see are loaded and
+ *     masked, so they must be finite.  A lower-triangle mask gives the BITS of the same call without a mask: a masked
+ *     score is -inf, and a tile or a chunk that a row sees nothing of adds exactly nothing under the exact running
+ *     maximum.
+ * Envelope: fa_forward_mla_paged's without the bound on R, and heads * nq * v_d < 2^31: outside it
+ *   FA_ERR_UNSUPPORTED, before anything is read.  A launch grid of 2^31 workgroups or more: FA_ERR_INVALID_ARGUMENT.
+ *   These entry points do not delegate: inside fa_forward_mla_paged's envelope they run their own plan, whose
+ *   results equal that entry point's to rounding, not bitwise (tf_flash_attention_amd.mla_paged_prefill_1d delegates).
+ * fa_forward_mla_paged_prefill_plan (host-only): out = {key chunks (0 outside the envelope), keys per chunk, query
+ *   slots per row block P_b, row blocks per sequence, query blocks, head blocks per query block}.  A row block is 64
+ *   rows: P_b = max(1, 64 / next_pow2(heads)) consecutive queries of 64 / P_b heads, so that a block holds as many
+ *   heads as it can (they share every key end and mask row); row blocks = ceil(nq / P_b) * ceil(heads / (64 / P_b)).
+ *   The more row blocks, the fewer chunks: chunk = max(ceil(ceil(nk / 64) / max(1, 64 / row blocks)) * 64, 512 for
+ *   one row block or 1024 above), chunks = ceil(nk / chunk).  A pure function of the problem WITHOUT b, the lengths,
+ *   the table, tail_causal or the mask.
+ * fa_forward_mla_paged_prefill_workspace_bytes (host-only): (b / heads) * row blocks * chunks * 64 * (v_d + 3)
+ *   floats rounded up to 256 bytes; 0 outside the envelope.
+ * fa_forward_mla_paged_prefill(_fp8): one partial workgroup per (sequence, chunk, row block).  Under tail_causal
+ *   without a mask a row block's keys end after its last query's position: workgroups of chunks at or past that end
+ *   return at once and the merge folds only the chunks below it.  With a mask every block ends at the length and only
+ *   the tiles that overlap the nq draft slots read mask words. */
+int fa_forward_mla_paged_prefill_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[6]);
+size_t fa_forward_mla_paged_prefill_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page);
+int fa_forward_mla_paged_prefill(void* stream, const fa_problem* p, int32_t heads,
+                                 const void* Q, const void* KV_pool,
+                                 const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                                 const int32_t* k_lens, int32_t tail_causal, float softmax_scale,
+                                 const int32_t* draft_mask,
+                                 void* O, void* l, void* m,
+                                 void* workspace, size_t workspace_bytes);
+int fa_forward_mla_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t heads,
+                                     const void* Q, const void* KV_pool8,
+                                     const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                                     const int32_t* k_lens, int32_t tail_causal, float softmax_scale,
+                                     const float* kv_scale, const int32_t* draft_mask,
+                                     void* O, void* l, void* m,
+                                     void* workspace, size_t workspace_bytes);
 
 /* Fused K/V append: the write side of the four caches above. New tokens' keys and values are stored IN PLACE into a
  * ragged cache or into page pools, fp16 or FP8, by one kernel launch enqueued on `stream`: a forward enqueued after it

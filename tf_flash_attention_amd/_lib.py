@@ -80,6 +80,10 @@ EXPORTED_SYMBOLS = (
     "fa_forward_mla_paged_workspace_bytes",
     "fa_forward_mla_paged",
     "fa_forward_mla_paged_fp8",
+    "fa_forward_mla_paged_prefill_plan",
+    "fa_forward_mla_paged_prefill_workspace_bytes",
+    "fa_forward_mla_paged_prefill",
+    "fa_forward_mla_paged_prefill_fp8",
     "fa_append_ragged",
     "fa_append_paged",
     "fa_append_ragged_fp8",
@@ -249,6 +253,18 @@ def _declare(lib):
             append = getattr(lib, "fa_append_mla_paged" + ("_fp8" if fp8 else ""))
             append.argtypes = [vp, i64, i32, i32, i32, vp, vp] + ([vp] if fp8 else []) + [vp, i32, i32, i64, vp, vp]
             append.restype = ctypes.c_int
+    # its query-blocked and tree-masked forms: the same arguments with the nullable device mask in front of O, and a
+    # plan of six numbers.  (Absent as above.)
+    if hasattr(lib, "fa_forward_mla_paged_prefill"):
+        lib.fa_forward_mla_paged_prefill_plan.argtypes = [P, i32, i32, ctypes.POINTER(i32)]
+        lib.fa_forward_mla_paged_prefill_plan.restype = ctypes.c_int
+        lib.fa_forward_mla_paged_prefill_workspace_bytes.argtypes = [P, i32, i32]
+        lib.fa_forward_mla_paged_prefill_workspace_bytes.restype = ctypes.c_size_t
+        for fp8 in (False, True):
+            forward = getattr(lib, "fa_forward_mla_paged_prefill" + ("_fp8" if fp8 else ""))
+            forward.argtypes = ([vp, P, i32, vp, vp, vp, i32, i32, i64, vp, i32, ctypes.c_float] + ([vp] if fp8 else [])
+                                + [vp, vp, vp, vp, vp, ctypes.c_size_t])
+            forward.restype = ctypes.c_int
     # The fused K/V appends (include/fa_api.h): the same pieces again, the caches written instead of read; (k_scale,
     # v_scale) after an FP8 cache, (block_table, max_pages, page, num_pages) after a paged one.  (Absent as above.)
     for cache in DECODE_CACHES:

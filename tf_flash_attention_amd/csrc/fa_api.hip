@@ -1378,6 +1378,139 @@ int fa_forward_mla_paged_fp8(void* stream, const fa_problem* p, int32_t heads, c
                      tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
 }
 
+// ---- the query-blocked and tree-masked forms of the MLA forward (include/fa_api.h; DESIGN.md §3.22;
+// fa_fwd_f16_mla_prefill.hip): any nq.  A block of 64 rows holds pb = max(1, 64 / next_pow2(heads)) queries of
+// 64 / pb heads, so a sequence has nrb = ceil(nq / pb) * nhb blocks, nhb = ceil(heads / (64 / pb)) (1 or 2).  The
+// chunks follow the prefill forms' rule: the blocks already supply workgroups and every (block, chunk) costs a record,
+// so at most max(1, 64 / nrb) chunks, of at least decode's minimum (512 keys for one block, 1024 above).  A pure
+// function of the problem without b, the lengths, the table, tail_causal or the mask.
+struct MlaPrefillPlan {
+  int32_t nchunks, chunk, pb, nrb, nqb, nhb;
+};
+
+// (after check_mla)
+static MlaPrefillPlan mla_prefill_plan(const fa_problem* p, int32_t heads, int32_t page) {
+  MlaPrefillPlan s = {};
+  const int64_t nq = p->q_seq[0], nk = p->k_seq[0];
+  const bool inside = p->dtype == FA_F16 && p->seq_dims == 1 && p->d % 64 == 0 && p->d >= 64 && p->d <= kMlaMaxC &&
+                      p->v_d % 64 == 0 && p->v_d >= 64 && p->v_d <= kMlaMaxV && p->v_d <= p->d && page % kSplitTile == 0 &&
+                      heads <= kMlaMaxHeads && nq >= 1 && nk >= 1 &&
+                      nq * heads * p->v_d <= 0x7fffffff;  // (the merge counts a sequence's outputs in 32 bits)
+  if (!inside) return s;
+  const int32_t hp = next_pow2(heads);
+  s.pb = hp >= kMlaBlockRows ? 1 : kMlaBlockRows / hp;
+  const int32_t hpb = kMlaBlockRows / s.pb;
+  s.nhb = (heads + hpb - 1) / hpb;
+  const int64_t nqb = (nq + s.pb - 1) / s.pb;
+  s.nqb = (int32_t)nqb;
+  s.nrb = (int32_t)(nqb * s.nhb);
+  const int32_t kmax = kSplitMaxChunks / s.nrb > 1 ? kSplitMaxChunks / s.nrb : 1;
+  const int32_t min_chunk = s.nrb == 1 ? 512 : 1024;
+  const int64_t tiles = (nk + kSplitTile - 1) / kSplitTile;
+  const int64_t capped = (tiles + kmax - 1) / kmax * kSplitTile;
+  s.chunk = (int32_t)(capped > min_chunk ? capped : min_chunk);
+  s.nchunks = (int32_t)((nk + s.chunk - 1) / s.chunk);
+  return s;
+}
+
+static size_t mla_prefill_ws_bytes(const fa_problem* p, int32_t heads, const MlaPrefillPlan& s) {
+  return align_up((size_t)(p->b / heads) * (size_t)s.nrb * (size_t)s.nchunks *
+                  (size_t)fa::fewq_record_floats(p->v_d, kMlaBlockRows) * sizeof(float));
+}
+
+int fa_forward_mla_paged_prefill_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[6]) {
+  const int st = check_mla(p, heads, page);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const MlaPrefillPlan s = mla_prefill_plan(p, heads, page);
+  out[0] = s.nchunks; out[1] = s.chunk; out[2] = s.pb; out[3] = s.nrb; out[4] = s.nqb; out[5] = s.nhb;
+  return FA_OK;
+}
+
+size_t fa_forward_mla_paged_prefill_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page) {
+  if (check_mla(p, heads, page) != FA_OK) return 0;
+  const MlaPrefillPlan s = mla_prefill_plan(p, heads, page);
+  return s.nchunks ? mla_prefill_ws_bytes(p, heads, s) : 0;
+}
+
+// both pool encodings, as forward_mla; `draft_mask` (nullable) is the device bit mask over the draft slots
+static int forward_mla_prefill(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
+                               bool fp8, const float* kv_scale, const int32_t* block_table, int32_t max_pages,
+                               int32_t page, int64_t num_pages, const int32_t* k_lens, int32_t tail_causal,
+                               float softmax_scale, const int32_t* draft_mask, void* O, void* l, void* m,
+                               void* workspace, size_t workspace_bytes) {
+  const int st = check_mla(p, heads, page);
+  if (st != FA_OK) return st;
+  if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: max_pages must be >= 1");
+  if (p->seq_dims == 1 && (int64_t)max_pages * page != p->k_seq[0])
+    return set_error(FA_ERR_INVALID_ARGUMENT,
+                     "MLA paged forward: max_pages * page = " + std::to_string((int64_t)max_pages * page) +
+                         " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
+  if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: num_pages must be >= 1");
+  if (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale))
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: softmax_scale must be positive and finite");
+  if (draft_mask && !tail_causal)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged prefill forward: a draft_mask requires tail_causal (the draft slots are the sequence's last positions)");
+  if (draft_mask && p->q_seq[0] > 128)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged prefill forward: a draft_mask takes at most 128 queries, got nq = " + std::to_string(p->q_seq[0]));
+  const MlaPrefillPlan mp = mla_prefill_plan(p, heads, page);
+  if (mp.nchunks == 0)
+    return set_error(FA_ERR_UNSUPPORTED,
+                     "MLA paged prefill forward: outside the envelope (fp16, 1d sequences, d % 64 == 0, 64 <= d <= 576, "
+                     "v_d % 64 == 0, 64 <= v_d <= min(d, 512), page % 64 == 0, 1 <= heads <= 128, nq >= 1, "
+                     "heads * nq * v_d < 2^31, nk >= 1)");
+  const int64_t seqs = p->b / heads, nq = p->q_seq[0];
+  if (seqs * mp.nrb * mp.nchunks > 0x7fffffff || (seqs * p->v_d * heads * nq + 255) / 256 > 0x7fffffff)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged prefill forward: b = " + std::to_string(p->b) + " needs a launch grid of 2^31 workgroups or more");
+  if (!workspace || workspace_bytes < mla_prefill_ws_bytes(p, heads, mp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "forward workspace is smaller than fa_forward_mla_paged_prefill_workspace_bytes()");
+  FA_DIAG_COUNT(0);
+  if (p->b == 0) return FA_OK;
+  if (!Q || !O || !l || !m) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null Q, O, l or m");
+  if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
+  if (!block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null block_table");
+  if (!KV_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null KV_pool");
+  if (reinterpret_cast<uintptr_t>(KV_pool) & 15)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: KV_pool must be 16-byte aligned");
+  fa::MlaPrefillArgs pa = {};
+  fa::MlaArgs& ma = pa.m;
+  fill_split(p, {mp.nchunks, mp.chunk, 0, p->k_seq[0], 0}, &ma.s);
+  fa::FwdArgs& a = ma.s.f;
+  a.Q = Q; a.K = KV_pool; a.V = nullptr; a.O = O; a.l = l; a.m = m;
+  a.b = seqs;
+  a.scale = (double)softmax_scale;
+  ma.s.ws = static_cast<float*>(workspace);
+  ma.block_table = block_table; ma.k_lens = k_lens;
+  ma.heads = heads; ma.pitch = mp.pb; ma.log2_pitch = ilog2(mp.pb); ma.nrb = mp.nrb;
+  ma.max_pages = max_pages; ma.page = page;
+  ma.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);
+  ma.tail_causal = tail_causal != 0;
+  pa.mask = reinterpret_cast<const uint32_t*>(draft_mask);
+  pa.nhb = mp.nhb;
+  const hipError_t e = fp8 ? fa::launch_fwd_f16_mla_prefill_fp8(fa::MlaPrefillFp8Args{pa, kv_scale}, static_cast<hipStream_t>(stream))
+                          : fa::launch_fwd_f16_mla_prefill(pa, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+  return FA_OK;
+}
+
+int fa_forward_mla_paged_prefill(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
+                                 const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                                 const int32_t* k_lens, int32_t tail_causal, float softmax_scale,
+                                 const int32_t* draft_mask, void* O, void* l, void* m, void* workspace,
+                                 size_t workspace_bytes) {
+  return forward_mla_prefill(stream, p, heads, Q, KV_pool, false, nullptr, block_table, max_pages, page, num_pages,
+                             k_lens, tail_causal, softmax_scale, draft_mask, O, l, m, workspace, workspace_bytes);
+}
+
+int fa_forward_mla_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t heads, const void* Q,
+                                     const void* KV_pool8, const int32_t* block_table, int32_t max_pages, int32_t page,
+                                     int64_t num_pages, const int32_t* k_lens, int32_t tail_causal, float softmax_scale,
+                                     const float* kv_scale, const int32_t* draft_mask, void* O, void* l, void* m,
+                                     void* workspace, size_t workspace_bytes) {
+  return forward_mla_prefill(stream, p, heads, Q, KV_pool8, true, kv_scale, block_table, max_pages, page, num_pages,
+                             k_lens, tail_causal, softmax_scale, draft_mask, O, l, m, workspace, workspace_bytes);
+}
+
 // ---- the fused K/V append of the same four caches (include/fa_api.h): every check on the host
 // before any device call, then one launch of fa_cache_append.hip's kernel.  No workspace, no plan.
 static int cache_append(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new,

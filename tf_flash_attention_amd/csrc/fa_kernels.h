@@ -189,6 +189,24 @@ struct MlaFp8Args {
 };
 hipError_t launch_fwd_f16_mla_fp8(const MlaFp8Args& ma8, hipStream_t s);
 
+// the query-blocked and tree-masked forms of the two (fa_fwd_f16_mla_prefill.hip): any number of queries, the
+// sequence's last nq positions.  A block of 64 rows holds m.pitch = P consecutive queries (a power of two) of 64 / P
+// heads: row (head % (64 / P)) * P + query % P of block rb = (query / P) * nhb + head / (64 / P).  m.nrb counts the
+// blocks of a sequence, nqb * nhb, and m.s.ws holds the records [sequences][nrb][nchunks] of stride 64.  Under
+// m.tail_causal without a mask a block's keys end after its last query's position.
+struct MlaPrefillArgs {
+  MlaArgs m;
+  const uint32_t* mask;  // device: [sequences][nq][ceil(nq / 32)] words, or null.  Not null: m.tail_causal != 0,
+                         //   nq <= 128; query i sees the keys below len - nq and draft slot j iff bit j of its row
+  int32_t nhb;           // head blocks per query block: ceil(heads / (64 / P)), 1 or 2
+};
+hipError_t launch_fwd_f16_mla_prefill(const MlaPrefillArgs& pa, hipStream_t s);
+struct MlaPrefillFp8Args {
+  MlaPrefillArgs p;
+  const float* kv_scale;
+};
+hipError_t launch_fwd_f16_mla_prefill_fp8(const MlaPrefillFp8Args& pa8, hipStream_t s);
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;

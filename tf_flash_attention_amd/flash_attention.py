@@ -40,6 +40,8 @@ float16 or FP8 (e4m3fn bytes with one device scale), with its fused append::
     mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False, softmax_scale=None,
                  returning_l_m=False, kv_scale=None)
     mla_paged_append_1d(KV_pool, KV_new, block_table, k_lens, new_lens=None, kv_scale=None)
+    mla_paged_prefill_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False, softmax_scale=None,
+                         returning_l_m=False, kv_scale=None, draft_mask=None)     # any Nq, tree masks
 
 Tensors are ``torch`` tensors on a ROCm device in the reference's channel-first
 layout ``batch_shape + (C, *seq_shape)``.  Each call returns ``O`` or
@@ -76,6 +78,7 @@ __all__ = [
     "ragged_append_1d", "paged_append_1d", "ragged_window_prefill_1d", "paged_window_prefill_1d",
     "mla_paged_1d",
     "mla_paged_append_1d",
+    "mla_paged_prefill_1d",
 ]
 
 
@@ -1143,6 +1146,7 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
 _MLA_PAGE_CONDITION = "the page size (the last axis of KV_pool) must be a multiple of 64 keys"
 _MLA_ENVELOPE = ("float16, C % 64 == 0 and 64 <= C <= 576, v_channels % 64 == 0 and 64 <= v_channels <= min(C, 512), "
                  "1 <= Hq <= 128, Nq >= 1, Hq * next_pow2(Nq) <= 512")
+_MLA_ENVELOPE_BLOCKED = _MLA_ENVELOPE.replace("Hq * next_pow2(Nq) <= 512", "Hq * Nq * v_channels < 2^31")
 
 
 def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False, softmax_scale=None,
@@ -1183,8 +1187,44 @@ def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False,
     1 <= Hq <= 128, Nq >= 1, Hq * next_pow2(Nq) <= 512, page % 64 == 0, capacity <= 2^30 keys; outside it ``NotImplementedError``
     names the condition: there is no fallback that would read the lengths on the host.  Inference only.  Not here:
     per-block or per-channel-group scales, sliding windows, tree masks, query blocking for more rows and a ragged
-    twin.  Returns ``O`` ``batch + (Hq, v_channels, Nq)`` or ``(O, l, m)``."""
-    what = "mla_paged_1d"
+    twin; ``mla_paged_prefill_1d`` has the tree masks and the query blocking.  Returns ``O``
+    ``batch + (Hq, v_channels, Nq)`` or ``(O, l, m)``."""
+    return _mla_paged("mla_paged_1d", False, Q, KV_pool, block_table, k_lens, v_channels, tail_causal, softmax_scale,
+                      returning_l_m, kv_scale, None)
+
+
+def mla_paged_prefill_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False, softmax_scale=None,
+                         returning_l_m=False, kv_scale=None, draft_mask=None):
+    """``mla_paged_1d`` for ANY number of queries, with an optional tree mask over the draft tokens: a draft tree or a
+    long draft chain of a speculative step, or a chunk of a prompt against its own latent prefix.  The arguments, the
+    checks, the outputs, the FP8 pool with its device ``kv_scale`` and the graph-replay contract are
+    ``mla_paged_1d``'s; ``block_table``, ``k_lens``, ``kv_scale`` and ``draft_mask`` are read only by the kernels, so a
+    captured graph may be replayed after any of them was overwritten in place.
+
+    The Nq queries are the sequence's last Nq positions.  Under ``tail_causal`` query i sees keys
+    ``j <= k_lens[s] - Nq + i``; rows before position 0 are empty rows (O = 0, l = 0, m bytes 0xFA), so a batch that
+    mixes chunk sizes right-aligns each sequence's real queries in the Nq slots, as in ``paged_prefill_1d``.  The
+    kernel cuts the queries into blocks of ``max(1, 64 // next_pow2(Hq))`` and ends each block's key walk after its
+    last query's position.
+
+    ``draft_mask`` is ``paged_1d``'s tree mask: an int32 tensor ``batch + (Nq, ceil(Nq / 32))`` on the device of Q,
+    shared by the heads.  With ``base = k_lens[s] - Nq`` query i sees every key below ``base``, and draft slot j (the
+    key at ``base + j``) iff bit ``j & 31`` of ``draft_mask[s, i, j >> 5]`` is set.  It requires ``tail_causal=True``
+    and Nq <= 128.  Bits at or past Nq are ignored, slots at negative positions name no key, and a row that sees
+    nothing is the empty row.  Draft keys that a row does not see are loaded and masked, so they must be finite.
+    ``draft_mask_from_parents`` builds the mask of a forest.  A lower-triangle mask gives the bits of the same call
+    without a mask wherever that call runs this kernel (outside ``mla_paged_1d``'s envelope).
+
+    Where ``Hq * next_pow2(Nq) <= 512`` and there is no mask, the call IS ``mla_paged_1d``, bit for bit.  Envelope:
+    ``mla_paged_1d``'s without that bound, and Hq * Nq * v_channels < 2^31; outside it ``NotImplementedError`` names
+    the condition, and there is no fallback.  Not here: sliding windows, masks past 128 drafts, a ragged twin."""
+    return _mla_paged("mla_paged_prefill_1d", True, Q, KV_pool, block_table, k_lens, v_channels, tail_causal,
+                      softmax_scale, returning_l_m, kv_scale, draft_mask)
+
+
+def _mla_paged(what, blocked, Q, KV_pool, block_table, k_lens, v_channels, tail_causal, softmax_scale, returning_l_m,
+               kv_scale, draft_mask):
+    """``mla_paged_1d`` (``blocked`` False) and ``mla_paged_prefill_1d``: one set of checks in one order."""
     if len(KV_pool.shape) != 3:
         raise InvalidArgumentError("KV_pool should be [num_pages, channels, page], but KV_pool_shape = "
                                    + _shape_str(KV_pool.shape) + " was received")
@@ -1221,6 +1261,7 @@ def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False,
                                    + " were received")
     if block_table.device != Q.device or k_lens.device != Q.device:
         raise InvalidArgumentError("block_table and k_lens must be on the device of Q and KV_pool")
+    draft_mask = _decode_mask(what, draft_mask, tail_causal, None, Q, batch, nq)
     if softmax_scale is None:
         softmax_scale = 1.0 / float(q_ch) ** 0.5
     softmax_scale = float(softmax_scale)
@@ -1238,14 +1279,21 @@ def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False,
     cap = max_pages * page
     if cap > 2 ** 30:
         raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    if draft_mask is not None and nq > 128:
+        raise NotImplementedError(what + ": a draft_mask takes at most 128 draft tokens (four mask words a row), got "
+                                  f"Nq = {nq}")
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_channels)
     L = _lib.lib()
-    plan = (ctypes.c_int32 * 5)()
-    st = L.fa_forward_mla_paged_plan(prob, hq, page, plan)
+    # one block of mla_paged_1d's fold holds the queries and there is no mask: the call is mla_paged_1d's
+    blocked = blocked and (draft_mask is not None or hq * (1 << max(nq - 1, 0).bit_length()) > 512)
+    entry = "fa_forward_mla_paged_prefill" if blocked else "fa_forward_mla_paged"
+    plan = (ctypes.c_int32 * 6)()
+    st = getattr(L, entry + "_plan")(prob, hq, page, plan)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     if plan[0] == 0:
-        raise NotImplementedError(what + ": outside the envelope (" + _MLA_ENVELOPE + "; and " + _MLA_PAGE_CONDITION
+        envelope = _MLA_ENVELOPE_BLOCKED if blocked else _MLA_ENVELOPE
+        raise NotImplementedError(what + ": outside the envelope (" + envelope + "; and " + _MLA_PAGE_CONDITION
                                   + "), got Q_shape = " + _shape_str(Q.shape) + ", KV_pool_shape = "
                                   + _shape_str(KV_pool.shape) + ", v_channels = " + str(v_channels))
     _check_device_tensors(Q, KV_pool)
@@ -1254,16 +1302,18 @@ def mla_paged_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causal=False,
     O = torch.empty(batch + (hq, v_channels, nq), dtype=Q.dtype, device=Q.device)
     l = torch.empty(batch + (hq, nq), dtype=torch.float32, device=Q.device)
     m = torch.empty(batch + (hq, nq), dtype=Q.dtype, device=Q.device)
-    ws_bytes = int(L.fa_forward_mla_paged_workspace_bytes(prob, hq, page))
+    ws_bytes = int(getattr(L, entry + "_workspace_bytes")(prob, hq, page))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
         head = (_stream_handle(Q.device), prob, hq, Q.data_ptr(), KV_pool.data_ptr(), block_table.data_ptr(),
                 max_pages, page, num_pages, k_lens.data_ptr(), int(bool(tail_causal)), softmax_scale)
         tail = (O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
+        if blocked:
+            tail = (draft_mask.data_ptr() if draft_mask is not None else None,) + tail
         if fp8:
-            st = L.fa_forward_mla_paged_fp8(*head, kv_scale.data_ptr() if kv_scale is not None else None, *tail)
+            st = getattr(L, entry + "_fp8")(*head, kv_scale.data_ptr() if kv_scale is not None else None, *tail)
         else:
-            st = L.fa_forward_mla_paged(*head, *tail)
+            st = getattr(L, entry)(*head, *tail)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     return (O, l, m) if returning_l_m else O
