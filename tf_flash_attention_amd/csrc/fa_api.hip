@@ -180,6 +180,28 @@ constexpr int32_t kSplitMinRange = 2048;   // shorter key ranges never split
 constexpr int32_t kSplitTile = 64;         // the kernels' key tile
 constexpr int32_t kSplitMaxChunks = 64;    // bounds the workspace beside K and V
 
+// The chunk rule of every split plan below: a chunk is at least min_chunk keys, a multiple of the granule, and long
+// enough that at most max_chunks of them cover the span.  For positive integers ceil(ceil(x / a) / b) ==
+// ceil(x / (a * b)), so "ceil(span / max_chunks) rounded up to the granule" and "ceil(granules / max_chunks) granules"
+// are this one function.
+int32_t chunk_keys(int64_t span, int64_t max_chunks, int32_t min_chunk, int32_t granule) {
+  const int64_t cover = max_chunks * granule;
+  const int64_t keys = (span + cover - 1) / cover * granule;  // the capped chunk: max_chunks of them reach the span
+  return (int32_t)(keys > min_chunk ? keys : min_chunk);
+}
+
+// Its minimum, min_chunk = 512 keys up to 64 rows (`small`; each plan says rows of what) and 1024 above, so that the
+// partial records stay a fixed share of the K/V bytes (split_plan and bwd_qsplit_plan say which).
+int32_t chunk_min(bool small) { return small ? 512 : 1024; }
+
+// A window's chunks, boundaries at absolute multiples of the chunk: those the capacity nk holds, and of them as many
+// as an interval of span_w keys can touch.
+void window_chunks(int64_t nk, int32_t span_w, int32_t chunk, int32_t* cap_chunks, int32_t* nchunks) {
+  *cap_chunks = (int32_t)((nk + chunk - 1) / chunk);
+  const int32_t touched = (span_w + chunk - 2) / chunk + 1;
+  *nchunks = touched < *cap_chunks ? touched : *cap_chunks;
+}
+
 struct SplitPlan {
   int32_t nchunks, chunk, kb, ke, k_first;
 };
@@ -202,9 +224,7 @@ SplitPlan split_plan(const fa_problem* p) {
   const int32_t span = s.ke - s.k_first;
   // a partial is nq*(v_d+3) floats per chunk beside chunk*(d+v_d) halfs of K/V: above 64 queries the
   // chunks are twice as long, so the partials stay near an eighth of the K/V bytes
-  const int32_t min_chunk = nq <= 64 ? 512 : 1024;
-  const int32_t capped = ((span + kSplitMaxChunks - 1) / kSplitMaxChunks + kSplitTile - 1) / kSplitTile * kSplitTile;
-  s.chunk = capped > min_chunk ? capped : min_chunk;
+  s.chunk = chunk_keys(span, kSplitMaxChunks, chunk_min(nq <= 64), kSplitTile);
   s.nchunks = (span + s.chunk - 1) / s.chunk;
   return s;
 }
@@ -243,9 +263,7 @@ GroupedPlan grouped_plan(const fa_problem* p, int32_t kv_group, int32_t min_grou
 #endif
   s.k_first = s.kb / kSplitTile * kSplitTile;
   const int32_t span = s.ke - s.k_first;
-  const int32_t min_chunk = s.rows <= 64 ? 512 : 1024;
-  const int32_t capped = ((span + kSplitMaxChunks - 1) / kSplitMaxChunks + kSplitTile - 1) / kSplitTile * kSplitTile;
-  s.chunk = capped > min_chunk ? capped : min_chunk;
+  s.chunk = chunk_keys(span, kSplitMaxChunks, chunk_min(s.rows <= 64), kSplitTile);
   s.nchunks = (span + s.chunk - 1) / s.chunk;
   if (s.nchunks < 1) s.nchunks = 1;  // an empty range: one chunk without tiles, so the merge writes the empty rows
   return s;
@@ -317,12 +335,8 @@ WindowPlan window_plan(const fa_problem* p, const GroupedPlan& base, int32_t win
   w.span_w = (int32_t)(nk < window + nq - 1 ? nk : window + nq - 1);
   w.delegated = window >= nk;
   if (w.delegated) return w;
-  const int32_t min_chunk = base.rows <= 64 ? 512 : 1024;
-  const int32_t capped = ((w.span_w + kSplitMaxChunks - 1) / kSplitMaxChunks + kSplitTile - 1) / kSplitTile * kSplitTile;
-  w.g.chunk = capped > min_chunk ? capped : min_chunk;
-  w.cap_chunks = (int32_t)((nk + w.g.chunk - 1) / w.g.chunk);
-  const int32_t touched = (w.span_w + w.g.chunk - 2) / w.g.chunk + 1;
-  w.g.nchunks = touched < w.cap_chunks ? touched : w.cap_chunks;
+  w.g.chunk = chunk_keys(w.span_w, kSplitMaxChunks, chunk_min(base.rows <= 64), kSplitTile);
+  window_chunks(nk, w.span_w, w.g.chunk, &w.cap_chunks, &w.g.nchunks);
   return w;
 }
 
@@ -378,10 +392,7 @@ PrefillPlan prefill_plan(const fa_problem* p, int32_t kv_group, const GroupedPla
   w.g.kb = w.g.k_first = 0;
   w.g.ke = (int32_t)nk;
   const int32_t kmax = kSplitMaxChunks / nqb > 1 ? kSplitMaxChunks / nqb : 1;
-  const int32_t min_chunk = w.rows <= 64 ? 512 : 1024;
-  const int64_t tiles = (nk + kSplitTile - 1) / kSplitTile;
-  const int64_t capped = (tiles + kmax - 1) / kmax * kSplitTile;
-  w.g.chunk = (int32_t)(capped > min_chunk ? capped : min_chunk);
+  w.g.chunk = chunk_keys(nk, kmax, chunk_min(w.rows <= 64), kSplitTile);
   w.g.nchunks = (int32_t)((nk + w.g.chunk - 1) / w.g.chunk);
   return w;
 }
@@ -436,12 +447,8 @@ WindowPrefillPlan window_prefill_plan(const fa_problem* p, int32_t kv_group, con
     return w;
   }
   const int32_t kmax = kSplitMaxChunks / w.pp.nqb > 1 ? kSplitMaxChunks / w.pp.nqb : 1;
-  const int32_t min_chunk = w.pp.rows <= 64 ? 512 : 1024;
-  const int32_t capped = ((w.span_w + kmax - 1) / kmax + kSplitTile - 1) / kSplitTile * kSplitTile;
-  w.pp.g.chunk = capped > min_chunk ? capped : min_chunk;
-  w.cap_chunks = (int32_t)((nk + w.pp.g.chunk - 1) / w.pp.g.chunk);
-  const int32_t touched = (w.span_w + w.pp.g.chunk - 2) / w.pp.g.chunk + 1;
-  w.pp.g.nchunks = touched < w.cap_chunks ? touched : w.cap_chunks;
+  w.pp.g.chunk = chunk_keys(w.span_w, kmax, chunk_min(w.pp.rows <= 64), kSplitTile);
+  window_chunks(nk, w.span_w, w.pp.g.chunk, &w.cap_chunks, &w.pp.g.nchunks);
   return w;
 }
 
@@ -518,9 +525,7 @@ QSplitPlan bwd_qsplit_plan(const fa_problem* p) {
   const int32_t span = s.qe - s.q_first;
   // a partial is nk*(d+v_d) floats per chunk beside chunk*(d+v_d) halfs of Q/dO: above 64 keys the chunks
   // are twice as long, so the partials stay within a quarter of the Q/dO bytes
-  const int32_t min_chunk = nk <= 64 ? 512 : 1024;
-  const int32_t capped = ((span + kSplitMaxChunks - 1) / kSplitMaxChunks + kQSplitGroup - 1) / kQSplitGroup * kQSplitGroup;
-  s.chunk = capped > min_chunk ? capped : min_chunk;
+  s.chunk = chunk_keys(span, kSplitMaxChunks, chunk_min(nk <= 64), kQSplitGroup);
   s.nchunks = (span + s.chunk - 1) / s.chunk;
   return s;
 }
@@ -583,6 +588,26 @@ int check_kv_per_len(int64_t bkv, int32_t kv_per_len) {
   return FA_OK;
 }
 
+// the checks of a block table's extents, under the caller's name and its name for the capacity
+int check_table(const std::string& name, int32_t max_pages, int32_t page, int64_t num_pages, int64_t capacity,
+                const char* capacity_name) {
+  if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": max_pages must be >= 1");
+  if ((int64_t)max_pages * page != capacity)
+    return set_error(FA_ERR_INVALID_ARGUMENT, name + ": max_pages * page = " + std::to_string((int64_t)max_pages * page) +
+                                                  " is not the capacity " + capacity_name + " = " + std::to_string(capacity));
+  if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": num_pages must be >= 1");
+  return FA_OK;
+}
+
+// the largest page a block-table entry may name (an int32 entry reaches no further)
+int32_t last_page(int64_t num_pages) { return (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff); }
+
+// a launch's status: FA_OK, or HIP's error with the message every entry point gives
+int launched(hipError_t e, const char* kernel) {
+  if (e == hipSuccess) return FA_OK;
+  return set_error((int)e, std::string("Failed to launch the ") + kernel + " kernel: " + hipGetErrorString(e));
+}
+
 #ifdef FA_DIAG
 // Diagnostic library only: FA_SLAB_MAX, read on every call like the variant selectors, lowers the slab limit of
 // the four slab loops below (fewq_slabs, bwd_slabs, fa_merge_partials, fa_accumulate_parts) so that a test can
@@ -634,9 +659,8 @@ int fewq_slabs(const fa_problem* p, const FewqPtrs& t, int32_t g, int64_t rows, 
     a.m = static_cast<uint16_t*>(t.m) + b0 * g * nq;
     sa->ws = static_cast<float*>(t.workspace) + b0 * nqb * sa->nchunks * fa::fewq_record_floats(p->v_d, rows);
     FA_DIAG_SLAB();
-    const hipError_t e = launch(b0);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
+    const int st = launched(launch(b0), "Forward");
+    if (st != FA_OK) return st;
   }
   return FA_OK;
 }
@@ -674,9 +698,8 @@ int bwd_slabs(const fa_problem* p, const fa::BwdArgs& whole, int64_t bmax, fa::B
     a->ws_D = static_cast<float*>(whole.ws_D) + b0 * nq;
     a->ws_lse = static_cast<float*>(whole.ws_lse) + b0 * nq;
     FA_DIAG_SLAB();
-    const hipError_t e = launch(b0);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
+    const int st = launched(launch(b0), "Backward");
+    if (st != FA_OK) return st;
   }
   return FA_OK;
 }
@@ -774,9 +797,7 @@ int fa_forward(void* stream, const fa_problem* p, const void* Q, const void* K, 
     case FwdFamily::kGeneric: e = fa::launch_fwd_generic(p->dtype, a, s); break;
     default: return set_error(FA_ERR_UNSUPPORTED, kGenericUnsupported);
   }
-  if (e != hipSuccess)
-    return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
-  return FA_OK;
+  return launched(e, "Forward");
 }
 
 const char* fa_forward_kernel(const fa_problem* p, const void* Q, const void* K, const void* V) {
@@ -947,14 +968,8 @@ static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, c
   if (kst != FA_OK) return kst;
   const int wst = c.window ? check_window(*c.window) : FA_OK;
   if (wst != FA_OK) return wst;
-  if (pg) {
-    if (pg->max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: max_pages must be >= 1");
-    if ((int64_t)pg->max_pages * pg->page != p->k_seq[0])
-      return set_error(FA_ERR_INVALID_ARGUMENT,
-                       "paged forward: max_pages * page = " + std::to_string((int64_t)pg->max_pages * pg->page) +
-                           " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
-    if (pg->num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: num_pages must be >= 1");
-  }
+  const int tst = pg ? check_table("paged forward", pg->max_pages, pg->page, pg->num_pages, p->k_seq[0], "k_seq[0]") : FA_OK;
+  if (tst != FA_OK) return tst;
   const GroupedPlan base = cache_plan(p, kv_group, page);
   const bool both = c.window && c.prefill;
   const WindowPrefillPlan wpp = both ? window_prefill_plan(p, kv_group, base, pg ? pg->page : 0, *c.window) : WindowPrefillPlan{};
@@ -991,7 +1006,7 @@ static int forward_decode(void* stream, const fa_problem* p, int32_t kv_group, c
   FewqPtrs ptrs = {Q, K, V, O, l, m, workspace, c.kv8 ? 1 : 2};
   if (pg) {
     pa.block_table = pg->block_table; pa.max_pages = pg->max_pages; pa.page = pg->page;
-    pa.last_page = (int32_t)(pg->num_pages - 1 < 0x7fffffff ? pg->num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
+    pa.last_page = last_page(pg->num_pages);
     ra.g.s.f.K = K; ra.g.s.f.V = V;  // the pools are not sliced per launch: the table says where a slice's keys are
     ptrs.K = ptrs.V = nullptr;
   }
@@ -1242,14 +1257,21 @@ int fa_forward_paged_tree_fp8(void* stream, const fa_problem* p, int32_t kv_grou
   return forward_decode(stream, p, kv_group, Q, K_pool8, V_pool8, {&pg, &kv8, nullptr, false, true, draft_mask}, k_lens, kv_per_len, 1, O, l, m, workspace, workspace_bytes);
 }
 
-// ---- MLA decode over a paged latent cache (include/fa_api.h; fa_fwd_f16_mla.hip): `heads` query
-// heads against one K/V head whose values are the first v_d channels of its keys.  The plan: the heads' P query
-// slots folded into R = heads * P rows, blocks of 64 rows, and ragged_plan's chunk formula over the capacity (a
-// 512-key minimum up to 64 rows, 1024 above; at most 64 chunks).  A pure function of the problem without b.
+// ---- MLA attention over a paged latent cache (include/fa_api.h; fa_fwd_f16_mla.hip,
+// fa_fwd_f16_mla_prefill.hip): `heads` query heads against one K/V head whose values are the first v_d channels of its
+// keys, in two forms that share every check, the workspace and the arguments.  Both plans are chunk_keys over the
+// capacity, and pure functions of the problem without b, the lengths, the table, tail_causal or the mask.
+//   decode:  the heads' pitch = next_pow2(nq) query slots folded into rows = heads * pitch <= 512, nrb blocks of 64
+//            rows; at most 64 chunks, of at least 512 keys up to 64 rows and 1024 above.
+//   blocked: the query-blocked and tree-masked form, any nq.  A block of 64 rows holds pitch = max(1, 64 /
+//            next_pow2(heads)) queries of 64 / pitch heads, so a sequence has nrb = nqb * nhb blocks, nqb = ceil(nq /
+//            pitch), nhb = ceil(heads / (64 / pitch)) (1 or 2).  As in the prefill forms the blocks already supply
+//            workgroups and every (block, chunk) costs a record: at most max(1, 64 / nrb) chunks, of at least 512
+//            keys for one block and 1024 above.
 constexpr int32_t kMlaMaxC = 576, kMlaMaxV = 512, kMlaMaxHeads = 128, kMlaMaxRows = 512, kMlaBlockRows = 64;
 
 struct MlaPlan {
-  int32_t nchunks, chunk, pitch, rows, nrb;
+  int32_t nchunks, chunk, pitch, rows, nrb, nqb, nhb;  // rows: decode only; nqb, nhb: blocked only
 };
 
 static int check_mla(const fa_problem* p, int32_t heads, int32_t page) {
@@ -1269,23 +1291,31 @@ static int check_mla(const fa_problem* p, int32_t heads, int32_t page) {
 }
 
 // (after check_mla)
-static MlaPlan mla_plan(const fa_problem* p, int32_t heads, int32_t page) {
+static MlaPlan mla_plan(const fa_problem* p, int32_t heads, int32_t page, bool blocked) {
   MlaPlan s = {};
-  const int64_t nq = p->q_seq[0];
-  if (p->seq_dims == 1 && nq >= 1) {
+  const int64_t nq = p->q_seq[0], nk = p->k_seq[0];
+  if (!blocked && p->seq_dims == 1 && nq >= 1) {  // (the fold is reported outside the envelope too)
     s.pitch = next_pow2((int32_t)nq);
     s.rows = (int64_t)heads * s.pitch <= 0x7fffffff ? heads * s.pitch : 0x7fffffff;
     s.nrb = (int32_t)(((int64_t)s.rows + kMlaBlockRows - 1) / kMlaBlockRows);
   }
-  const int32_t nk = p->k_seq[0];
   const bool inside = p->dtype == FA_F16 && p->seq_dims == 1 && p->d % 64 == 0 && p->d >= 64 && p->d <= kMlaMaxC &&
                       p->v_d % 64 == 0 && p->v_d >= 64 && p->v_d <= kMlaMaxV && p->v_d <= p->d && page % kSplitTile == 0 &&
-                      heads <= kMlaMaxHeads && nq >= 1 && (int64_t)heads * s.pitch <= kMlaMaxRows && nk >= 1;
-  if (!inside) return s;
-  const int32_t min_chunk = s.rows <= 64 ? 512 : 1024;
-  const int32_t capped = ((nk + kSplitMaxChunks - 1) / kSplitMaxChunks + kSplitTile - 1) / kSplitTile * kSplitTile;
-  s.chunk = capped > min_chunk ? capped : min_chunk;
-  s.nchunks = (nk + s.chunk - 1) / s.chunk;
+                      heads <= kMlaMaxHeads && nq >= 1 && nk >= 1;
+  // each form's own clause: decode's fold has 512 rows; the blocked merge counts a sequence's outputs in 32 bits
+  if (!inside || (blocked ? nq * heads * p->v_d > 0x7fffffff : (int64_t)heads * s.pitch > kMlaMaxRows)) return s;
+  int32_t kmax = kSplitMaxChunks;
+  if (blocked) {
+    const int32_t hp = next_pow2(heads);
+    s.pitch = hp >= kMlaBlockRows ? 1 : kMlaBlockRows / hp;
+    const int32_t hpb = kMlaBlockRows / s.pitch;
+    s.nhb = (heads + hpb - 1) / hpb;
+    s.nqb = (int32_t)((nq + s.pitch - 1) / s.pitch);
+    s.nrb = s.nqb * s.nhb;
+    kmax = kSplitMaxChunks / s.nrb > 1 ? kSplitMaxChunks / s.nrb : 1;
+  }
+  s.chunk = chunk_keys(nk, kmax, chunk_min(blocked ? s.nrb == 1 : s.rows <= 64), kSplitTile);
+  s.nchunks = (int32_t)((nk + s.chunk - 1) / s.chunk);
   return s;
 }
 
@@ -1294,48 +1324,66 @@ static size_t mla_ws_bytes(const fa_problem* p, int32_t heads, const MlaPlan& s)
                   (size_t)fa::fewq_record_floats(p->v_d, kMlaBlockRows) * sizeof(float));
 }
 
-int fa_forward_mla_paged_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[5]) {
+// the _plan and _workspace_bytes entry points of both forms; out: {nchunks, chunk, pitch, rows, nrb}, or blocked
+// {nchunks, chunk, pitch, nrb, nqb, nhb}
+static int mla_plan_out(const fa_problem* p, int32_t heads, int32_t page, bool blocked, int32_t* out) {
   const int st = check_mla(p, heads, page);
   if (st != FA_OK) return st;
   if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  const MlaPlan s = mla_plan(p, heads, page);
-  out[0] = s.nchunks; out[1] = s.chunk; out[2] = s.pitch; out[3] = s.rows; out[4] = s.nrb;
+  const MlaPlan s = mla_plan(p, heads, page, blocked);
+  out[0] = s.nchunks; out[1] = s.chunk; out[2] = s.pitch;
+  if (blocked) { out[3] = s.nrb; out[4] = s.nqb; out[5] = s.nhb; }
+  else { out[3] = s.rows; out[4] = s.nrb; }
   return FA_OK;
 }
 
-size_t fa_forward_mla_paged_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page) {
+static size_t mla_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page, bool blocked) {
   if (check_mla(p, heads, page) != FA_OK) return 0;
-  const MlaPlan s = mla_plan(p, heads, page);
+  const MlaPlan s = mla_plan(p, heads, page, blocked);
   return s.nchunks ? mla_ws_bytes(p, heads, s) : 0;
 }
 
-// both pool encodings: every check is the fp16 entry point's (the plan does not know the encoding); `fp8` takes
-// the pool as e4m3fn bytes with the device scale `kv_scale` (null: 1.0), which only the kernel reads
-static int forward_mla(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool, bool fp8,
-                       const float* kv_scale, const int32_t* block_table, int32_t max_pages, int32_t page,
-                       int64_t num_pages, const int32_t* k_lens, int32_t tail_causal, float softmax_scale, void* O,
-                       void* l, void* m, void* workspace, size_t workspace_bytes) {
+struct MlaKind {
+  bool blocked;           // the query-blocked form, with
+  const int32_t* mask;    //   its device bit mask over the draft slots (nullable)
+  bool fp8;               // the pool as e4m3fn bytes, with
+  const float* kv_scale;  //   its device scale (null: 1.0), which only the kernel reads
+};
+
+// Every MLA forward: the same checks (the plan does not know the pool's encoding), plan, workspace and arguments;
+// the kind picks the launcher.
+static int forward_mla(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
+                       const MlaKind& c, const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                       const int32_t* k_lens, int32_t tail_causal, float softmax_scale, void* O, void* l, void* m,
+                       void* workspace, size_t workspace_bytes) {
+  const std::string name = c.blocked ? "MLA paged prefill forward" : "MLA paged forward";
   const int st = check_mla(p, heads, page);
   if (st != FA_OK) return st;
-  if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: max_pages must be >= 1");
-  if (p->seq_dims == 1 && (int64_t)max_pages * page != p->k_seq[0])
-    return set_error(FA_ERR_INVALID_ARGUMENT,
-                     "MLA paged forward: max_pages * page = " + std::to_string((int64_t)max_pages * page) +
-                         " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
-  if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: num_pages must be >= 1");
+  // (2d sequences have no capacity to compare: the envelope refuses them below)
+  const int tst = check_table("MLA paged forward", max_pages, page, num_pages,
+                              p->seq_dims == 1 ? p->k_seq[0] : (int64_t)max_pages * page, "k_seq[0]");
+  if (tst != FA_OK) return tst;
   if (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale))
     return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: softmax_scale must be positive and finite");
-  const MlaPlan mp = mla_plan(p, heads, page);
+  if (c.mask && !tail_causal)
+    return set_error(FA_ERR_INVALID_ARGUMENT, name + ": a draft_mask requires tail_causal (the draft slots are the sequence's last positions)");
+  if (c.mask && p->q_seq[0] > 128)
+    return set_error(FA_ERR_INVALID_ARGUMENT, name + ": a draft_mask takes at most 128 queries, got nq = " + std::to_string(p->q_seq[0]));
+  const MlaPlan mp = mla_plan(p, heads, page, c.blocked);
   if (mp.nchunks == 0)
     return set_error(FA_ERR_UNSUPPORTED,
-                     "MLA paged forward: outside the envelope (fp16, 1d sequences, d % 64 == 0, 64 <= d <= 576, "
-                     "v_d % 64 == 0, 64 <= v_d <= min(d, 512), page % 64 == 0, 1 <= heads <= 128, nq >= 1, "
-                     "heads * pitch <= 512, nk >= 1)");
+                     name + ": outside the envelope (fp16, 1d sequences, d % 64 == 0, 64 <= d <= 576, "
+                     "v_d % 64 == 0, 64 <= v_d <= min(d, 512), page % 64 == 0, 1 <= heads <= 128, nq >= 1, " +
+                         (c.blocked ? "heads * nq * v_d < 2^31" : "heads * pitch <= 512") + ", nk >= 1)");
   const int64_t seqs = p->b / heads, nq = p->q_seq[0];
+  // (the two forms were written with different codes here, and tests/test_mla_prefill_api.py,
+  // test_argument_errors_of_the_entry_points, pins the blocked one)
   if (seqs * mp.nrb * mp.nchunks > 0x7fffffff || (seqs * p->v_d * heads * nq + 255) / 256 > 0x7fffffff)
-    return set_error(FA_ERR_UNSUPPORTED, "MLA paged forward: b = " + std::to_string(p->b) + " needs a launch grid of 2^31 workgroups or more");
+    return set_error(c.blocked ? FA_ERR_INVALID_ARGUMENT : FA_ERR_UNSUPPORTED,
+                     name + ": b = " + std::to_string(p->b) + " needs a launch grid of 2^31 workgroups or more");
   if (!workspace || workspace_bytes < mla_ws_bytes(p, heads, mp))
-    return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "forward workspace is smaller than fa_forward_mla_paged_workspace_bytes()");
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL, std::string("forward workspace is smaller than fa_forward_mla_paged_") +
+                                                     (c.blocked ? "prefill_" : "") + "workspace_bytes()");
   FA_DIAG_COUNT(0);
   if (p->b == 0) return FA_OK;
   if (!Q || !O || !l || !m) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null Q, O, l or m");
@@ -1344,7 +1392,8 @@ static int forward_mla(void* stream, const fa_problem* p, int32_t heads, const v
   if (!KV_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null KV_pool");
   if (reinterpret_cast<uintptr_t>(KV_pool) & 15)
     return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: KV_pool must be 16-byte aligned");
-  fa::MlaArgs ma = {};
+  fa::MlaPrefillArgs pa = {};  // the blocked form's arguments: decode sends the part it has
+  fa::MlaArgs& ma = pa.m;
   fill_split(p, {mp.nchunks, mp.chunk, 0, p->k_seq[0], 0}, &ma.s);
   fa::FwdArgs& a = ma.s.f;
   a.Q = Q; a.K = KV_pool; a.V = nullptr; a.O = O; a.l = l; a.m = m;
@@ -1354,143 +1403,43 @@ static int forward_mla(void* stream, const fa_problem* p, int32_t heads, const v
   ma.block_table = block_table; ma.k_lens = k_lens;
   ma.heads = heads; ma.pitch = mp.pitch; ma.log2_pitch = ilog2(mp.pitch); ma.nrb = mp.nrb;
   ma.max_pages = max_pages; ma.page = page;
-  ma.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
+  ma.last_page = last_page(num_pages);
   ma.tail_causal = tail_causal != 0;
-  const hipError_t e = fp8 ? fa::launch_fwd_f16_mla_fp8(fa::MlaFp8Args{ma, kv_scale}, static_cast<hipStream_t>(stream))
-                          : fa::launch_fwd_f16_mla(ma, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
-  return FA_OK;
+  pa.mask = reinterpret_cast<const uint32_t*>(c.mask);
+  pa.nhb = mp.nhb;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return launched(c.blocked ? (c.fp8 ? fa::launch_fwd_f16_mla_prefill_fp8({pa, c.kv_scale}, s) : fa::launch_fwd_f16_mla_prefill(pa, s))
+                            : (c.fp8 ? fa::launch_fwd_f16_mla_fp8({ma, c.kv_scale}, s) : fa::launch_fwd_f16_mla(ma, s)),
+                  "Forward");
+}
+
+int fa_forward_mla_paged_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[5]) {
+  return mla_plan_out(p, heads, page, false, out);
+}
+size_t fa_forward_mla_paged_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page) {
+  return mla_workspace_bytes(p, heads, page, false);
+}
+int fa_forward_mla_paged_prefill_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[6]) {
+  return mla_plan_out(p, heads, page, true, out);
+}
+size_t fa_forward_mla_paged_prefill_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page) {
+  return mla_workspace_bytes(p, heads, page, true);
 }
 
 int fa_forward_mla_paged(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
                          const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
                          const int32_t* k_lens, int32_t tail_causal, float softmax_scale, void* O, void* l, void* m,
                          void* workspace, size_t workspace_bytes) {
-  return forward_mla(stream, p, heads, Q, KV_pool, false, nullptr, block_table, max_pages, page, num_pages, k_lens,
-                     tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
+  return forward_mla(stream, p, heads, Q, KV_pool, {}, block_table, max_pages, page, num_pages, k_lens, tail_causal,
+                     softmax_scale, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_mla_paged_fp8(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool8,
                              const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
                              const int32_t* k_lens, int32_t tail_causal, float softmax_scale, const float* kv_scale,
                              void* O, void* l, void* m, void* workspace, size_t workspace_bytes) {
-  return forward_mla(stream, p, heads, Q, KV_pool8, true, kv_scale, block_table, max_pages, page, num_pages, k_lens,
-                     tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
-}
-
-// ---- the query-blocked and tree-masked forms of the MLA forward (include/fa_api.h; DESIGN.md §3.22;
-// fa_fwd_f16_mla_prefill.hip): any nq.  A block of 64 rows holds pb = max(1, 64 / next_pow2(heads)) queries of
-// 64 / pb heads, so a sequence has nrb = ceil(nq / pb) * nhb blocks, nhb = ceil(heads / (64 / pb)) (1 or 2).  The
-// chunks follow the prefill forms' rule: the blocks already supply workgroups and every (block, chunk) costs a record,
-// so at most max(1, 64 / nrb) chunks, of at least decode's minimum (512 keys for one block, 1024 above).  A pure
-// function of the problem without b, the lengths, the table, tail_causal or the mask.
-struct MlaPrefillPlan {
-  int32_t nchunks, chunk, pb, nrb, nqb, nhb;
-};
-
-// (after check_mla)
-static MlaPrefillPlan mla_prefill_plan(const fa_problem* p, int32_t heads, int32_t page) {
-  MlaPrefillPlan s = {};
-  const int64_t nq = p->q_seq[0], nk = p->k_seq[0];
-  const bool inside = p->dtype == FA_F16 && p->seq_dims == 1 && p->d % 64 == 0 && p->d >= 64 && p->d <= kMlaMaxC &&
-                      p->v_d % 64 == 0 && p->v_d >= 64 && p->v_d <= kMlaMaxV && p->v_d <= p->d && page % kSplitTile == 0 &&
-                      heads <= kMlaMaxHeads && nq >= 1 && nk >= 1 &&
-                      nq * heads * p->v_d <= 0x7fffffff;  // (the merge counts a sequence's outputs in 32 bits)
-  if (!inside) return s;
-  const int32_t hp = next_pow2(heads);
-  s.pb = hp >= kMlaBlockRows ? 1 : kMlaBlockRows / hp;
-  const int32_t hpb = kMlaBlockRows / s.pb;
-  s.nhb = (heads + hpb - 1) / hpb;
-  const int64_t nqb = (nq + s.pb - 1) / s.pb;
-  s.nqb = (int32_t)nqb;
-  s.nrb = (int32_t)(nqb * s.nhb);
-  const int32_t kmax = kSplitMaxChunks / s.nrb > 1 ? kSplitMaxChunks / s.nrb : 1;
-  const int32_t min_chunk = s.nrb == 1 ? 512 : 1024;
-  const int64_t tiles = (nk + kSplitTile - 1) / kSplitTile;
-  const int64_t capped = (tiles + kmax - 1) / kmax * kSplitTile;
-  s.chunk = (int32_t)(capped > min_chunk ? capped : min_chunk);
-  s.nchunks = (int32_t)((nk + s.chunk - 1) / s.chunk);
-  return s;
-}
-
-static size_t mla_prefill_ws_bytes(const fa_problem* p, int32_t heads, const MlaPrefillPlan& s) {
-  return align_up((size_t)(p->b / heads) * (size_t)s.nrb * (size_t)s.nchunks *
-                  (size_t)fa::fewq_record_floats(p->v_d, kMlaBlockRows) * sizeof(float));
-}
-
-int fa_forward_mla_paged_prefill_plan(const fa_problem* p, int32_t heads, int32_t page, int32_t out[6]) {
-  const int st = check_mla(p, heads, page);
-  if (st != FA_OK) return st;
-  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
-  const MlaPrefillPlan s = mla_prefill_plan(p, heads, page);
-  out[0] = s.nchunks; out[1] = s.chunk; out[2] = s.pb; out[3] = s.nrb; out[4] = s.nqb; out[5] = s.nhb;
-  return FA_OK;
-}
-
-size_t fa_forward_mla_paged_prefill_workspace_bytes(const fa_problem* p, int32_t heads, int32_t page) {
-  if (check_mla(p, heads, page) != FA_OK) return 0;
-  const MlaPrefillPlan s = mla_prefill_plan(p, heads, page);
-  return s.nchunks ? mla_prefill_ws_bytes(p, heads, s) : 0;
-}
-
-// both pool encodings, as forward_mla; `draft_mask` (nullable) is the device bit mask over the draft slots
-static int forward_mla_prefill(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
-                               bool fp8, const float* kv_scale, const int32_t* block_table, int32_t max_pages,
-                               int32_t page, int64_t num_pages, const int32_t* k_lens, int32_t tail_causal,
-                               float softmax_scale, const int32_t* draft_mask, void* O, void* l, void* m,
-                               void* workspace, size_t workspace_bytes) {
-  const int st = check_mla(p, heads, page);
-  if (st != FA_OK) return st;
-  if (max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: max_pages must be >= 1");
-  if (p->seq_dims == 1 && (int64_t)max_pages * page != p->k_seq[0])
-    return set_error(FA_ERR_INVALID_ARGUMENT,
-                     "MLA paged forward: max_pages * page = " + std::to_string((int64_t)max_pages * page) +
-                         " is not the capacity k_seq[0] = " + std::to_string(p->k_seq[0]));
-  if (num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: num_pages must be >= 1");
-  if (!(softmax_scale > 0.f) || !std::isfinite(softmax_scale))
-    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: softmax_scale must be positive and finite");
-  if (draft_mask && !tail_causal)
-    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged prefill forward: a draft_mask requires tail_causal (the draft slots are the sequence's last positions)");
-  if (draft_mask && p->q_seq[0] > 128)
-    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged prefill forward: a draft_mask takes at most 128 queries, got nq = " + std::to_string(p->q_seq[0]));
-  const MlaPrefillPlan mp = mla_prefill_plan(p, heads, page);
-  if (mp.nchunks == 0)
-    return set_error(FA_ERR_UNSUPPORTED,
-                     "MLA paged prefill forward: outside the envelope (fp16, 1d sequences, d % 64 == 0, 64 <= d <= 576, "
-                     "v_d % 64 == 0, 64 <= v_d <= min(d, 512), page % 64 == 0, 1 <= heads <= 128, nq >= 1, "
-                     "heads * nq * v_d < 2^31, nk >= 1)");
-  const int64_t seqs = p->b / heads, nq = p->q_seq[0];
-  if (seqs * mp.nrb * mp.nchunks > 0x7fffffff || (seqs * p->v_d * heads * nq + 255) / 256 > 0x7fffffff)
-    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged prefill forward: b = " + std::to_string(p->b) + " needs a launch grid of 2^31 workgroups or more");
-  if (!workspace || workspace_bytes < mla_prefill_ws_bytes(p, heads, mp))
-    return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "forward workspace is smaller than fa_forward_mla_paged_prefill_workspace_bytes()");
-  FA_DIAG_COUNT(0);
-  if (p->b == 0) return FA_OK;
-  if (!Q || !O || !l || !m) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null Q, O, l or m");
-  if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
-  if (!block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null block_table");
-  if (!KV_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: null KV_pool");
-  if (reinterpret_cast<uintptr_t>(KV_pool) & 15)
-    return set_error(FA_ERR_INVALID_ARGUMENT, "MLA paged forward: KV_pool must be 16-byte aligned");
-  fa::MlaPrefillArgs pa = {};
-  fa::MlaArgs& ma = pa.m;
-  fill_split(p, {mp.nchunks, mp.chunk, 0, p->k_seq[0], 0}, &ma.s);
-  fa::FwdArgs& a = ma.s.f;
-  a.Q = Q; a.K = KV_pool; a.V = nullptr; a.O = O; a.l = l; a.m = m;
-  a.b = seqs;
-  a.scale = (double)softmax_scale;
-  ma.s.ws = static_cast<float*>(workspace);
-  ma.block_table = block_table; ma.k_lens = k_lens;
-  ma.heads = heads; ma.pitch = mp.pb; ma.log2_pitch = ilog2(mp.pb); ma.nrb = mp.nrb;
-  ma.max_pages = max_pages; ma.page = page;
-  ma.last_page = (int32_t)(num_pages - 1 < 0x7fffffff ? num_pages - 1 : 0x7fffffff);
-  ma.tail_causal = tail_causal != 0;
-  pa.mask = reinterpret_cast<const uint32_t*>(draft_mask);
-  pa.nhb = mp.nhb;
-  const hipError_t e = fp8 ? fa::launch_fwd_f16_mla_prefill_fp8(fa::MlaPrefillFp8Args{pa, kv_scale}, static_cast<hipStream_t>(stream))
-                          : fa::launch_fwd_f16_mla_prefill(pa, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return set_error((int)e, std::string("Failed to launch the Forward kernel: ") + hipGetErrorString(e));
-  return FA_OK;
+  return forward_mla(stream, p, heads, Q, KV_pool8, {false, nullptr, true, kv_scale}, block_table, max_pages, page,
+                     num_pages, k_lens, tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_mla_paged_prefill(void* stream, const fa_problem* p, int32_t heads, const void* Q, const void* KV_pool,
@@ -1498,8 +1447,8 @@ int fa_forward_mla_paged_prefill(void* stream, const fa_problem* p, int32_t head
                                  const int32_t* k_lens, int32_t tail_causal, float softmax_scale,
                                  const int32_t* draft_mask, void* O, void* l, void* m, void* workspace,
                                  size_t workspace_bytes) {
-  return forward_mla_prefill(stream, p, heads, Q, KV_pool, false, nullptr, block_table, max_pages, page, num_pages,
-                             k_lens, tail_causal, softmax_scale, draft_mask, O, l, m, workspace, workspace_bytes);
+  return forward_mla(stream, p, heads, Q, KV_pool, {true, draft_mask}, block_table, max_pages, page, num_pages, k_lens,
+                     tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
 }
 
 int fa_forward_mla_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t heads, const void* Q,
@@ -1507,8 +1456,8 @@ int fa_forward_mla_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t 
                                      int64_t num_pages, const int32_t* k_lens, int32_t tail_causal, float softmax_scale,
                                      const float* kv_scale, const int32_t* draft_mask, void* O, void* l, void* m,
                                      void* workspace, size_t workspace_bytes) {
-  return forward_mla_prefill(stream, p, heads, Q, KV_pool8, true, kv_scale, block_table, max_pages, page, num_pages,
-                             k_lens, tail_causal, softmax_scale, draft_mask, O, l, m, workspace, workspace_bytes);
+  return forward_mla(stream, p, heads, Q, KV_pool8, {true, draft_mask, true, kv_scale}, block_table, max_pages, page,
+                     num_pages, k_lens, tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
 }
 
 // ---- the fused K/V append of the same four caches (include/fa_api.h): every check on the host
@@ -1528,12 +1477,8 @@ static int cache_append(void* stream, int64_t sequences, int32_t kv_heads, int32
                                                   " must be >= 1");
   if (pg) {
     if (pg->page < 1) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": page must be >= 1");
-    if (pg->max_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": max_pages must be >= 1");
-    if ((int64_t)pg->max_pages * pg->page != nk)
-      return set_error(FA_ERR_INVALID_ARGUMENT,
-                       name + ": max_pages * page = " + std::to_string((int64_t)pg->max_pages * pg->page) +
-                           " is not the capacity nk = " + std::to_string(nk));
-    if (pg->num_pages < 1) return set_error(FA_ERR_INVALID_ARGUMENT, name + ": num_pages must be >= 1");
+    const int tst = check_table(name, pg->max_pages, pg->page, pg->num_pages, nk, "nk");
+    if (tst != FA_OK) return tst;
     if (pg->page % kSplitTile != 0)
       return set_error(FA_ERR_UNSUPPORTED, name + ": outside the envelope (page % 64 == 0), got page = " + std::to_string(pg->page));
   }
@@ -1556,15 +1501,13 @@ static int cache_append(void* stream, int64_t sequences, int32_t kv_heads, int32
   if (kv8) { a.k_scale = kv8->k_scale; a.v_scale = kv8->v_scale; }
   if (pg) {
     a.block_table = pg->block_table; a.max_pages = pg->max_pages; a.page = pg->page;
-    a.last_page = (int32_t)(pg->num_pages - 1 < 0x7fffffff ? pg->num_pages - 1 : 0x7fffffff);  // (an int32 entry reaches no further)
+    a.last_page = last_page(pg->num_pages);
   }
   a.k_lens = k_lens; a.new_lens = new_lens;
   a.kv_heads = kv_heads; a.d = d; a.v_d = v_d; a.n_new = n_new; a.nk = nk;
   a.chunks = (int32_t)chunks; a.slice_blocks = (int32_t)slice_blocks;
-  const hipError_t e = fa::launch_cache_append(pg != nullptr, kv8 != nullptr, a, sequences * kv_heads * slice_blocks,
-                                               static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return set_error((int)e, std::string("Failed to launch the append kernel: ") + hipGetErrorString(e));
-  return FA_OK;
+  return launched(fa::launch_cache_append(pg != nullptr, kv8 != nullptr, a, sequences * kv_heads * slice_blocks,
+                                          static_cast<hipStream_t>(stream)), "append");
 }
 
 int fa_append_ragged(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new, int32_t nk,
@@ -1648,9 +1591,7 @@ int fa_backward(void* stream, const fa_problem* p, const void* Q, const void* K,
   } else {
     return set_error(FA_ERR_UNSUPPORTED, kGenericUnsupported);
   }
-  if (e != hipSuccess)
-    return set_error((int)e, std::string("Failed to launch the Backward kernel: ") + hipGetErrorString(e));
-  return FA_OK;
+  return launched(e, "Backward");
 }
 
 int fa_backward_split_plan(const fa_problem* p, int32_t out[4]) {
@@ -1775,9 +1716,8 @@ int fa_merge_partials(void* stream, int32_t dtype, int64_t b, int64_t nq, int32_
     a.l = static_cast<char*>(l) + l_off;
     a.m = static_cast<char*>(m) + m_off;
     FA_DIAG_SLAB();
-    const hipError_t e = fa::launch_merge(dtype, n_parts, a, s);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the merge kernel: ") + hipGetErrorString(e));
+    const int st = launched(fa::launch_merge(dtype, n_parts, a, s), "merge");
+    if (st != FA_OK) return st;
   }
   return FA_OK;
 }
@@ -1806,9 +1746,8 @@ int fa_accumulate_parts(void* stream, int32_t dtype, int64_t count, int32_t n_pa
     for (int i = 0; i < n_parts; ++i) a.parts[i] = static_cast<const char*>(parts[i]) + es * (size_t)c0;
     a.out = static_cast<char*>(out) + es * (size_t)c0;
     FA_DIAG_SLAB();
-    const hipError_t e = fa::launch_accumulate(dtype, n_parts, a, s);
-    if (e != hipSuccess)
-      return set_error((int)e, std::string("Failed to launch the accumulate kernel: ") + hipGetErrorString(e));
+    const int st = launched(fa::launch_accumulate(dtype, n_parts, a, s), "accumulate");
+    if (st != FA_OK) return st;
   }
   return FA_OK;
 }
