@@ -659,6 +659,37 @@ int fa_forward_mla_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t 
                                      void* O, void* l, void* m,
                                      void* workspace, size_t workspace_bytes);
 
+/* The paged few-query forward for WIDE heads: fa_forward_paged's pools, table, lengths, fold and empty rows at more
+ * than 128 channels a head (Gemma-style 256-channel heads), with the tail rule and a sliding window in one entry point.
+ *   p, Q, K_pool [num_pages][kv_per_len][d][page], V_pool [num_pages][kv_per_len][v_d][page], block_table, max_pages,
+ *     page, num_pages, k_lens, kv_per_len = Hk, tail_causal, O, l, m: fa_forward_paged's, fp16.  Both pools must be
+ *     16-byte aligned.  The scale is 1 / sqrt(d).
+ *   window: 0 means no window.  window = W > 0 needs tail_causal != 0 (else FA_ERR_INVALID_ARGUMENT): query i stands
+ *     at pos = len - nq + i and sees the keys max(0, pos - W + 1) <= j <= pos.  W >= nk is the tail-causal call
+ *     itself, bit for bit.  With lo = max(0, len - nq - W + 1): keys below lo / 64 * 64 are never read and table
+ *     entries of pages wholly below that key are never loaded, like those past the last live page; the at most 63
+ *     keys between lo / 64 * 64 and lo are read and masked, so they must be finite.
+ * Envelope: fp16, seq_dims == 1, d % 64 == 0, v_d % 64 == 0, 64 <= d, v_d <= 256, max(d, v_d) > 128 (at or below
+ *   128: fa_forward_paged), kv_group >= 1, nq >= 1, R = kv_group * P <= 128 with P the smallest power of two >= nq,
+ *   page % 64 == 0, nk >= 1, and launch grids below 2^31 workgroups.  A well-formed problem outside it:
+ *   FA_ERR_UNSUPPORTED, nothing written.  Argument errors, FA_ERR_WORKSPACE_TOO_SMALL and b == 0: fa_forward_paged's.
+ * fa_forward_paged_wide_plan (host-only): out = {key chunks (0 outside the envelope), keys per chunk, P, R, blocks of
+ *   64 rows, 0}.  chunk = max(ceil(nk / 64) rounded up to 64 keys, 512 for R <= 64 or 1024 above), chunks =
+ *   ceil(nk / chunk): the un-windowed plan over the capacity, whatever the window (a workgroup whose chunk lies
+ *   outside [lo / 64 * 64, len) returns at once).  A pure function of the problem WITHOUT b.
+ * fa_forward_paged_wide_workspace_bytes (host-only): (b / kv_group) * blocks * chunks * 64 * (v_d + 3) floats rounded
+ *   up to 256 bytes; 0 outside the envelope.
+ * Not here: a ragged twin, FP8 pools, tree masks, query blocks past R = 128, and the reduced-launch window plan of
+ *   fa_forward_paged_window.  The write side is fa_append_paged, which takes any channel count. */
+int fa_forward_paged_wide_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]);
+size_t fa_forward_paged_wide_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page);
+int fa_forward_paged_wide(void* stream, const fa_problem* p, int32_t kv_group,
+                          const void* Q, const void* K_pool, const void* V_pool,
+                          const int32_t* block_table, int32_t max_pages, int32_t page, int64_t num_pages,
+                          const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal, int32_t window,
+                          void* O, void* l, void* m,
+                          void* workspace, size_t workspace_bytes);
+
 /* Fused K/V append: the write side of the four caches above. New tokens' keys and values are stored IN PLACE into a
  * ragged cache or into page pools, fp16 or FP8, by one kernel launch enqueued on `stream`: a forward enqueued after it
  * on that stream sees the tokens.  Every control value is device data; the host reads nothing and does not

@@ -84,6 +84,9 @@ EXPORTED_SYMBOLS = (
     "fa_forward_mla_paged_prefill_workspace_bytes",
     "fa_forward_mla_paged_prefill",
     "fa_forward_mla_paged_prefill_fp8",
+    "fa_forward_paged_wide_plan",
+    "fa_forward_paged_wide_workspace_bytes",
+    "fa_forward_paged_wide",
     "fa_append_ragged",
     "fa_append_paged",
     "fa_append_ragged_fp8",
@@ -265,6 +268,16 @@ def _declare(lib):
             forward.argtypes = ([vp, P, i32, vp, vp, vp, i32, i32, i64, vp, i32, ctypes.c_float] + ([vp] if fp8 else [])
                                 + [vp, vp, vp, vp, vp, ctypes.c_size_t])
             forward.restype = ctypes.c_int
+    # the paged forward at more than 128 channels a head: fa_forward_paged's arguments with `window` (0: none) after
+    # tail_causal, and a plan of six numbers.  (Absent as above.)
+    if hasattr(lib, "fa_forward_paged_wide"):
+        lib.fa_forward_paged_wide_plan.argtypes = [P, i32, i32, ctypes.POINTER(i32)]
+        lib.fa_forward_paged_wide_plan.restype = ctypes.c_int
+        lib.fa_forward_paged_wide_workspace_bytes.argtypes = [P, i32, i32]
+        lib.fa_forward_paged_wide_workspace_bytes.restype = ctypes.c_size_t
+        lib.fa_forward_paged_wide.argtypes = [vp, P, i32, vp, vp, vp, vp, i32, i32, i64, vp, i32, i32, i32,
+                                              vp, vp, vp, vp, ctypes.c_size_t]
+        lib.fa_forward_paged_wide.restype = ctypes.c_int
     # The fused K/V appends (include/fa_api.h): the same pieces again, the caches written instead of read; (k_scale,
     # v_scale) after an FP8 cache, (block_table, max_pages, page, num_pages) after a paged one.  (Absent as above.)
     for cache in DECODE_CACHES:

@@ -1460,6 +1460,102 @@ int fa_forward_mla_paged_prefill_fp8(void* stream, const fa_problem* p, int32_t 
                      num_pages, k_lens, tail_causal, softmax_scale, O, l, m, workspace, workspace_bytes);
 }
 
+// ---- the paged few-query forward at more than 128 channels a head (include/fa_api.h; DESIGN.md §3.23;
+// fa_fwd_f16_paged_wide.hip): the paged forward's checks and fold, the MLA decode's row blocks of 64 and its chunk
+// minimum, one entry point for the plain call, the tail rule and the window.  The plan is chunk_keys over the capacity
+// and a pure function of the problem without b, the lengths, the table, tail_causal or the window.
+constexpr int32_t kWideMaxD = 256, kWideBlockRows = 64;
+
+struct WidePlan {
+  int32_t nchunks, chunk, pitch, rows, nrb;
+};
+
+// (after check_paged)
+static WidePlan wide_plan(const fa_problem* p, int32_t kv_group, int32_t page) {
+  WidePlan s = {};
+  const int64_t nq = p->q_seq[0], nk = p->k_seq[0];
+  if (p->seq_dims == 1 && nq >= 1) {  // (the fold is reported outside the envelope too)
+    s.pitch = next_pow2((int32_t)nq);
+    s.rows = (int64_t)kv_group * s.pitch <= 0x7fffffff ? kv_group * s.pitch : 0x7fffffff;
+    s.nrb = (int32_t)(((int64_t)s.rows + kWideBlockRows - 1) / kWideBlockRows);
+  }
+  const bool inside = p->dtype == FA_F16 && p->seq_dims == 1 && p->d % 64 == 0 && p->d >= 64 && p->d <= kWideMaxD &&
+                      p->v_d % 64 == 0 && p->v_d >= 64 && p->v_d <= kWideMaxD && (p->d > 128 || p->v_d > 128) &&
+                      page % kSplitTile == 0 && nq >= 1 && nk >= 1;
+  if (!inside || (int64_t)kv_group * s.pitch > kGroupMaxRows) return s;
+  s.chunk = chunk_keys(nk, kSplitMaxChunks, chunk_min(s.rows <= 64), kSplitTile);
+  s.nchunks = (int32_t)((nk + s.chunk - 1) / s.chunk);
+  return s;
+}
+
+static size_t wide_ws_bytes(const fa_problem* p, int32_t kv_group, const WidePlan& s) {
+  return align_up((size_t)(p->b / kv_group) * (size_t)s.nrb * (size_t)s.nchunks *
+                  (size_t)fa::fewq_record_floats(p->v_d, kWideBlockRows) * sizeof(float));
+}
+
+int fa_forward_paged_wide_plan(const fa_problem* p, int32_t kv_group, int32_t page, int32_t out[6]) {
+  const int st = check_paged(p, kv_group, page);
+  if (st != FA_OK) return st;
+  if (!out) return set_error(FA_ERR_INVALID_ARGUMENT, "null plan buffer");
+  const WidePlan s = wide_plan(p, kv_group, page);
+  out[0] = s.nchunks; out[1] = s.chunk; out[2] = s.pitch; out[3] = s.rows; out[4] = s.nrb; out[5] = 0;
+  return FA_OK;
+}
+
+size_t fa_forward_paged_wide_workspace_bytes(const fa_problem* p, int32_t kv_group, int32_t page) {
+  if (check_paged(p, kv_group, page) != FA_OK) return 0;
+  const WidePlan s = wide_plan(p, kv_group, page);
+  return s.nchunks ? wide_ws_bytes(p, kv_group, s) : 0;
+}
+
+int fa_forward_paged_wide(void* stream, const fa_problem* p, int32_t kv_group, const void* Q, const void* K_pool,
+                          const void* V_pool, const int32_t* block_table, int32_t max_pages, int32_t page,
+                          int64_t num_pages, const int32_t* k_lens, int32_t kv_per_len, int32_t tail_causal,
+                          int32_t window, void* O, void* l, void* m, void* workspace, size_t workspace_bytes) {
+  const int st = check_paged(p, kv_group, page);
+  if (st != FA_OK) return st;
+  const int kst = check_kv_per_len(p->b / kv_group, kv_per_len);
+  if (kst != FA_OK) return kst;
+  if (window < 0) return set_error(FA_ERR_INVALID_ARGUMENT, "wide paged forward: window must be >= 0 (0: no window)");
+  if (window > 0 && !tail_causal)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "wide paged forward: a window requires tail_causal (the queries stand at the sequence's last positions)");
+  const int tst = check_table("paged forward", max_pages, page, num_pages, p->k_seq[0], "k_seq[0]");
+  if (tst != FA_OK) return tst;
+  const WidePlan wp = wide_plan(p, kv_group, page);
+  if (wp.nchunks == 0)
+    return set_error(FA_ERR_UNSUPPORTED,
+                     "wide paged forward: outside the fused envelope (fp16, 1d sequences, d % 64 == 0, v_d % 64 == 0, "
+                     "64 <= d, v_d <= 256, max(d, v_d) > 128, kv_group * pitch <= 128, nq >= 1, nk >= 1, page % 64 == 0)");
+  const int64_t bkv = p->b / kv_group, nq = p->q_seq[0];
+  if (bkv * wp.nrb * wp.nchunks > 0x7fffffff || (bkv * p->v_d * kv_group * nq + 255) / 256 > 0x7fffffff)
+    return set_error(FA_ERR_UNSUPPORTED, "wide paged forward: b = " + std::to_string(p->b) +
+                                             " needs a launch grid of 2^31 workgroups or more");
+  if (!workspace || workspace_bytes < wide_ws_bytes(p, kv_group, wp))
+    return set_error(FA_ERR_WORKSPACE_TOO_SMALL, "forward workspace is smaller than fa_forward_paged_wide_workspace_bytes()");
+  FA_DIAG_COUNT(0);
+  if (p->b == 0) return FA_OK;
+  if (!Q || !O || !l || !m) return set_error(FA_ERR_INVALID_ARGUMENT, "wide paged forward: null Q, O, l or m");
+  if (!k_lens) return set_error(FA_ERR_INVALID_ARGUMENT, "null k_lens");
+  if (!block_table) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null block_table");
+  if (!K_pool || !V_pool) return set_error(FA_ERR_INVALID_ARGUMENT, "paged forward: null K_pool or V_pool");
+  if ((reinterpret_cast<uintptr_t>(K_pool) | reinterpret_cast<uintptr_t>(V_pool)) & 15)
+    return set_error(FA_ERR_INVALID_ARGUMENT, "wide paged forward: K_pool and V_pool must be 16-byte aligned");
+  fa::PagedWideArgs pa = {};
+  fill_split(p, {wp.nchunks, wp.chunk, 0, p->k_seq[0], 0}, &pa.s);
+  fa::FwdArgs& a = pa.s.f;
+  a.Q = Q; a.K = K_pool; a.V = V_pool; a.O = O; a.l = l; a.m = m;
+  a.b = bkv;
+  pa.s.ws = static_cast<float*>(workspace);
+  pa.block_table = block_table; pa.k_lens = k_lens;
+  pa.g = kv_group; pa.pitch = wp.pitch; pa.log2_pitch = ilog2(wp.pitch); pa.nrb = wp.nrb;
+  pa.kv_heads = kv_per_len;
+  pa.max_pages = max_pages; pa.page = page;
+  pa.last_page = last_page(num_pages);
+  pa.tail_causal = tail_causal != 0;
+  pa.window = window < p->k_seq[0] ? window : 0;  // a window that reaches the capacity: the tail rule itself
+  return launched(fa::launch_fwd_f16_paged_wide(pa, static_cast<hipStream_t>(stream)), "Forward");
+}
+
 // ---- the fused K/V append of the same four caches (include/fa_api.h): every check on the host
 // before any device call, then one launch of fa_cache_append.hip's kernel.  No workspace, no plan.
 static int cache_append(void* stream, int64_t sequences, int32_t kv_heads, int32_t d, int32_t v_d, int32_t n_new,
@@ -1827,7 +1923,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 #endif
 
 const char* fa_build_info(void) {
-  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill, tree-masked draft decode, sliding-window prefill, MLA paged latent decode), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
+  return "tf_flash_attention_amd: src=" FA_SRC_HASH "; lib=" FA_LIB_KIND "; gfx950; fwd={mfma_f16 (+ split-key, grouped-query fold, ragged key lengths, paged K/V, fp8 e4m3 K/V cache, sliding-window decode, query-blocked prefill, tree-masked draft decode, sliding-window prefill, MLA paged latent decode, 256-channel paged decode), mfma_f32, mfma_f64, generic(f16,f32,f64)}; bwd={mfma_f16 (two-pass (+ split-key dQ, split-query dK/dV)), mfma_f32 (two-pass), mfma_f64 (two-pass, d<=256), generic(f16,f32,f64)}; merge={f16,f32,f64, 1..8 parts}; append={fused K/V append: ragged, paged x f16, fp8 e4m3}";
 }
 
 }  // extern "C"

@@ -207,6 +207,27 @@ struct MlaPrefillFp8Args {
 };
 hipError_t launch_fwd_f16_mla_prefill_fp8(const MlaPrefillFp8Args& pa8, hipStream_t s);
 
+// the paged few-query forward at more than 128 channels a head (fa_fwd_f16_paged_wide.hip): the paged forward's
+// pools, K [num_pages][kv_heads][d][page] and V [num_pages][kv_heads][v_d][page] halfs, and its fold of g query heads
+// x pitch query slots into rows, here in nrb blocks of 64.  s.f: Q / O / l / m of b * g slices, K / V the POOLS,
+// b = the K/V SLICES (sequences * kv_heads), rule.k.n = the capacity max_pages * page.  s.ws: the records
+// [b][nrb][nchunks] of stride 64; s.nchunks / s.chunk the plan over the capacity.
+struct PagedWideArgs {
+  SplitArgs s;
+  const int32_t* block_table;  // device: [sequences][max_pages], loaded entries clamped to [0, last_page]
+  const int32_t* k_lens;       // device: [sequences], clamped to [0, capacity]
+  int32_t g;                   // query heads per K/V head, >= 1
+  int32_t pitch, log2_pitch;   // rows per head: the smallest power of two >= nq; g * pitch <= 128
+  int32_t nrb;                 // blocks of 64 folded rows: 1 or 2
+  int32_t kv_heads;            // Hk: K/V slice bkv is head bkv % Hk of sequence bkv / Hk
+  int32_t max_pages, page, last_page;
+  int32_t tail_causal;         // != 0: query i sees keys j <= len - nq + i
+  int32_t window;              // 0: none; else 1 <= W < capacity with tail_causal: query i sees j > len - nq + i - W
+};
+// one partial workgroup per (K/V slice, row block, key chunk) and one merge thread per output element; the caller
+// has checked that both grids fit
+hipError_t launch_fwd_f16_paged_wide(const PagedWideArgs& pa, hipStream_t s);
+
 // split-key dQ pass of the fp16 backward (fa_bwd_f16_dq.hip): the plan of fa_api.hip plus the partials
 struct BwdSplitArgs {
   BwdArgs b;

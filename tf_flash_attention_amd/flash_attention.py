@@ -953,6 +953,8 @@ def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, 
 # (include/fa_api.h, "Paged few-query forward")
 # ----------------------------------------------------------------------------
 _PAGE_CONDITION = "the page size (the last axis of K_pool and V_pool) must be a multiple of 64 keys"
+_WIDE_ENVELOPE = (", or for paged_1d with float16 pools and no draft_mask: C % 64 == 0, Cv % 64 == 0, "
+                  "64 <= C, Cv <= 256, g * next_pow2(Nq) <= 128")
 
 
 def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returning_l_m=False, k_scale=None,
@@ -1003,6 +1005,15 @@ def paged_1d(Q, K_pool, V_pool, block_table, k_lens, tail_causal=False, returnin
     ``k_lens[s] - Nq`` and the draft slots its row names.  One call replaces a context call, a gather of the draft
     keys out of the pages, a masked attention over them and ``merge_partials``; the mask may be overwritten in place
     between replays like ``k_lens`` and ``block_table``.  ``draft_mask_from_parents`` builds it from a forest.
+
+    Wide heads (Gemma-style stacks, 256 channels a head): float16 pools with ``max(C, Cv) > 128`` and no
+    ``draft_mask`` run a kernel of their own (``fa_forward_paged_wide``) for ``C % 64 == 0``, ``Cv % 64 == 0``,
+    ``64 <= C, Cv <= 256`` and ``g * next_pow2(Nq) <= 128``: the plain call, ``tail_causal`` and ``window_size``,
+    with the same pools, table, lengths, empty rows, graph replay and page rules.  Under a window it launches the
+    capacity's chunks (those outside the window return at once) and ``W >= cap`` is the tail-causal call itself.
+    Out of scope at wide channels, and NotImplementedError: a ragged twin (``ragged_1d``), FP8 pools, tree masks
+    (``draft_mask``), query blocking past 128 rows (``paged_prefill_1d``, ``paged_window_prefill_1d``) and the
+    reduced window plan.  There is no wide fused append to need: ``paged_append_1d`` stores any channel count.
 
     Inference only (no gradient); float16 only; the page size must be a multiple of 64; outside the envelope the
     call raises NotImplementedError (there is no gather fallback).  More queries than the envelope's
@@ -1109,15 +1120,31 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
     mask = _decode_mask(what, draft_mask, tail_causal, window_size, Q, batch, nq)
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_ch)
     L = _lib.lib()
-    plan_name, ws_name, forward_name = decode_entry_points("paged", _decode_form(prefill, window, mask), fp8)
-    own = (prob, g, page) + (() if window is None else (window,))  # the plan functions' own arguments
+    # more than 128 channels a head: the wide forward where its plan reports chunks (float16 pools, no draft_mask,
+    # not query-blocked); its `window` argument stands behind tail_causal, 0 for none
+    wide = False
+    if not prefill and not fp8 and mask is None and max(k_ch, v_ch) > 128:
+        plan = (ctypes.c_int32 * 8)()
+        st = L.fa_forward_paged_wide_plan(prob, g, page, plan)
+        if st != _lib.FA_OK:
+            _raise_status(st, "Forward")
+        wide = plan[0] != 0
+    if wide:
+        plan_name, ws_name, forward_name = (
+            "fa_forward_paged_wide_plan", "fa_forward_paged_wide_workspace_bytes", "fa_forward_paged_wide")
+        # (a window implies the tail rule, which one query satisfies as it stands)
+        own, tail = (prob, g, page), (int(bool(tail_causal) or window is not None), 0 if window is None else window)
+    else:
+        plan_name, ws_name, forward_name = decode_entry_points("paged", _decode_form(prefill, window, mask), fp8)
+        own = (prob, g, page) + (() if window is None else (window,))  # the plan functions' own arguments
+        tail = (mask.data_ptr() if mask is not None else int(bool(tail_causal)) if window is None else window,)
     plan = (ctypes.c_int32 * 8)()
     st = getattr(L, plan_name)(*own, plan)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
     if plan[0] == 0:
         raise NotImplementedError(what + ": outside the fused envelope ("
-                                  + (_PREFILL_ENVELOPE if prefill else _RAGGED_ENVELOPE) + "; and "
+                                  + (_PREFILL_ENVELOPE if prefill else _RAGGED_ENVELOPE + _WIDE_ENVELOPE) + "; and "
                                   + _PAGE_CONDITION + "), got Q_shape = " + _shape_str(Q.shape) + ", K_pool_shape = "
                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape))
     _check_device_tensors(Q, K_pool, V_pool)
@@ -1131,9 +1158,7 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
         st = getattr(L, forward_name)(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
                                       V_pool.data_ptr(), *_scale_ptrs(fp8, k_scale, v_scale), block_table.data_ptr(),
-                                      max_pages, page, num_pages, k_lens.data_ptr(), hk,
-                                      mask.data_ptr() if mask is not None else int(bool(tail_causal)) if window is None
-                                      else window, O.data_ptr(),
+                                      max_pages, page, num_pages, k_lens.data_ptr(), hk, *tail, O.data_ptr(),
                                       l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
     if st != _lib.FA_OK:
         _raise_status(st, "Forward")
