@@ -213,6 +213,15 @@ def _stream_handle(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _new_o_l_m(Q, batch, v_ch, seq, l_dtype=torch.float32):
+    """The uninitialised outputs of a forward of ``Q``: O ``batch + (v_ch,) + seq`` and m ``batch + seq`` of Q's dtype,
+    l ``batch + seq`` of ``l_dtype``."""
+    dtype, device = Q.dtype, Q.device
+    return (torch.empty(batch + (v_ch,) + seq, dtype=dtype, device=device),
+            torch.empty(batch + seq, dtype=l_dtype, device=device),
+            torch.empty(batch + seq, dtype=dtype, device=device))
+
+
 def attention_forward(policy: str, seq_dims: int, Q, K, V, sync_mode, window_size=1, log2_stride_size=0,
                       is_causal=False, float16_op=None):
     """Op-level forward: returns (O, l, m).  Mirrors FlashAttentionForwardBase::Compute."""
@@ -225,10 +234,7 @@ def attention_forward(policy: str, seq_dims: int, Q, K, V, sync_mode, window_siz
         raise TypeError("Q, K and V must share one dtype")
     _check_device_tensors(Q, K, V)
     Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
-    l_dtype = torch.float32 if dt == _lib.F16 else Q.dtype
-    O = torch.empty(Qb + (V_ch,) + Qs, dtype=Q.dtype, device=Q.device)
-    l = torch.empty(Qb + Qs, dtype=l_dtype, device=Q.device)
-    m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
+    O, l, m = _new_o_l_m(Q, Qb, V_ch, Qs, torch.float32 if dt == _lib.F16 else Q.dtype)
     prob = _lib.make_problem(dt, _POLICIES[policy], seq_dims, sid, _prod(Qb), Qs, Ks, Q_ch, V_ch,
                              window_size, log2_stride_size, is_causal)
     L = _lib.lib()
@@ -582,9 +588,7 @@ def attention_forward_grouped(policy: str, seq_dims: int, Q, K, V, sync_mode, wi
         return attention_forward(policy, seq_dims, Q, _expand_groups(K, ch, g), _expand_groups(V, ch, g), sync_mode,
                                  window_size, log2_stride_size, is_causal)
     Q, K, V = Q.contiguous(), K.contiguous(), V.contiguous()
-    O = torch.empty(Qb + (V_ch,) + Qs, dtype=Q.dtype, device=Q.device)
-    l = torch.empty(Qb + Qs, dtype=torch.float32, device=Q.device)
-    m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
+    O, l, m = _new_o_l_m(Q, Qb, V_ch, Qs)
     ws_bytes = int(L.fa_forward_grouped_workspace_bytes(prob, g))
     with torch.cuda.device(Q.device):
         ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
@@ -733,12 +737,19 @@ def _scale_ptrs(fp8, k_scale, v_scale):
 decode_entry_points = _lib.decode_entry_points
 
 
-def _decode_form(prefill, window, mask=None):
-    """The form of a decode call: query-blocked (under a window or not), under a window (an int), tree-masked (a
-    tensor), or plain."""
-    if prefill and window is not None:
-        return "window_prefill"
-    return "prefill" if prefill else "tree" if mask is not None else "plain" if window is None else "window"
+def _decode_form(prefill, tail_causal, window, mask):
+    """(form, tail) of a decode call.  The form: query-blocked (under a window or not), tree-masked (``mask`` a tensor),
+    under a window (an int), or plain.  The tail is what stands in the forward's ``tail_causal`` argument: the device
+    mask of a tree, the window of a windowed form (which implies the tail rule), else the rule itself as 0 or 1."""
+    if mask is not None:
+        tail = mask.data_ptr()
+    else:
+        tail = int(bool(tail_causal)) if window is None else window
+    if prefill:
+        return ("prefill" if window is None else "window_prefill"), tail
+    if mask is not None:
+        return "tree", tail
+    return ("plain" if window is None else "window"), tail
 
 
 def _decode_window(what, window_size, tail_causal, nq):
@@ -776,6 +787,124 @@ def _decode_mask(what, draft_mask, tail_causal, window_size, Q, batch, nq):
     if window_size is not None:
         raise InvalidArgumentError(f"{what}: there is no windowed tree form; give draft_mask or window_size, not both")
     return draft_mask.contiguous()
+
+
+# How the messages name the batch shape that a block table and the per-sequence lengths follow.  The forwards and the
+# K/V appends read it off a tensor with a heads axis (Q, K_new) and say so; mla_paged_append_1d reads it off KV_new,
+# batch + (C, Nnew), which has no heads axis to leave out.
+_BATCH_WITHOUT_HEADS = "the batch shape without the heads"
+_BATCH = "the batch shape"
+
+
+def _index_tensors(batch, batch_phrase, *named):
+    """The checks of the tensors that the kernels find their keys by, as ``(name, tensor)`` pairs: each an int32
+    tensor; then ``block_table`` of shape ``batch + (max_pages,)`` and every other one (``k_lens``, ``new_lens``) of
+    shape ``batch``, which the messages call ``batch_phrase``."""
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    for name, t in named:
+        shape = tuple(t.shape)  # (read once: a tensor makes a new Size at every access)
+        if name == "block_table":
+            if shape[:-1] != batch or len(shape) != len(batch) + 1 or shape[-1] < 1:
+                raise InvalidArgumentError("The shape of block_table should be " + batch_phrase + " plus "
+                                           "(max_pages,), but block_table_shape = " + _shape_str(shape)
+                                           + ", batch_shape = " + _shape_str(batch) + " were received")
+        elif shape != batch:
+            raise InvalidArgumentError(f"The shape of {name} should be {batch_phrase}, but {name}_shape = "
+                                       + _shape_str(shape) + ", batch_shape = " + _shape_str(batch) + " were received")
+
+
+def _inference_only(what, *ts):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
+                           "detach its inputs")
+
+
+def _page_multiple(what, condition, page):
+    if page < 1 or page % 64 != 0:
+        raise NotImplementedError(what + ": " + condition + ", got page = " + str(page))
+
+
+def _paged_capacity(block_table, page):
+    """(max_pages, capacity) of a paged cache, the capacity checked.  (The padded cache's capacity is an axis of K, and
+    ragged_append_1d words its bound without the product.)"""
+    max_pages = int(block_table.shape[-1])
+    cap = max_pages * page
+    if cap > 2 ** 30:
+        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    return max_pages, cap
+
+
+def _kv_pools(K_pool, V_pool):
+    """(num_pages, Hk, C, Cv, page) of a pair of K/V pools, after the checks of their shapes."""
+    ks, vs = K_pool.shape, V_pool.shape  # (each read once: a tensor makes a new Size at every access)
+    if len(ks) != 4 or len(vs) != 4:
+        raise InvalidArgumentError("K_pool and V_pool should be [num_pages, Hk, channels, page], but K_pool_shape = "
+                                   + _shape_str(ks) + ", V_pool_shape = " + _shape_str(vs) + " were received")
+    num_pages, hk, k_ch, page = map(int, ks)
+    if (int(vs[0]), int(vs[1]), int(vs[3])) != (num_pages, hk, page):
+        raise InvalidArgumentError("K_pool and V_pool should agree in num_pages, Hk and page, but K_pool_shape = "
+                                   + _shape_str(ks) + ", V_pool_shape = " + _shape_str(vs) + " were received")
+    return num_pages, hk, k_ch, int(vs[2]), page
+
+
+def _latent_pool(KV_pool):
+    """(num_pages, C, page) of a latent pool, after the check of its shape."""
+    shape = KV_pool.shape
+    if len(shape) != 3:
+        raise InvalidArgumentError("KV_pool should be [num_pages, channels, page], but KV_pool_shape = "
+                                   + _shape_str(shape) + " was received")
+    return tuple(map(int, shape))
+
+
+def _paged_queries(Q):
+    """(batch, Hq, C, Nq) of the queries of a paged forward, after the check of their shape."""
+    shape = Q.shape
+    if len(shape) < 3:
+        raise InvalidArgumentError("Q should be batch + (Hq, C, Nq), but Q_shape = " + _shape_str(shape)
+                                   + " was received")
+    return tuple(shape[:-3]), int(shape[-3]), int(shape[-2]), int(shape[-1])
+
+
+def _launch_decode(routes, cache, scales, paged, k_lens, out, outside, returning_l_m, plan_len=8):
+    """The launch of every decode-family forward, after its checks.  Every forward of the library takes the same pieces
+    in the same order (see ``_lib._declare``): the stream; the problem and the heads, which also open the plan functions'
+    own arguments; the pointers of ``cache`` (Q, then the cache); the ``scales`` of an FP8 K/V cache; for a ``paged``
+    cache (block_table, max_pages, page, num_pages), else (); ``k_lens``; the route's tail; O, l, m and the workspace.
+
+    ``routes`` are ``(entry points, own, tail)`` in order of preference: the names of (plan, workspace_bytes, forward),
+    the plan functions' own arguments and the forward's arguments between ``k_lens`` and O.  The first route whose plan
+    (of ``plan_len`` numbers) reports chunks runs.  With none the call raises NotImplementedError of the parts of
+    ``outside`` joined, a tensor among them standing for its shape.  ``out`` is the (batch, channels, sequence) shapes
+    of O.  Returns ``O`` or ``(O, l, m)``."""
+    L = _lib.lib()
+    for (plan_name, ws_name, forward_name), own, tail in routes:
+        plan = (ctypes.c_int32 * plan_len)()
+        st = getattr(L, plan_name)(*own, plan)
+        if st != _lib.FA_OK:
+            _raise_status(st, "Forward")
+        if plan[0] != 0:
+            break
+    else:
+        raise NotImplementedError("".join(p if isinstance(p, str) else _shape_str(p.shape) for p in outside))
+    _check_device_tensors(*cache)
+    cache = tuple(map(torch.Tensor.contiguous, cache))
+    k_lens = k_lens.contiguous()
+    if paged:
+        block_table = paged[0].contiguous()
+        paged = (block_table.data_ptr(),) + paged[1:]
+    O, l, m = _new_o_l_m(cache[0], *out)
+    device = O.device
+    ws_bytes = int(getattr(L, ws_name)(*own))
+    with torch.cuda.device(device):
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=device)
+        st = getattr(L, forward_name)(_stream_handle(device), own[0], own[1], *map(torch.Tensor.data_ptr, cache), *scales,
+                                      *paged, k_lens.data_ptr(), *tail, O.data_ptr(), l.data_ptr(), m.data_ptr(),
+                                      ws.data_ptr(), ws_bytes)
+    if st != _lib.FA_OK:
+        _raise_status(st, "Forward")
+    return (O, l, m) if returning_l_m else O
 
 
 def draft_mask_from_parents(parents):
@@ -898,54 +1027,29 @@ _PREFILL_ENVELOPE = ("float16, 1d sequences, at most 128 channels, Nq >= 1, capa
 
 def _ragged_forward(what, prefill, Q, K, V, k_lens, tail_causal, returning_l_m, k_scale, v_scale, window_size,
                     draft_mask=None):
-    """``ragged_1d`` (``prefill`` False) and ``ragged_prefill_1d``: one validation, the entry points differ."""
+    """Every forward over the padded cache (``what`` names the public wrapper): ``ragged_1d`` plain, under a window
+    (``window_size``) or under a tree (``draft_mask``), and with ``prefill`` the query-blocked ``ragged_prefill_1d``
+    and, with a window, ``ragged_window_prefill_1d``.  One validation in one order; the form picks the entry points."""
     Qb, Qs, Q_ch, Kb, Ks, V_ch, g = verify_grouped_shapes(1, Q.shape, K.shape, V.shape)
     dt = _dtype_id(Q, True)
     kv_per_len = int(Kb[-1]) if Kb else 1
     fp8 = _kv_cache_scales("K and V", Q, K, V, kv_per_len, k_scale, v_scale)
-    if not isinstance(k_lens, torch.Tensor) or k_lens.dtype != torch.int32:
-        raise TypeError(f"k_lens must be an int32 tensor, got {getattr(k_lens, 'dtype', type(k_lens).__name__)}")
     batch = Qb[:-1]
-    if tuple(k_lens.shape) != tuple(batch):
-        raise InvalidArgumentError("The shape of k_lens should be the batch shape without the heads, but k_lens_shape = "
-                                   + _shape_str(k_lens.shape) + ", batch_shape = " + _shape_str(batch)
-                                   + " were received")
+    _index_tensors(batch, _BATCH_WITHOUT_HEADS, ("k_lens", k_lens))
     if k_lens.device != Q.device:
         raise InvalidArgumentError("k_lens must be on the device of Q, K and V")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, K, V)):
-        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
-                           "detach its inputs")
+    _inference_only(what, Q, K, V)
     window = _decode_window(what, window_size, tail_causal, int(Qs[0]))
     mask = _decode_mask(what, draft_mask, tail_causal, window_size, Q, batch, int(Qs[0]))
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(Qb), Qs, Ks, Q_ch, V_ch)
-    L = _lib.lib()
-    plan_name, ws_name, forward_name = decode_entry_points("ragged", _decode_form(prefill, window, mask), fp8)
     own = (prob, g) + (() if window is None else (window,))  # the plan functions' own arguments
-    plan = (ctypes.c_int32 * 8)()
-    st = getattr(L, plan_name)(*own, plan)
-    if st != _lib.FA_OK:
-        _raise_status(st, "Forward")
-    if plan[0] == 0:
-        raise NotImplementedError(what + ": outside the fused envelope ("
-                                  + (_PREFILL_ENVELOPE if prefill else _RAGGED_ENVELOPE) + "), got Q_shape = "
-                                  + _shape_str(Q.shape) + ", K_shape = " + _shape_str(K.shape) + ", V_shape = "
-                                  + _shape_str(V.shape))
-    _check_device_tensors(Q, K, V)
-    Q, K, V, k_lens = Q.contiguous(), K.contiguous(), V.contiguous(), k_lens.contiguous()
-    O = torch.empty(Qb + (V_ch,) + Qs, dtype=Q.dtype, device=Q.device)
-    l = torch.empty(Qb + Qs, dtype=torch.float32, device=Q.device)
-    m = torch.empty(Qb + Qs, dtype=Q.dtype, device=Q.device)
-    ws_bytes = int(getattr(L, ws_name)(*own))
-    with torch.cuda.device(Q.device):
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        st = getattr(L, forward_name)(_stream_handle(Q.device), prob, g, Q.data_ptr(), K.data_ptr(), V.data_ptr(),
-                                      *_scale_ptrs(fp8, k_scale, v_scale), k_lens.data_ptr(), kv_per_len,
-                                      mask.data_ptr() if mask is not None else int(bool(tail_causal)) if window is None
-                                      else window, O.data_ptr(),
-                                      l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
-    if st != _lib.FA_OK:
-        _raise_status(st, "Forward")
-    return (O, l, m) if returning_l_m else O
+    form, tail = _decode_form(prefill, tail_causal, window, mask)
+    return _launch_decode(
+        [(decode_entry_points("ragged", form, fp8), own, (kv_per_len, tail))],
+        cache=(Q, K, V), scales=_scale_ptrs(fp8, k_scale, v_scale), paged=(), k_lens=k_lens, out=(Qb, V_ch, Qs),
+        outside=(what, ": outside the fused envelope (", _PREFILL_ENVELOPE if prefill else _RAGGED_ENVELOPE,
+                 "), got Q_shape = ", Q, ", K_shape = ", K, ", V_shape = ", V),
+        returning_l_m=returning_l_m)
 
 
 # ----------------------------------------------------------------------------
@@ -1069,21 +1173,12 @@ def paged_window_prefill_1d(Q, K_pool, V_pool, block_table, k_lens, window_size,
 
 def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_causal, returning_l_m, k_scale, v_scale,
                    window_size, draft_mask=None):
-    """``paged_1d`` (``prefill`` False) and ``paged_prefill_1d``: one validation, the entry points differ."""
-    if len(K_pool.shape) != 4 or len(V_pool.shape) != 4:
-        raise InvalidArgumentError("K_pool and V_pool should be [num_pages, Hk, channels, page], but K_pool_shape = "
-                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
-                                   + " were received")
-    num_pages, hk, k_ch, page = (int(x) for x in K_pool.shape)
-    if (int(V_pool.shape[0]), int(V_pool.shape[1]), int(V_pool.shape[3])) != (num_pages, hk, page):
-        raise InvalidArgumentError("K_pool and V_pool should agree in num_pages, Hk and page, but K_pool_shape = "
-                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
-                                   + " were received")
-    v_ch = int(V_pool.shape[2])
-    if len(Q.shape) < 3:
-        raise InvalidArgumentError("Q should be batch + (Hq, C, Nq), but Q_shape = " + _shape_str(Q.shape)
-                                   + " was received")
-    batch, hq, q_ch, nq = tuple(Q.shape[:-3]), int(Q.shape[-3]), int(Q.shape[-2]), int(Q.shape[-1])
+    """Every forward over the K/V page pools (``what`` names the public wrapper): ``paged_1d`` plain, under a window
+    (``window_size``) or under a tree (``draft_mask``), on the wide route where that applies, and with ``prefill`` the
+    query-blocked ``paged_prefill_1d`` and, with a window, ``paged_window_prefill_1d``.  One validation in one order;
+    the form picks the entry points."""
+    num_pages, hk, k_ch, v_ch, page = _kv_pools(K_pool, V_pool)
+    batch, hq, q_ch, nq = _paged_queries(Q)
     if q_ch != k_ch:
         raise InvalidArgumentError("The channels of Q and K_pool should be the same, but Q_shape = "
                                    + _shape_str(Q.shape) + ", K_pool_shape = " + _shape_str(K_pool.shape)
@@ -1094,75 +1189,34 @@ def _paged_forward(what, prefill, Q, K_pool, V_pool, block_table, k_lens, tail_c
                                    + _shape_str(K_pool.shape) + " were received")
     dt = _dtype_id(Q, True)
     fp8 = _kv_cache_scales("K_pool and V_pool", Q, K_pool, V_pool, hk, k_scale, v_scale)
-    for name, t in (("block_table", block_table), ("k_lens", k_lens)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if tuple(block_table.shape[:-1]) != batch or len(block_table.shape) != len(batch) + 1 or block_table.shape[-1] < 1:
-        raise InvalidArgumentError("The shape of block_table should be the batch shape without the heads plus "
-                                   "(max_pages,), but block_table_shape = " + _shape_str(block_table.shape)
-                                   + ", batch_shape = " + _shape_str(batch) + " were received")
-    if tuple(k_lens.shape) != batch:
-        raise InvalidArgumentError("The shape of k_lens should be the batch shape without the heads, but k_lens_shape = "
-                                   + _shape_str(k_lens.shape) + ", batch_shape = " + _shape_str(batch)
-                                   + " were received")
+    _index_tensors(batch, _BATCH_WITHOUT_HEADS, ("block_table", block_table), ("k_lens", k_lens))
     if block_table.device != Q.device or k_lens.device != Q.device:
         raise InvalidArgumentError("block_table and k_lens must be on the device of Q, K_pool and V_pool")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, K_pool, V_pool)):
-        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
-                           "detach its inputs")
-    if page < 1 or page % 64 != 0:
-        raise NotImplementedError(what + ": " + _PAGE_CONDITION + ", got page = " + str(page))
-    g, max_pages = hq // hk, int(block_table.shape[-1])
-    cap = max_pages * page
-    if cap > 2 ** 30:
-        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    _inference_only(what, Q, K_pool, V_pool)
+    _page_multiple(what, _PAGE_CONDITION, page)
+    g = hq // hk
+    max_pages, cap = _paged_capacity(block_table, page)
     window = _decode_window(what, window_size, tail_causal, nq)
     mask = _decode_mask(what, draft_mask, tail_causal, window_size, Q, batch, nq)
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_ch)
-    L = _lib.lib()
+    routes = []
     # more than 128 channels a head: the wide forward where its plan reports chunks (float16 pools, no draft_mask,
     # not query-blocked); its `window` argument stands behind tail_causal, 0 for none
-    wide = False
     if not prefill and not fp8 and mask is None and max(k_ch, v_ch) > 128:
-        plan = (ctypes.c_int32 * 8)()
-        st = L.fa_forward_paged_wide_plan(prob, g, page, plan)
-        if st != _lib.FA_OK:
-            _raise_status(st, "Forward")
-        wide = plan[0] != 0
-    if wide:
-        plan_name, ws_name, forward_name = (
-            "fa_forward_paged_wide_plan", "fa_forward_paged_wide_workspace_bytes", "fa_forward_paged_wide")
         # (a window implies the tail rule, which one query satisfies as it stands)
-        own, tail = (prob, g, page), (int(bool(tail_causal) or window is not None), 0 if window is None else window)
-    else:
-        plan_name, ws_name, forward_name = decode_entry_points("paged", _decode_form(prefill, window, mask), fp8)
-        own = (prob, g, page) + (() if window is None else (window,))  # the plan functions' own arguments
-        tail = (mask.data_ptr() if mask is not None else int(bool(tail_causal)) if window is None else window,)
-    plan = (ctypes.c_int32 * 8)()
-    st = getattr(L, plan_name)(*own, plan)
-    if st != _lib.FA_OK:
-        _raise_status(st, "Forward")
-    if plan[0] == 0:
-        raise NotImplementedError(what + ": outside the fused envelope ("
-                                  + (_PREFILL_ENVELOPE if prefill else _RAGGED_ENVELOPE + _WIDE_ENVELOPE) + "; and "
-                                  + _PAGE_CONDITION + "), got Q_shape = " + _shape_str(Q.shape) + ", K_pool_shape = "
-                                  + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape))
-    _check_device_tensors(Q, K_pool, V_pool)
-    Q, K_pool, V_pool = Q.contiguous(), K_pool.contiguous(), V_pool.contiguous()
-    block_table, k_lens = block_table.contiguous(), k_lens.contiguous()
-    O = torch.empty(batch + (hq, v_ch, nq), dtype=Q.dtype, device=Q.device)
-    l = torch.empty(batch + (hq, nq), dtype=torch.float32, device=Q.device)
-    m = torch.empty(batch + (hq, nq), dtype=Q.dtype, device=Q.device)
-    ws_bytes = int(getattr(L, ws_name)(*own))
-    with torch.cuda.device(Q.device):
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        st = getattr(L, forward_name)(_stream_handle(Q.device), prob, g, Q.data_ptr(), K_pool.data_ptr(),
-                                      V_pool.data_ptr(), *_scale_ptrs(fp8, k_scale, v_scale), block_table.data_ptr(),
-                                      max_pages, page, num_pages, k_lens.data_ptr(), hk, *tail, O.data_ptr(),
-                                      l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
-    if st != _lib.FA_OK:
-        _raise_status(st, "Forward")
-    return (O, l, m) if returning_l_m else O
+        routes.append((("fa_forward_paged_wide_plan", "fa_forward_paged_wide_workspace_bytes", "fa_forward_paged_wide"),
+                       (prob, g, page),
+                       (hk, int(bool(tail_causal) or window is not None), 0 if window is None else window)))
+    own = (prob, g, page) + (() if window is None else (window,))  # the plan functions' own arguments
+    form, tail = _decode_form(prefill, tail_causal, window, mask)
+    routes.append((decode_entry_points("paged", form, fp8), own, (hk, tail)))
+    return _launch_decode(
+        routes, cache=(Q, K_pool, V_pool), scales=_scale_ptrs(fp8, k_scale, v_scale),
+        paged=(block_table, max_pages, page, num_pages), k_lens=k_lens, out=(batch + (hq,), v_ch, (nq,)),
+        outside=(what, ": outside the fused envelope (", _PREFILL_ENVELOPE if prefill else _RAGGED_ENVELOPE,
+                 "" if prefill else _WIDE_ENVELOPE, "; and ", _PAGE_CONDITION, "), got Q_shape = ", Q,
+                 ", K_pool_shape = ", K_pool, ", V_pool_shape = ", V_pool),
+        returning_l_m=returning_l_m)
 
 
 # ----------------------------------------------------------------------------
@@ -1250,14 +1304,8 @@ def mla_paged_prefill_1d(Q, KV_pool, block_table, k_lens, v_channels, tail_causa
 def _mla_paged(what, blocked, Q, KV_pool, block_table, k_lens, v_channels, tail_causal, softmax_scale, returning_l_m,
                kv_scale, draft_mask):
     """``mla_paged_1d`` (``blocked`` False) and ``mla_paged_prefill_1d``: one set of checks in one order."""
-    if len(KV_pool.shape) != 3:
-        raise InvalidArgumentError("KV_pool should be [num_pages, channels, page], but KV_pool_shape = "
-                                   + _shape_str(KV_pool.shape) + " was received")
-    num_pages, k_ch, page = (int(x) for x in KV_pool.shape)
-    if len(Q.shape) < 3:
-        raise InvalidArgumentError("Q should be batch + (Hq, C, Nq), but Q_shape = " + _shape_str(Q.shape)
-                                   + " was received")
-    batch, hq, q_ch, nq = tuple(Q.shape[:-3]), int(Q.shape[-3]), int(Q.shape[-2]), int(Q.shape[-1])
+    num_pages, k_ch, page = _latent_pool(KV_pool)
+    batch, hq, q_ch, nq = _paged_queries(Q)
     if q_ch != k_ch:
         raise InvalidArgumentError("The channels of Q and KV_pool should be the same, but Q_shape = "
                                    + _shape_str(Q.shape) + ", KV_pool_shape = " + _shape_str(KV_pool.shape)
@@ -1273,17 +1321,7 @@ def _mla_paged(what, blocked, Q, KV_pool, block_table, k_lens, v_channels, tail_
     if not fp8 and KV_pool.dtype != Q.dtype:
         raise TypeError(f"Q and KV_pool must share one dtype, got {Q.dtype} and {KV_pool.dtype}")
     _mla_kv_scale(fp8, kv_scale, Q.device, "Q")
-    for name, t in (("block_table", block_table), ("k_lens", k_lens)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if tuple(block_table.shape[:-1]) != batch or len(block_table.shape) != len(batch) + 1 or block_table.shape[-1] < 1:
-        raise InvalidArgumentError("The shape of block_table should be the batch shape without the heads plus "
-                                   "(max_pages,), but block_table_shape = " + _shape_str(block_table.shape)
-                                   + ", batch_shape = " + _shape_str(batch) + " were received")
-    if tuple(k_lens.shape) != batch:
-        raise InvalidArgumentError("The shape of k_lens should be the batch shape without the heads, but k_lens_shape = "
-                                   + _shape_str(k_lens.shape) + ", batch_shape = " + _shape_str(batch)
-                                   + " were received")
+    _index_tensors(batch, _BATCH_WITHOUT_HEADS, ("block_table", block_table), ("k_lens", k_lens))
     if block_table.device != Q.device or k_lens.device != Q.device:
         raise InvalidArgumentError("block_table and k_lens must be on the device of Q and KV_pool")
     draft_mask = _decode_mask(what, draft_mask, tail_causal, None, Q, batch, nq)
@@ -1292,56 +1330,31 @@ def _mla_paged(what, blocked, Q, KV_pool, block_table, k_lens, v_channels, tail_
     softmax_scale = float(softmax_scale)
     if not (softmax_scale > 0.0 and softmax_scale != float("inf")):
         raise InvalidArgumentError(f"softmax_scale must be positive and finite, got {softmax_scale!r}")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (Q, KV_pool)):
-        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
-                           "detach its inputs")
-    if page < 1 or page % 64 != 0:
-        raise NotImplementedError(what + ": " + _MLA_PAGE_CONDITION + ", got page = " + str(page))
+    _inference_only(what, Q, KV_pool)
+    _page_multiple(what, _MLA_PAGE_CONDITION, page)
     if v_channels > q_ch:
         raise NotImplementedError(what + ": the values are channels of the cached vectors, v_channels <= C, got "
                                   f"v_channels = {v_channels}, C = {q_ch}")
-    max_pages = int(block_table.shape[-1])
-    cap = max_pages * page
-    if cap > 2 ** 30:
-        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    max_pages, cap = _paged_capacity(block_table, page)
     if draft_mask is not None and nq > 128:
         raise NotImplementedError(what + ": a draft_mask takes at most 128 draft tokens (four mask words a row), got "
                                   f"Nq = {nq}")
     prob = _lib.make_problem(dt, _lib.FULL, 1, _lib.NONE_FRONT, _prod(batch) * hq, (nq,), (cap,), q_ch, v_channels)
-    L = _lib.lib()
     # one block of mla_paged_1d's fold holds the queries and there is no mask: the call is mla_paged_1d's
     blocked = blocked and (draft_mask is not None or hq * (1 << max(nq - 1, 0).bit_length()) > 512)
     entry = "fa_forward_mla_paged_prefill" if blocked else "fa_forward_mla_paged"
-    plan = (ctypes.c_int32 * 6)()
-    st = getattr(L, entry + "_plan")(prob, hq, page, plan)
-    if st != _lib.FA_OK:
-        _raise_status(st, "Forward")
-    if plan[0] == 0:
-        envelope = _MLA_ENVELOPE_BLOCKED if blocked else _MLA_ENVELOPE
-        raise NotImplementedError(what + ": outside the envelope (" + envelope + "; and " + _MLA_PAGE_CONDITION
-                                  + "), got Q_shape = " + _shape_str(Q.shape) + ", KV_pool_shape = "
-                                  + _shape_str(KV_pool.shape) + ", v_channels = " + str(v_channels))
-    _check_device_tensors(Q, KV_pool)
-    Q, KV_pool = Q.contiguous(), KV_pool.contiguous()
-    block_table, k_lens = block_table.contiguous(), k_lens.contiguous()
-    O = torch.empty(batch + (hq, v_channels, nq), dtype=Q.dtype, device=Q.device)
-    l = torch.empty(batch + (hq, nq), dtype=torch.float32, device=Q.device)
-    m = torch.empty(batch + (hq, nq), dtype=Q.dtype, device=Q.device)
-    ws_bytes = int(getattr(L, entry + "_workspace_bytes")(prob, hq, page))
-    with torch.cuda.device(Q.device):
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=Q.device)
-        head = (_stream_handle(Q.device), prob, hq, Q.data_ptr(), KV_pool.data_ptr(), block_table.data_ptr(),
-                max_pages, page, num_pages, k_lens.data_ptr(), int(bool(tail_causal)), softmax_scale)
-        tail = (O.data_ptr(), l.data_ptr(), m.data_ptr(), ws.data_ptr(), ws_bytes)
-        if blocked:
-            tail = (draft_mask.data_ptr() if draft_mask is not None else None,) + tail
-        if fp8:
-            st = getattr(L, entry + "_fp8")(*head, kv_scale.data_ptr() if kv_scale is not None else None, *tail)
-        else:
-            st = getattr(L, entry)(*head, *tail)
-    if st != _lib.FA_OK:
-        _raise_status(st, "Forward")
-    return (O, l, m) if returning_l_m else O
+    # the scale of an FP8 pool and the mask of the blocked form, both nullable, stand in front of O in that order
+    tail = (int(bool(tail_causal)), softmax_scale) + (
+        (kv_scale.data_ptr() if kv_scale is not None else None,) if fp8 else ()) + (
+        (draft_mask.data_ptr() if draft_mask is not None else None,) if blocked else ())
+    return _launch_decode(
+        [((entry + "_plan", entry + "_workspace_bytes", entry + ("_fp8" if fp8 else "")), (prob, hq, page), tail)],
+        cache=(Q, KV_pool), scales=(), paged=(block_table, max_pages, page, num_pages), k_lens=k_lens,
+        out=(batch + (hq,), v_channels, (nq,)),
+        outside=(what, ": outside the envelope (", _MLA_ENVELOPE_BLOCKED if blocked else _MLA_ENVELOPE, "; and ",
+                 _MLA_PAGE_CONDITION, "), got Q_shape = ", Q, ", KV_pool_shape = ", KV_pool, ", v_channels = ",
+                 str(v_channels)),
+        returning_l_m=returning_l_m, plan_len=6)
 
 
 def _mla_kv_scale(fp8, kv_scale, device, q):
@@ -1377,10 +1390,7 @@ def mla_paged_append_1d(KV_pool, KV_new, block_table, k_lens, new_lens=None, kv_
     pool must be contiguous (a copy would silently take the write) and its page a multiple of 64.  Inference only.
     Returns None."""
     what = "mla_paged_append_1d"
-    if len(KV_pool.shape) != 3:
-        raise InvalidArgumentError("KV_pool should be [num_pages, channels, page], but KV_pool_shape = "
-                                   + _shape_str(KV_pool.shape) + " was received")
-    num_pages, k_ch, page = (int(x) for x in KV_pool.shape)
+    num_pages, k_ch, page = _latent_pool(KV_pool)
     if num_pages < 1:
         raise InvalidArgumentError("The pool should hold a page, but KV_pool_shape = " + _shape_str(KV_pool.shape)
                                    + " was received")
@@ -1395,31 +1405,15 @@ def mla_paged_append_1d(KV_pool, KV_new, block_table, k_lens, new_lens=None, kv_
         raise TypeError("KV_pool must be float16 or an FP8 pool (float8_e4m3fn or uint8), got " + str(KV_pool.dtype))
     _mla_kv_scale(fp8, kv_scale, KV_pool.device, "KV_pool")
     ints = (("block_table", block_table), ("k_lens", k_lens)) + ((("new_lens", new_lens),) if new_lens is not None else ())
-    for name, t in ints:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if tuple(block_table.shape[:-1]) != batch or len(block_table.shape) != len(batch) + 1 or block_table.shape[-1] < 1:
-        raise InvalidArgumentError("The shape of block_table should be the batch shape plus (max_pages,), but "
-                                   "block_table_shape = " + _shape_str(block_table.shape) + ", batch_shape = "
-                                   + _shape_str(batch) + " were received")
-    for name, t in ints[1:]:
-        if tuple(t.shape) != batch:
-            raise InvalidArgumentError(f"The shape of {name} should be the batch shape, but {name}_shape = "
-                                       + _shape_str(t.shape) + ", batch_shape = " + _shape_str(batch) + " were received")
+    _index_tensors(batch, _BATCH, *ints)
     if KV_new.device != KV_pool.device or any(t.device != KV_pool.device for _, t in ints):
         raise InvalidArgumentError(", ".join(n for n, _ in ints) + " and KV_new must be on the device of KV_pool")
-    if torch.is_grad_enabled() and (KV_pool.requires_grad or KV_new.requires_grad):
-        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
-                           "detach its inputs")
+    _inference_only(what, KV_pool, KV_new)
     if not KV_pool.is_contiguous():
         raise InvalidArgumentError(what + ": KV_pool must be contiguous: the append writes in place, and a contiguous "
                                    "copy would silently take the write")
-    if page < 1 or page % 64 != 0:
-        raise NotImplementedError(what + ": " + _MLA_PAGE_CONDITION + ", got page = " + str(page))
-    max_pages = int(block_table.shape[-1])
-    cap = max_pages * page
-    if cap > 2 ** 30:
-        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    _page_multiple(what, _MLA_PAGE_CONDITION, page)
+    max_pages, cap = _paged_capacity(block_table, page)
     _check_device_tensors(KV_pool, KV_new)
     KV_new, block_table, k_lens = KV_new.contiguous(), block_table.contiguous(), k_lens.contiguous()
     new_lens = new_lens.contiguous() if new_lens is not None else None
@@ -1488,28 +1482,15 @@ def paged_append_1d(K_pool, V_pool, K_new, V_new, block_table, k_lens, new_lens=
     Lengths, ``new_lens``, scales, FP8 rounding, graph replay, the stream and the contiguous pools: as in
     ``ragged_append_1d``.  The page size must be a multiple of 64 (NotImplementedError otherwise: nothing here can
     read such a pool).  Inference only.  Returns None."""
-    if len(K_pool.shape) != 4 or len(V_pool.shape) != 4:
-        raise InvalidArgumentError("K_pool and V_pool should be [num_pages, Hk, channels, page], but K_pool_shape = "
-                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
-                                   + " were received")
-    num_pages, hk, k_ch, page = (int(x) for x in K_pool.shape)
-    if (int(V_pool.shape[0]), int(V_pool.shape[1]), int(V_pool.shape[3])) != (num_pages, hk, page):
-        raise InvalidArgumentError("K_pool and V_pool should agree in num_pages, Hk and page, but K_pool_shape = "
-                                   + _shape_str(K_pool.shape) + ", V_pool_shape = " + _shape_str(V_pool.shape)
-                                   + " were received")
-    v_ch = int(V_pool.shape[2])
+    num_pages, hk, k_ch, v_ch, page = _kv_pools(K_pool, V_pool)
     if num_pages < 1:
         raise InvalidArgumentError("The pools should hold a page, but K_pool_shape = " + _shape_str(K_pool.shape)
                                    + " was received")
     batch = tuple(K_new.shape[:-3]) if len(getattr(K_new, "shape", ())) >= 3 else ()
     n_new = _append_checks("paged_append_1d", "K_pool and V_pool", K_pool, V_pool, K_new, V_new, batch, hk, k_ch, v_ch,
                            (("block_table", block_table), ("k_lens", k_lens)), new_lens, k_scale, v_scale)
-    if page < 1 or page % 64 != 0:
-        raise NotImplementedError("paged_append_1d: " + _PAGE_CONDITION + ", got page = " + str(page))
-    max_pages = int(block_table.shape[-1])
-    cap = max_pages * page
-    if cap > 2 ** 30:
-        raise InvalidArgumentError("The capacity max_pages * page = " + str(cap) + " is above 2^30 keys")
+    _page_multiple("paged_append_1d", _PAGE_CONDITION, page)
+    max_pages, cap = _paged_capacity(block_table, page)
     _append_call("paged", K_pool, V_pool, K_new, V_new, batch, hk, k_ch, v_ch, n_new, cap,
                  (block_table, max_pages, page, num_pages), k_lens, new_lens, k_scale, v_scale)
 
@@ -1529,23 +1510,10 @@ def _append_checks(what, caches, K, V, K_new, V_new, batch, hk, k_ch, v_ch, int_
                                    + ", V_new_shape = " + _shape_str(V_new.shape) + " were received")
     _kv_cache_scales(caches, K_new, K, V, hk, k_scale, v_scale, q="K_new and V_new")
     int_tensors = int_tensors + ((("new_lens", new_lens),) if new_lens is not None else ())
-    for name, t in int_tensors:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-            raise TypeError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    for name, t in int_tensors:
-        if name == "block_table":
-            if tuple(t.shape[:-1]) != batch or len(t.shape) != len(batch) + 1 or t.shape[-1] < 1:
-                raise InvalidArgumentError("The shape of block_table should be the batch shape without the heads plus "
-                                           "(max_pages,), but block_table_shape = " + _shape_str(t.shape)
-                                           + ", batch_shape = " + _shape_str(batch) + " were received")
-        elif tuple(t.shape) != batch:
-            raise InvalidArgumentError(f"The shape of {name} should be the batch shape without the heads, but {name}_shape = "
-                                       + _shape_str(t.shape) + ", batch_shape = " + _shape_str(batch) + " were received")
+    _index_tensors(batch, _BATCH_WITHOUT_HEADS, *int_tensors)
     if any(t.device != K.device for t in (V, K_new, V_new)) or any(t.device != K.device for _, t in int_tensors):
         raise InvalidArgumentError(", ".join(n for n, _ in int_tensors) + f", K_new and V_new must be on the device of {caches}")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (K, V, K_new, V_new)):
-        raise RuntimeError(what + " is inference only and has no gradient; call it under torch.no_grad() or "
-                           "detach its inputs")
+    _inference_only(what, K, V, K_new, V_new)
     if not K.is_contiguous() or not V.is_contiguous():
         raise InvalidArgumentError(f"{what}: {caches} must be contiguous: the append writes in place, and a contiguous "
                                    "copy would silently take the write")
